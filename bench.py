@@ -16,7 +16,17 @@ synthetic CoM preview systems, inputs already resident in HBM.
           `--scaling weak` instead keeps 65536 instances per GPU with per-rank seeds (rank 0 = configs[2]).
 Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline needs: set-up, spin-up and warm-up, the K timed steps, the outputs when --dump-outputs DIR
+is given, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration).  Everything else it can measure
+or check runs only with --full: the cold-clock steps, the per-kernel timing, the roofline, the iteration statistics, the N > 1 check of
+what rank 0 gathered, and the objects below (--no-cpu-baseline / --no-extra leave out the last two).
+
+  --dump-outputs DIR -- after the timed steps, rank 0 writes what the last step handed its caller, in float64: DIR/control.npy [b, n],
+                  DIR/trajectory.npy [b, nx (N + 1)], DIR/status.npy [b], DIR/iter.npy [b, 2] -- every instance when they fit into
+                  DUMP_BYTES, else the same fixed, seeded sample of instances (sorted) in all four.  The inputs are seeded, so two
+                  builds of the project can be compared output for output.
+
+Extra objects in the --full line:
   roofline     -- the launches that are the hot path (copra_lmpc_axis_kernel since round 6: one (instance, axis) per lane -- LQ sweep, roll-out
                   and the whole active-set iteration, gains in registers; copra_lmpc_fused_ric_kernel behind it for the handful of instances
                   it leaves): algorithmic bytes per launch (2016 B/solve: A,B,d,x0 in, U,X out) / their duration from HIP events
@@ -50,6 +60,26 @@ PMC_SUMMARY = os.path.join("profiles", "r06", "headline_rocprof_summary.json")  
 
 
 SPIN_UP_SOLVES = 40  # untimed solves before the warm-up steps (clock ramp; see main)
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs: at most this many bytes of arrays (64 MB with room for the .npy headers)
+DUMP_SEED = 0  # the sample of instances written when the whole result does not fit
+
+
+def dump_outputs(out_dir, views, batch):
+    """--dump-outputs: the four result arrays of the last timed step (device views into the result slab), as float64 .npy files"""
+    import numpy as np
+    import torch
+    names = ("control", "trajectory", "status", "iter")
+    per_instance = sum(8 * (views[k].numel() // batch) for k in names)
+    take = min(batch, DUMP_BYTES // per_instance)
+    pick = None
+    if take < batch:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(batch, take, replace=False))
+        pick = torch.from_numpy(idx).to(views["control"].device)
+    os.makedirs(out_dir, exist_ok=True)
+    for k in names:
+        a = views[k] if pick is None else views[k][pick]
+        np.save(os.path.join(out_dir, k + ".npy"), a.cpu().numpy().astype(np.float64))
+
 
 def cpu_model():
     try:
@@ -76,9 +106,6 @@ def host_cores():
     except Exception:
         pass
     return cores, hw, note
-
-
-from tools.bench_extra import extra_measurements  # noqa: E402  (the side measurements: tools/bench_extra.py)
 
 
 def spawn_ranks(n_gpus):
@@ -115,8 +142,14 @@ def main():
     ap.add_argument("--scaling", choices=["auto", "weak"], default="auto",
                     help="auto: N > 1 shards ONE seed-2 batch of 32768 N instances (N = 8: BASELINE configs[3]); "
                          "weak: 65536 instances per GPU with per-rank seeds")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the measurements outside the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: cold clock, kernel time, roofline, iteration "
+                         "statistics, the N > 1 gather check, cpu_baseline and extra")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/<name>.npy (float64; a fixed, seeded sample of the "
+                         "instances when the whole result exceeds DUMP_BYTES)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the measurements outside the timed region")
     ap.add_argument("--dense-hessian", action="store_true",
                     help="hand the TrajectoryCost over as a full-size entry (126x126 M): the Hessian is then built by "
                          "the dense v_mfma_f64_16x16x4 Psi'WPsi contraction instead of the block-diagonal prefix sums")
@@ -152,7 +185,7 @@ def main():
             raise SystemExit("--selftest-rccl2 needs two visible GPUs (found %d)" % torch.cuda.device_count())
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", "29531", os.path.abspath(__file__), "--gpus", "2", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--payload", args.payload, "--no-extra"]
+               "--payload", args.payload, "--full", "--no-extra"]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=1800)
         line = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 and r.stdout.strip() else None
         mg = (line or {}).get("multi_gpu_check", {})
@@ -261,7 +294,7 @@ def main():
                       payload_bytes=payload_bytes)
     # the device at the clock it has when work arrives after an idle period (see below): a few timed steps BEFORE the spin-up
     cold_ms = None
-    if world == 1 and not comm_path:
+    if args.full and world == 1 and not comm_path:
         solve_into(views0, 0)  # (module load, LDS opt-in, layout controller)
         torch.cuda.synchronize()
         time.sleep(0.5)
@@ -312,10 +345,12 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, slabs[loop.last][1], batch)
 
     # ---- N > 1: rank 0 verifies what it gathered (after the timed region) ----
     multi = None
-    if comm_path:
+    if comm_path and args.full:
         ok_sum, sums = loop.verify()
         if rank == 0:
             sent = payload_bytes if payload_bytes is not None else slabs[0][0].numel()
@@ -353,23 +388,52 @@ def main():
                 multi.update({"oracle_sample_per_shard": 16, "instances_checked": checked, "max_rel_u_err": worst,
                               "status_agree": agree})
 
-    # device time of the dominant kernel: HIP events recorded by the C ABI around the launch on `stream`
-    # (measured in a separate short loop so that the event sync does not perturb the timed region)
-    eng.set_outputs(views0["control"], views0["trajectory"], views0["status"], views0["iter"])
-    for _ in range(min(args.steps, 10)):
-        eng.solve(stream)
-        kernel_s.append(eng.last_first_tier_seconds())  # (the dominant kernel alone: what rocprofv3's kernel trace shows)
-    torch.cuda.synchronize()
-    out_u, out_s, out_i = views0["control"], views0["status"], views0["iter"]
-    status = out_s.cpu().numpy()
-    iters = out_i.cpu().numpy()
-    n_ok = int((status == 0).sum())
-    lane_ran, lane_done = eng.lane_pass_info()  # (the one-instance-per-lane pass in front of the first tier, lmpc_lane.hpp)
-
     line = None
     if rank == 0:
-        total = global_batch * args.steps
-        value = total / elapsed
+        line = {
+            "metric": "MPC solves/sec (batched) at (nx=6,nu=3,N=20); max |u-u_ref|",
+            "value": global_batch * args.steps / elapsed,
+            "unit": "solves/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "spin_up_solves": spin_up_done,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": workload_name,
+                       "hessian": "dense MFMA f64 contraction (full-size cost entry)" if args.dense_hessian
+                       else "none (Riccati stage form: the condensed Hessian is never built; per-step cost entries)",
+                       "structure": ("the CoM model's three axes are decoupled (BASELINE configs[2] as specified): every (instance, axis) is solved by one "
+                                     "lane of copra_lmpc_axis_kernel, systems checked per instance; the same workload on coupled systems runs the "
+                                     "round-5 pair: extra.headline_with_coupled_axes_batch65536"),
+                       "batch_per_gpu": batch, "global_batch": global_batch, "nvar": n, "ineq_rows": 63,
+                       "bound_rows": 2 * n,
+                       "parallelism": ("contiguous batch shards x%d + 1 RCCL gather/step (%s)"
+                                       % (world, "overlapped with the next solve" if overlap else "synchronous"))
+                       if world > 1 else "single GPU"},
+        }
+        if multi is not None:
+            line["multi_gpu_check"] = multi
+
+    if args.full:
+        # device time of the dominant kernel: HIP events recorded by the C ABI around the launch on `stream`
+        # (measured in a separate short loop so that the event sync does not perturb the timed region)
+        eng.set_outputs(views0["control"], views0["trajectory"], views0["status"], views0["iter"])
+        for _ in range(min(args.steps, 10)):
+            eng.solve(stream)
+            kernel_s.append(eng.last_first_tier_seconds())  # (the dominant kernel alone: what rocprofv3's kernel trace shows)
+        torch.cuda.synchronize()
+        out_u, out_s, out_i = views0["control"], views0["status"], views0["iter"]
+        status = out_s.cpu().numpy()
+        iters = out_i.cpu().numpy()
+        n_ok = int((status == 0).sum())
+        lane_ran, lane_done = eng.lane_pass_info()  # (the one-instance-per-lane pass in front of the first tier, lmpc_lane.hpp)
+
+    if rank == 0 and args.full:
         kern = float(np.mean(kernel_s))
         alg_bytes = 8 * (nx * nx + nx * nu + 2 * nx) + 8 * (n + X)  # 528 in + 1488 out = 2016 B / solve
         achieved = alg_bytes * batch / kern / 1e9
@@ -425,33 +489,9 @@ def main():
             except Exception:
                 traffic = None
         hist = np.bincount(np.minimum(iters[:, 0], 15), minlength=16)
-        line = {
-            "metric": "MPC solves/sec (batched) at (nx=6,nu=3,N=20); max |u-u_ref|",
-            "value": value,
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "spin_up_solves": spin_up_done,
+        line.update({
             "cold_clock_ms_per_step": cold_ms,  # five steps after half a second of idle, before the spin-up: the clock a sporadic caller gets
             "cold_clock_solves_per_s": (batch / (cold_ms * 1e-3)) if cold_ms else None,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": workload_name,
-                       "hessian": "dense MFMA f64 contraction (full-size cost entry)" if args.dense_hessian
-                       else "none (Riccati stage form: the condensed Hessian is never built; per-step cost entries)",
-                       "structure": ("the CoM model's three axes are decoupled (BASELINE configs[2] as specified): every (instance, axis) is solved by one "
-                                     "lane of copra_lmpc_axis_kernel, systems checked per instance; the same workload on coupled systems runs the "
-                                     "round-5 pair: extra.headline_with_coupled_axes_batch65536"),
-                       "batch_per_gpu": batch, "global_batch": global_batch, "nvar": n, "ineq_rows": 63,
-                       "bound_rows": 2 * n,
-                       "parallelism": ("contiguous batch shards x%d + 1 RCCL gather/step (%s)"
-                                       % (world, "overlapped with the next solve" if overlap else "synchronous"))
-                       if world > 1 else "single GPU"},
             "solved_ok": n_ok,
             "first_kernel": {"kernel": "copra_lmpc_axis_kernel" if axis_ran else ("copra_lmpc_lane_kernel" if lane_ran else "copra_lmpc_fused_ric_kernel"),
                              "finished": lane_done, "left_to_the_first_tier": (batch - lane_done) if lane_ran else None,
@@ -485,11 +525,9 @@ def main():
                               "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                               "frac": (issue["executed_fp64_tflops"] / FP64_PEAK_TFLOPS) if issue.get("executed_fp64_tflops") else None,
                               "source": traffic_src, "stale": traffic_stale},
-        }
-        if multi is not None:
-            line["multi_gpu_check"] = multi
+        })
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         cores, hw, quota_note = host_cores()
@@ -534,7 +572,8 @@ def main():
         line["max_rel_x_err_floor_1e-6"] = parity_rel(xdev[ok], ref["trajectory"][ok], floor=1e-6)
         line["iterations_agree"] = bool((ref["iter"][ok] == iters[:sample][ok]).all())
         line["status_agree"] = bool((ref["status"] == status[:sample]).all())
-    if rank == 0 and world == 1 and not args.no_extra and not comm_path and not args.dense_hessian:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not comm_path and not args.dense_hessian:
+        from tools.bench_extra import extra_measurements  # (the side measurements: tools/bench_extra.py)
         eng.close()
         try:
             line["extra"] = extra_measurements(np, torch, dev)

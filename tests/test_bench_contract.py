@@ -13,7 +13,8 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 
 
 def _run(*extra):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4096",
+    """a --full run: the line with everything the benchmark measures and checks besides the headline"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--batch", "4096",
                         *extra], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = r.stdout.strip().splitlines()[-1]
@@ -24,6 +25,42 @@ def _run(*extra):
     rf = out["roofline"]
     assert rf["bound"] == "hbm" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
     return out
+
+
+def test_dump_outputs_writes_the_last_step_in_float64_within_64_mb(tmp_path):
+    """--dump-outputs on result slabs in host memory: every instance when the four arrays fit, else one fixed, sorted sample of
+    instances for all four arrays, the same from call to call; float64, at most 64 MB in all"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from copra_amd.sharding import alloc_result_slab
+    n, X = 60, 126
+    for batch in (1000, 65536):
+        _, v = alloc_result_slab(batch, n, X, torch.device("cpu"))
+        ids = torch.arange(batch, dtype=torch.float64)
+        v["control"].copy_(ids[:, None].expand(batch, n))
+        v["trajectory"].copy_(-ids[:, None].expand(batch, X))
+        v["status"].copy_((ids % 3).to(torch.int32))
+        v["iter"].copy_(torch.stack([ids % 7, ids % 5], 1).to(torch.int32))
+        outs = []
+        for k in range(2):
+            d = os.path.join(str(tmp_path), "b%d_%d" % (batch, k))
+            bench.dump_outputs(d, v, batch)
+            outs.append({name: np.load(os.path.join(d, name + ".npy")) for name in ("control", "trajectory", "status", "iter")})
+            assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 1000 * 1000
+        got = outs[0]
+        assert all(a.dtype == np.float64 for a in got.values())
+        idx = got["control"][:, 0].astype(np.int64)
+        if batch == 1000:
+            assert (idx == np.arange(batch)).all()
+        else:
+            assert 0 < len(idx) < batch and (np.diff(idx) > 0).all()
+        assert got["control"].shape == (len(idx), n) and got["trajectory"].shape == (len(idx), X)
+        assert (got["trajectory"] == -idx[:, None]).all() and (got["status"] == idx % 3).all()
+        assert (got["iter"] == np.stack([idx % 7, idx % 5], 1)).all()
+        for name in got:
+            assert np.array_equal(got[name], outs[1][name]), name
 
 
 def test_plain_multi_gpu_command_starts_its_own_ranks():
@@ -40,6 +77,36 @@ def test_plain_multi_gpu_command_starts_its_own_ranks():
     assert "launch with torch.distributed.run" not in r.stderr
     # (the launcher ends the sibling as soon as one rank fails: on a loaded machine the slower one may not reach its own check)
     assert "rank 0 of 2" in r.stderr or "rank 1 of 2" in r.stderr, r.stderr[-1500:]
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """a plain run measures the headline and nothing else; --dump-outputs hands back the last timed step's results, which are the
+    CPU path's on an oracle sample of the seeded batch"""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import pyoracle
+    from copra_amd import workloads
+    batch = 4096
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", str(batch),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert KEYS - {"roofline"} <= set(out), KEYS - set(out)
+    assert out["unit"] == "solves/s" and out["value"] > 0 and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - batch / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+    for key in ("roofline", "kernel_ms", "cold_clock_ms_per_step", "solved_ok", "cpu_baseline", "extra"):
+        assert key not in out, key
+    res = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("control", "trajectory", "status", "iter")}
+    assert all(a.dtype == np.float64 for a in res.values())
+    assert res["control"].shape == (batch, 60) and res["trajectory"].shape == (batch, 126) and res["iter"].shape == (batch, 2)
+    assert (res["status"] == 0).all()
+    wl = workloads.com_preview(batch, N=20, seed=1)
+    pick = np.linspace(0, batch - 1, 32).astype(int)
+    ref = pyoracle.lmpc_solve_batch(wl["A"][pick], wl["B"][pick], wl["d"][pick], wl["x0"][pick], wl["N"], wl["costs"], wl["cstrs"])
+    assert (res["status"][pick] == ref["status"]).all() and (res["iter"][pick] == ref["iter"]).all()
+    for k in ("control", "trajectory"):
+        assert np.nanmax(np.abs(res[k][pick] - ref[k]) / np.maximum(np.abs(ref[k]), 1e-3)) <= 1e-6, k
 
 
 @pytest.mark.gpu
@@ -100,7 +167,7 @@ def test_world_2_rccl_selftest_when_two_gpus_are_visible():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert json.loads(r.stdout.strip().splitlines()[-1])["selftest_rccl2"] is True
     # and the plain command the contract documents: no launcher, the parent starts the two ranks
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extra"],
                        capture_output=True, text=True, timeout=1800, env={k: v for k, v in os.environ.items() if k != "WORLD_SIZE"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

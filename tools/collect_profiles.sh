@@ -28,7 +28,7 @@ python tools/pmc_summary.py $O/c5_stats $O/c5_fetch $O/c5_write $O/c5_sq > profi
 find $O/c5_stats -name "*kernel_stats.csv" -exec cp {} profiles/r02/config5_kernel_stats.csv \;
 cp profiles/r02/*.json profiles/r02/*.csv $O/ 2>/dev/null || true
 # ---- the bench line itself (with cpu_baseline and extra) ----
-python bench.py --steps 20 --warmup 3 > $O/bench_r02.json 2> $O/bench_r02.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench_r02.json 2> $O/bench_r02.err
 tail -c 3000 $O/bench_r02.json
 head -5 profiles/r02/headline_kernel_stats.csv
 head -5 profiles/r02/config5_kernel_stats.csv

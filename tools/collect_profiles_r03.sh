@@ -60,7 +60,7 @@ python tools/sweep_shapes.py 2>&1 | grep -v amdgpu.ids > $R/shape_sweep.txt || t
 python tools/sweep_shapes.py --specialise 2>&1 | grep -v amdgpu.ids > $R/shape_sweep_specialised.txt || true
 cp $R/*.json $R/*.csv $R/*.txt $O/ 2>/dev/null || true
 # ---- the bench line itself (with cpu_baseline and extra) ----
-python bench.py --steps 20 --warmup 3 > $O/bench_r03.json 2> $O/bench_r03.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench_r03.json 2> $O/bench_r03.err
 cp $O/bench_r03.json $R/bench_line_final.json
 tail -c 1500 $O/bench_r03.json
 head -4 $R/headline_kernel_stats.csv

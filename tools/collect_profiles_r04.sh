@@ -64,7 +64,7 @@ python tools/exp/shared_tick_shapes.py 2>&1 | grep -v amdgpu.ids > $R/shared_tic
 (python tests/fuzz/fuzz_dense_qp.py 1000 800 2>&1 | grep -v amdgpu.ids) > $R/fuzz_dense_qp.txt || true
 (python tests/fuzz/fuzz_modes.py 0 400 2>&1 | grep -v amdgpu.ids | grep " <\|ERROR\|mismatching" | cut -c1-400) > $R/fuzz_engine_modes.txt || true
 # ---- the bench line itself (with cpu_baseline and extra): AFTER the summaries, so that its roofline.traffic is the one just measured ----
-python bench.py --steps 20 --warmup 3 > $O/bench_r04.json 2> $O/bench_r04.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench_r04.json 2> $O/bench_r04.err
 cp $O/bench_r04.json $R/bench_line_final.json
 # (only gpurun_out/ travels back from the box: the summaries go there as well, under their own directory)
 mkdir -p $O/profiles_r04 && cp $R/* $O/profiles_r04/

@@ -58,7 +58,7 @@ python tools/exp/truth_distances.py 2>&1 | grep -v amdgpu.ids > $R/truth_distanc
 (python tests/fuzz/fuzz_modes.py 0 420 2>&1 | grep -v amdgpu.ids | grep " <\|ERROR\|mismatching" | cut -c1-400) > $R/fuzz_engine_modes.txt || true
 (python tests/fuzz/fuzz_vs_oracle.py 0 1500 48 2>&1 | grep -v amdgpu.ids | tail -40) > $R/fuzz_random_controllers.txt || true
 # ---- the bench line itself (with cpu_baseline and extra): AFTER the summaries, so that its roofline.traffic is the one just measured ----
-python bench.py --warmup 3 > $O/bench_r06.json 2> $O/bench_r06.err
+python bench.py --full --warmup 3 > $O/bench_r06.json 2> $O/bench_r06.err
 cp $O/bench_r06.json $R/bench_line_final.json
 mkdir -p $O/profiles_r06 && cp $R/* $O/profiles_r06/
 tail -c 1500 $O/bench_r06.json
