@@ -300,6 +300,8 @@ def lib():
         L.copra_batch_set_cost_reference.argtypes = [vp, C.c_int, vp, C.c_int]
         L.copra_batch_set_cost_reference_all.restype = C.c_int
         L.copra_batch_set_cost_reference_all.argtypes = [vp, C.c_int, vp, C.c_int]
+        L.copra_batch_set_cost_weights.restype = C.c_int
+        L.copra_batch_set_cost_weights.argtypes = [vp, C.c_int, vp, C.c_int]
         L.copra_batch_set_shared_system.restype = C.c_int
         L.copra_batch_set_shared_system.argtypes = [vp, vp, vp, vp, C.c_int]
         L.copra_batch_set_outputs.restype = C.c_int

@@ -40,7 +40,10 @@ class BatchLMPC:
         self.X = self.nx * (self.N + 1)
         self._keep = []
         self._ref_keep = {}  # torch tensors used in place as per-instance cost references, by cost index
+        self._w_keep = {}  # ... and as per-instance cost weights
         cc = _capi.pack_costs(costs, self._keep)
+        # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
+        self._cost_rows = [None if cc[i].kind == _capi.COST_KINDS["dense"] else int(cc[i].rows) for i in range(len(costs))]
         kk = _capi.pack_cstrs(cstrs, self._keep)
         dims = _capi.Dims(self.nx, self.nu, self.N, self.batch)
         self._h = C.c_void_p()
@@ -185,6 +188,33 @@ class BatchLMPC:
             pb = np.ascontiguousarray(p, dtype=np.float64)
             assert pb.shape[0] == self.batch
             _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), pb.ctypes.data, 0))
+
+    def set_cost_weights(self, cost_index, w):
+        """per-instance weights of cost `cost_index` (copra_batch_set_cost_weights): w of shape (batch, rows) with the rows of that
+        cost as created (numpy: copied; a torch CUDA float64 tensor: used in place and kept alive -- changing it changes the next
+        solve); w of shape (rows,): the same weights for every instance; None restores the weights given at creation"""
+        self._w_keep.pop(int(cost_index), None)  # one slot per cost: the previous tensor is released
+        if w is None:
+            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), None, 0))
+        elif _is_torch(w):
+            assert w.is_cuda and str(w.dtype) == "torch.float64"
+            if w.ndim == 1:
+                w = w.unsqueeze(0).expand(self.batch, -1)
+            w = w.contiguous()
+            rows = self._cost_rows[int(cost_index)]
+            if rows is not None and tuple(w.shape) != (self.batch, rows):  # (the kernels read batch x rows doubles from it)
+                raise _capi.CopraDomainError("set_cost_weights: expected (%d, %d), got %s" % (self.batch, self._cost_rows[int(cost_index)], tuple(w.shape)))
+            self._w_keep[int(cost_index)] = w
+            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), w.data_ptr(), 1))
+        else:
+            wb = np.asarray(w, dtype=np.float64)
+            if wb.ndim == 1:
+                wb = np.broadcast_to(wb, (self.batch, wb.shape[0]))
+            wb = np.ascontiguousarray(wb)
+            rows = self._cost_rows[int(cost_index)]
+            if rows is not None and wb.shape != (self.batch, rows):
+                raise _capi.CopraDomainError("set_cost_weights: expected (%d, %d), got %s" % (self.batch, self._cost_rows[int(cost_index)], wb.shape))
+            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), wb.ctypes.data, 0))
 
     def set_constraint_rhs(self, cstr_index, f):
         """per-instance right-hand side f (batch, rows) of the Trajectory / Control / Mixed constraint `cstr_index`"""

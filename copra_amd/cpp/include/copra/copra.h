@@ -1043,6 +1043,7 @@ protected:
     struct CostSnapshot {
         int kind = 0, rows = 0, m_cols = 0, n_cols = 0;
         std::vector<double> M, N, p, w;
+        std::vector<double> w0; // the weights the handle was created with (new weights equal to them: the setter restores, NULL)
     };
     static CostSnapshot snapshot(const copra_cost_desc_t& d)
     {
@@ -1052,11 +1053,12 @@ protected:
         if (d.N) c.N.assign(d.N, d.N + (size_t)d.rows * d.n_cols);
         if (d.p) c.p.assign(d.p, d.p + d.rows);
         if (d.weights) c.w.assign(d.weights, d.weights + d.rows);
+        c.w0 = c.w;
         return c;
     }
 public:
     // (measurement aid of this mirror, no reference counterpart: rebuild the device-side controller whenever a cost object was
-    //  replaced, as the mirror did before it learnt to send a changed reference to the handle that exists)
+    //  replaced or its weights changed, as the mirror did before it learnt to send changed references and weights to the handle that exists)
     static bool& newHandlePerCostChange()
     {
         static bool on = false;
@@ -1064,7 +1066,8 @@ public:
     }
 
 protected:
-    // 0: the costs are what the handle was built from; 1: so they are up to the references p (pushed to the handle); 2: anything else
+    // 0: the costs are what the handle was built from; 1: so they are up to the references p and the weights (pushed to the handle:
+    // copra_batch_set_cost_reference, copra_batch_set_cost_weights); 2: anything else
     int costsAgainstHandle()
     {
         if (!builtCostsKnown_ || spCost_.size() != builtCosts_.size()) return 2;
@@ -1076,11 +1079,25 @@ protected:
             copra_cost_desc_t& d = now[t];
             if (!spCost_[t]->deviceDescriptor(d)) return 2;
             if (d.kind != b.kind || d.rows != b.rows || d.m_cols != b.m_cols || d.n_cols != b.n_cols) return 2;
-            if (!same(d.weights, b.w, (size_t)d.rows)) return 2;
+            if (!d.weights || b.w.size() != (size_t)d.rows) return 2;
+            // (new weights go to the handle for per-step costs; a full-size cost -- weights that may change along the horizon, which the
+            //  plan of a cost it evaluates step by step cannot take -- gets a new handle, as before)
+            const bool fullSize = (d.M && d.m_cols != ps_->xDim) || (d.N && d.n_cols != ps_->uDim);
+            if ((newHandlePerCostChange() || fullSize) && !same(d.weights, b.w, (size_t)d.rows)) return 2;
             // (M and N are constructor arguments: the same object still has the ones the handle was built from)
             if (costsDirty_ && (!same(d.M, b.M, (size_t)d.rows * d.m_cols) || !same(d.N, b.N, (size_t)d.rows * d.n_cols))) return 2;
         }
         int rc = 0;
+        for (size_t t = 0; t < spCost_.size(); ++t) {
+            if (same(now[t].weights, builtCosts_[t].w, (size_t)now[t].rows)) continue;
+            // (CostFunction::weights between solves, costFunctions.h:49-76: the instance's weights.  The kernels that hold the creation
+            //  weights in tables give way while they are set; the interior-point kernels refuse them -- there a new handle)
+            if (copra_batch_lanes_per_instance(h_) > 64 || copra_batch_solver_info(h_) == COPRA_SOLVER_RICCATI_IPM) return 2;
+            const bool created = same(now[t].weights, builtCosts_[t].w0, (size_t)now[t].rows); // (back to the creation weights: the fast kernels again)
+            if (copra_batch_set_cost_weights(h_, (int)t, created ? nullptr : now[t].weights, 0) != COPRA_OK) return 2; // (a setter that refuses: a new handle)
+            builtCosts_[t].w.assign(now[t].weights, now[t].weights + now[t].rows);
+            rc = 1;
+        }
         for (size_t t = 0; t < spCost_.size(); ++t) {
             if (same(now[t].p, builtCosts_[t].p, (size_t)now[t].rows)) continue;
             // (a controller past the one-wave kernels would leave its fast kernels in per-instance-reference mode -- the LDS-resident

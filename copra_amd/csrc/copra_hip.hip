@@ -63,6 +63,10 @@ COPRA_AXIS_KERNELS_MORE(COPRA_AXIS_DECL)
 #define COPRA_AXIS_LIST_DECL(NXA, NU, NMAX, QMAX, CT, RPA) extern template __global__ void copra_lmpc_axis_list_kernel<NXA, NU, NMAX, QMAX, CT, RPA>(const FusedPlan);
 COPRA_AXIS_LIST_KERNELS(COPRA_AXIS_LIST_DECL)
 COPRA_AXIS_LIST_KERNELS_MORE(COPRA_AXIS_LIST_DECL)
+#define COPRA_AXIS_W_DECL(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) extern template __global__ void copra_lmpc_axis_w_kernel<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(const FusedPlan);
+COPRA_AXIS_W_KERNELS(COPRA_AXIS_W_DECL)
+#define COPRA_AXIS_LIST_W_DECL(NXA, NU, NMAX, QMAX, CT, RPA) extern template __global__ void copra_lmpc_axis_list_w_kernel<NXA, NU, NMAX, QMAX, CT, RPA>(const FusedPlan);
+COPRA_AXIS_LIST_W_KERNELS(COPRA_AXIS_LIST_W_DECL)
 // run-time-horizon builds (NH == 0) for the shapes of ric_aot_shape: instantiated in copra_hip_ric.hip, a translation unit of its own
 #define COPRA_RIC_RT_DECL(NX, NU)                                                                                      \
     extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, false>(const FusedPlan);      \
@@ -361,7 +365,7 @@ FusedPlan device_plan(const copra_batch* h)
     P.ws = h->d_ws;
     P.model_out = nullptr;
     P.model = nullptr;
-    for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = h->cost_p[k];
+    for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = h->cost_p[k], P.cost_w[k] = h->cost_w[k];
     P.row_f_inst = h->d_row_f_inst;
     P.lb_inst = h->d_lb_inst;
     P.ub_inst = h->d_ub_inst;
@@ -414,9 +418,23 @@ static fused_kernel_t select_lane_shared_kernel(const FusedPlan& P)
     return nullptr;
 }
 // ---- the one-(instance, axis)-per-lane solver (lmpc_axis.hpp): the whole solve of a controller whose axes are decoupled ----
+// per-instance cost weights in the launch's plan (copra_batch_set_cost_weights): only the builds that read them may run
+static bool plan_has_weights(const FusedPlan& P)
+{
+    for (int t = 0; t < kMaxCosts; ++t)
+        if (P.cost_w[t]) return true;
+    return false;
+}
 static fused_kernel_t select_axis_kernel(const FusedPlan& P)
 {
     const int nmax = axis_solver_nmax(P.nx, P.nu, P.N);
+    if (plan_has_weights(P)) { // (the builds that rebuild their tables from the instance's weights: the headline's shape, tables in registers)
+        if (nmax != 20 || P.nx != 6 || P.nu != 3 || !P.axis_const) return nullptr;
+        const bool exact = P.N == 20 && !P.stage_refs;
+        if (P.axis_rpa <= 1)
+            return exact ? copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, true, true, 1> : copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, false, true, 1>;
+        return exact ? copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, true, true, 2> : copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, false, true, 2>;
+    }
     if (nmax == 31 && P.nx == P.nu) // (one state per control in the plane, horizons up to 31)
         return (P.axis_const && P.axis_rpa <= 1) ? copra_lmpc_axis_kernel<1, 2, 31, kAxisQmax, false, true, 1> : copra_lmpc_axis_kernel<1, 2, 31, kAxisQmax, false, false, 2>;
     if (nmax == 20 && (P.nx == 3 * P.nu || P.nx == P.nu)) { // (copra_hip_axis3.hip: tables in registers with one row per axis and step, or read from LDS)
@@ -440,6 +458,10 @@ static fused_kernel_t select_axis_kernel(const FusedPlan& P)
 static fused_kernel_t select_axis_list_kernel(const FusedPlan& P)
 {
     const int nmax = axis_solver_nmax(P.nx, P.nu, P.N);
+    if (plan_has_weights(P)) {
+        if (nmax != 20 || P.nx != 6 || P.nu != 3) return nullptr;
+        return P.axis_const ? copra_lmpc_axis_list_w_kernel<2, 3, 20, kAxisQmaxBig, true, 2> : copra_lmpc_axis_list_w_kernel<2, 3, 20, kAxisQmaxBig, false, 2>;
+    }
     if (nmax == 31 && P.nx == P.nu) return copra_lmpc_axis_list_kernel<1, 2, 31, kAxisQmaxBig, false, 2>;
     if (nmax == 20 && P.nx == P.nu)
         return P.nu == 2 ? copra_lmpc_axis_list_kernel<1, 2, 20, kAxisQmaxBig, false, 2> : copra_lmpc_axis_list_kernel<1, 3, 20, kAxisQmaxBig, false, 2>;
@@ -465,6 +487,18 @@ static size_t axis_lds_bytes(const FusedPlan& P)
 static bool axis_solver_wanted(const copra_batch* h, const FusedPlan& P)
 {
     const copra_options_t& opt = h->hp.opt;
+    if (own_weights(h)) { // per-instance weights: only where BOTH the solver and its second chance run builds that read them (lmpc_axis.hpp, WTS) --
+        // a lane rebuilds its tables from the coefficients of FusedPlan::axis_cref divided by the creation weight, which must be non-zero, and
+        // the cost's weights must repeat along the horizon (a reference-trajectory cost: the kernels read the first step's)
+        if (P.axis_cref < 0 || !select_axis_kernel(P) || !select_axis_list_kernel(P)) return false;
+        for (int t = 0; t < P.ncost; ++t) {
+            if (!h->cost_w[t]) continue;
+            const CostTerm& ct = P.cost[t];
+            if (ct.full) return false;
+            for (int r = 0; r < ct.rows; ++r)
+                if (h->hp.params[(size_t)ct.offW + r] == 0.0) return false;
+        }
+    }
     if (h->ad.axis_off || opt.no_axis_solver || opt.no_lane_pass || P.axis_tab < 0 || P.prof_fine) return false;
     if (opt.lane_min_batch > 0 && P.batch < opt.lane_min_batch) return false;
     if (h->packed || h->shared || h->hp.large || P.initial_state) return false;
@@ -503,6 +537,7 @@ static bool lane_batch_ok(const copra_options_t& opt, int batch, bool ric_tier, 
 static bool lane_pass_wanted(const copra_batch* h, const FusedPlan& P, bool jit_launch)
 {
     const copra_options_t& opt = h->hp.opt;
+    if (own_weights(h)) return false; // (its tables hold the creation weights)
     if (h->ad.lane_off || opt.no_lane_pass || !lane_batch_ok(opt, P.batch, P.lds.ric != 0)) return false;
     if (P.prof_fine) return false; // (the fine-grained stamps of the profiling build follow ONE kernel through a whole solve)
     // (in front of the Riccati-factor tier, which takes the factor over, or of any other one-wave first tier, where it only filters)
@@ -654,6 +689,7 @@ static copra_status_t adapt_axis_solver(copra_batch* h)
 static copra_status_t adapt_layout(copra_batch* h)
 {
     if (!h->hp.two_tier || h->hp.large || h->ad.adapt_left <= 0 || !h->ad.solved_once) return COPRA_OK;
+    if (h->wt_saved) return COPRA_OK; // (routed off its layout for per-instance weights, weights_route: the ladder is neither judged nor spent)
     h->ad.adapt_left -= 1;
     int count = 0;
     HIP_TRY(hipStreamSynchronize(h->last_stream));
@@ -713,6 +749,7 @@ static copra_status_t rechoose_layout(copra_batch* h)
     constexpr long long kPeriod = 256;
     const FusedPlan& P = h->hp.plan;
     if (!h->hp.two_tier || h->hp.large || h->shared || !P.lds.tri || h->hp.opt.no_ladder || P.batch <= 0 || P.initial_state) return COPRA_OK;
+    if (h->wt_saved) return COPRA_OK; // (as adapt_layout)
     if (!h->ad.lds_top_set) { // (first solve of this ladder: remember where it starts)
         h->ad.lds_top = P.lds;
         h->ad.lds_top_set = true;
@@ -892,6 +929,7 @@ copra_status_t prepare_riccati(copra_batch* h)
 // does the next solve of this controller run the Riccati interior-point kernel?
 bool use_riccati(copra_batch* h)
 {
+    if (own_weights(h)) return false; // (the stage plan holds the creation weights: copra_batch_solve refuses what only it covers)
     if (h->hp.ric_only) return prepare_riccati(h) == COPRA_OK && h->hs.eligible;
     if (h->solver == COPRA_SOLVER_QUADPROG_DENSE || h->shared) return false;
     if (h->solver == COPRA_SOLVER_DEFAULT && (!h->hp.large || h->hp.opt.no_riccati)) return false;
@@ -901,7 +939,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 5; } // 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 6; } // 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 
 
@@ -1065,7 +1103,7 @@ void copra_batch_destroy(copra_batch_t* h)
     (void)hipFree(h->own_x0lb);
     (void)hipFree(h->own_x0ub);
     if (h->jit_module) (void)hipModuleUnload(h->jit_module);
-    for (int k = 0; k < kMaxCosts; ++k) (void)hipFree(h->d_cost_p[k]);
+    for (int k = 0; k < kMaxCosts; ++k) (void)hipFree(h->d_cost_p[k]), (void)hipFree(h->d_cost_w[k]);
     (void)hipFree(h->d_row_f_inst);
     (void)hipFree(h->d_lb_inst);
     (void)hipFree(h->d_ub_inst);
@@ -1625,6 +1663,43 @@ static copra_status_t solve_initial_state(copra_batch* h, FusedPlan& P, hipStrea
     return COPRA_OK;
 }
 
+// Per-instance weights (own_weights): the Riccati-factor tier reads its stage costs from tables the plan builder weighted with the creation
+// weights, so a controller that has them runs the layout that tier's ladder ends on (adapt_layout: the compact or the full layout of the
+// generic one-wave kernels, which evaluate the costs per instance) -- and gets the layout it had back once the weights are restored, so that a
+// restored controller runs the same kernels as before.
+static void weights_route(copra_batch* h)
+{
+    const bool own = own_weights(h);
+    if (own && !h->wt_saved && h->hp.plan.lds.ric && !h->hp.large && !h->hp.plan.initial_state) {
+        h->wt_saved = true;
+        h->wt_lds = h->hp.plan.lds;
+        h->wt_lds_bytes = h->hp.lds_bytes;
+        h->wt_two_tier = h->hp.two_tier;
+        h->wt_dense = h->hp.dense;
+        h->wt_packed = h->packed;
+        if (h->hp.dense && h->hp.safe_two_tier && !h->hp.lds_safe.ric) {
+            h->hp.plan.lds = h->hp.lds_safe;
+            h->hp.two_tier = true;
+        } else {
+            h->hp.plan.lds = h->hp.lds_full;
+            h->hp.two_tier = false;
+        }
+        h->hp.dense = false;
+        h->hp.lds_bytes = (size_t)h->hp.plan.lds.total * sizeof(double);
+        const FusedPlan& P = h->hp.plan;
+        h->packed = (P.lds.tri || h->hp.opt.no_packed) ? 0 : packed_width(P.n, P.nx * (P.nx + P.nu + 1), P.rfull > 0, h->hp.lds_bytes);
+        h->lds_attr_set = false;
+    } else if (!own && h->wt_saved) {
+        h->wt_saved = false;
+        h->hp.plan.lds = h->wt_lds;
+        h->hp.lds_bytes = h->wt_lds_bytes;
+        h->hp.two_tier = h->wt_two_tier;
+        h->hp.dense = h->wt_dense;
+        h->packed = h->wt_packed;
+        h->lds_attr_set = false;
+    }
+}
+
 // The one-wave kernels: [one-instance-per-lane pass ->] first tier [-> second tier].  ext_timed: the launches carry their events in their
 // dispatch packets (hipExtLaunchKernelGGL): start of the first launch, end of the first tier (copra_batch_last_first_tier_seconds), end of
 // the solve -- no barrier packets in the stream: two hipEventRecord per solve cost ~ 20 us between consecutive solves, 3 % of a headline step.
@@ -1908,6 +1983,13 @@ copra_status_t copra_batch_solve(copra_batch_t* h, void* hip_stream)
     copra_status_t rc = learn_from_the_last_solve(h);
     if (rc != COPRA_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
+    if (own_weights(h)) { // (copra_batch_set_cost_weights: what no kernel that reads the instance's weights covers is refused, never solved with the creation weights)
+        if (h->shared)
+            return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_solve: per-instance cost weights and the shared-model path (its model holds the creation weights)");
+        if (h->hp.ric_only || h->solver == COPRA_SOLVER_RICCATI_IPM)
+            return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_solve: per-instance cost weights and the Riccati interior-point solver (its stage plan holds the creation weights)");
+    }
+    weights_route(h);
     if (h->shared) {
         rc = solve_shared_model(h, s);
         if (rc == COPRA_OK) remember_outputs(h, device_plan(h));

@@ -287,6 +287,40 @@ copra_status_t copra_batch_set_cost_reference(copra_batch_t* h, int cost_index, 
     return COPRA_OK;
 }
 
+copra_status_t copra_batch_set_cost_weights(copra_batch_t* h, int cost_index, const double* w, int on_device)
+{
+    if (!h) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_weights: null handle");
+    const FusedPlan& P = h->hp.plan;
+    if (cost_index < 0 || cost_index >= (int)h->hp.cost_slot.size()) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_weights: no such cost");
+    const int t = h->hp.cost_slot[(size_t)cost_index]; // (dense costs are not among the kernel-evaluated terms)
+    if (t < 0) return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_weights: a dense (host-evaluated) cost has no weights the kernels read");
+    if (!w) { // back to the weights given at creation
+        h->cost_w[t] = nullptr;
+        return COPRA_OK;
+    }
+    if (h->shared) return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_weights: the shared-model path holds the creation weights in its model");
+    const CostTerm& ct = P.cost[t];
+    if (on_device) {
+        if (ct.pstride) // (the kernels read one block of weights, and device weights are not checked for repeating along the horizon)
+            return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_weights: a full-size cost the controller evaluates step by step takes host weights only "
+                                               "(they are checked to repeat along the horizon)");
+        h->cost_w[t] = w;
+        return COPRA_OK;
+    }
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), rows = (size_t)ct.prows;
+    if (ct.pstride) { // (a full-size cost the plan evaluates step by step: the kernels read one block of weights -- it must repeat along the horizon)
+        for (size_t i = 0; i < b; ++i)
+            for (size_t e = (size_t)ct.pstride; e < rows; ++e)
+                if (w[i * rows + e] != w[i * rows + e % (size_t)ct.pstride])
+                    return fail(COPRA_ERR_DOMAIN, "copra_batch_set_cost_weights: the weights of this full-size cost differ from step to step "
+                                                  "(the controller evaluates it step by step: create it with copra_options_t::no_stage_refs)");
+    }
+    if (!h->d_cost_w[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_w[t], b * rows * sizeof(double)));
+    HIP_TRY(hipMemcpy(h->d_cost_w[t], w, b * rows * sizeof(double), hipMemcpyHostToDevice));
+    h->cost_w[t] = h->d_cost_w[t];
+    return COPRA_OK;
+}
+
 copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_index, const double* p, int on_device)
 {
     if (!h || !p) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference_all: null argument");

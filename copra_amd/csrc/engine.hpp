@@ -136,6 +136,15 @@ struct copra_batch {
     double *d_row_f_inst = nullptr, *d_lb_inst = nullptr, *d_ub_inst = nullptr; // per-instance rhs / control bounds
     double* d_cost_p[kMaxCosts] = {}; // per-instance cost references (owned copies) ...
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
+    double* d_cost_w[kMaxCosts] = {}; // per-instance cost weights (owned copies) ...
+    const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
+    // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
+    // weights): the layout it had is kept here and given back once the weights are restored (weights_route, copra_hip.hip)
+    bool wt_saved = false;
+    LdsLayout wt_lds {};
+    size_t wt_lds_bytes = 0;
+    bool wt_two_tier = false, wt_dense = false;
+    int wt_packed = 0;
     // copra_batch_specialise: this controller's shape compiled into its own kernels (hipcc --genco, cached on disk)
     hipModule_t jit_module = nullptr;
     hipFunction_t jit_fused = nullptr, jit_shared = nullptr;
@@ -183,6 +192,16 @@ struct copra_batch {
     bool timed = false;
     bool lds_attr_set = false;
 };
+
+// Per-instance cost weights (copra_batch_set_cost_weights) are set.  Every kernel that bakes the weights into tables at plan time -- the
+// (instance, axis)-per-lane solver, the one-instance-per-lane pass, the Riccati-factor tier, the shared-model kernels, the Riccati
+// interior-point kernels -- is off while this holds; every selector of those kernels asks it.
+inline bool own_weights(const copra_batch* h)
+{
+    for (int t = 0; t < kMaxCosts; ++t)
+        if (h->cost_w[t]) return true;
+    return false;
+}
 
 // ---- copra_hip.hip ----
 typedef void (*fused_kernel_t)(const FusedPlan);

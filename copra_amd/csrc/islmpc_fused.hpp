@@ -182,7 +182,7 @@ COPRA_DEV void islmpc_fused_body(const FusedPlan& P, int inst)
             const double* Mr = (ct.offM >= 0) ? P.params + ct.offM : nullptr; // R x X, row-major
             const double* Nr = (ct.offN >= 0) ? P.params + ct.offN : nullptr; // R x n, row-major
             const double* pp = cost_reference(P, t, inst);
-            const double* ww = P.params + ct.offW;
+            const double* ww = cost_weights(P, t, inst);
             double* rowbuf = S.dv; // n doubles (the solver vectors are not live yet)
             double* mphi = S.xs; // (M Phi)(rr, 0..nx-1) and the residual (M xi - p)(rr)
             const int jb = lane / nu, jc = lane - jb * nu;
@@ -231,7 +231,7 @@ COPRA_DEV void islmpc_fused_body(const FusedPlan& P, int inst)
         for (int e = lane; e < r * nu; e += kWave) Nm[e] = (ct.offN >= 0) ? P.params[ct.offN + e] : 0.0;
         for (int e = lane; e < r; e += kWave) {
             p[e] = cost_reference(P, t, inst)[e];
-            w[e] = P.params[ct.offW + e];
+            w[e] = cost_weights(P, t, inst)[e];
         }
         wave_sync();
         if (ct.kind == kCostControl) { // costFunctions.cpp:148-156: Q blocks, E = 0, f = -p'WN

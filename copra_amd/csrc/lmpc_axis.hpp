@@ -65,7 +65,9 @@ COPRA_DEV double axis_pred(double x)
 // LIST: the SECOND CHANCE of the instances the first launch listed (FusedPlan::axis_list_in): the same solver with room for more active
 //       constraints per lane (QMAX > 8: S, its factor and the small vectors in the lane's LDS, loops with run-time trip counts), the wave's
 //       instances taken from the list, loaded and stored lane by lane; what it cannot finish either goes on to the first tier's list
-template <int NXA, int NU, int NMAX, int QMAX, bool EXACT = false, bool CT = false, int RPA_ = kAxisMaxRpa, bool LIST = false>
+// WTS: the builds that read per-instance cost weights (copra_batch_set_cost_weights): the lane rebuilds H, HN and the reference coefficients
+//      of its axis from its instance's weights before the sweep (below, 1.); the other builds compile without that code
+template <int NXA, int NU, int NMAX, int QMAX, bool EXACT = false, bool CT = false, int RPA_ = kAxisMaxRpa, bool LIST = false, bool WTS = false>
 COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
 {
     constexpr int NX = NXA * NU, NZ = NXA + 1, RW = NXA + 3, RPA = RPA_;
@@ -108,6 +110,12 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
     bool own_refs = false;
     for (int t = 0; t < P.ncost; ++t) own_refs = own_refs || P.cost_p[t] != nullptr;
     own_refs = own_refs && P.axis_cref >= 0;
+    bool own_w = false; // per-instance weights: the affine terms are rebuilt as for per-instance references, with the rescaled coefficients
+    if constexpr (WTS) {
+        for (int t = 0; t < P.ncost; ++t) own_w = own_w || P.cost_w[t] != nullptr;
+        own_w = own_w && P.axis_cref >= 0;
+        own_refs = own_refs || own_w;
+    }
     // REFERENCE TRAJECTORIES (FusedPlan::stage_refs, CostTerm::pstride: a TrajectoryCost given as a full-size entry whose reference changes along
     // the horizon -- the only form the reference's API has for it, costFunctions.cpp:63-82 with AutoSpan): h differs from stage to stage.  The
     // builds with a run-time horizon rebuild it stage by stage into the lane's (still idle) sparse array before the sweep.
@@ -154,8 +162,10 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
     const double* bj[MR];
     int psj[MR], lastj[MR];
     double ch[MR][NZ], cN[MR][NXA], pl[MR];
+    double wn[MR], w0[MR]; // (WTS: the instance's weight of the entry's cost row, and the creation weight the coefficients were built with)
 #pragma unroll
     for (int j = 0; j < MR; ++j) {
+        wn[j] = w0[j] = 1.0;
         bj[j] = P.params;
         psj[j] = lastj[j] = 0;
         pl[j] = 0.0;
@@ -180,6 +190,17 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
 #pragma unroll
             for (int tt = 0; tt < kMaxCosts; ++tt) own = (t == tt) ? P.cost_p[tt] : own;
             bj[j] = (own ? own + (size_t)inst * prows : P.params + offP) + r;
+            if constexpr (WTS) { // (requested with the entries and the references: no dependent trip of its own in front of the sweep)
+                const double* ow = nullptr;
+                int offW = 0;
+#pragma unroll
+                for (int tt = 0; tt < kMaxCosts; ++tt) {
+                    ow = (t == tt) ? P.cost_w[tt] : ow;
+                    offW = (t == tt) ? P.cost[tt].offW : offW;
+                }
+                w0[j] = on ? P.params[offW + r] : 1.0;
+                wn[j] = (on && ow) ? ow[(size_t)inst * prows + r] : w0[j];
+            }
             psj[j] = ps;
             lastj[j] = ps ? prows / ps - 1 : 0; // (the last step the reference has)
         }
@@ -320,6 +341,30 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
 #pragma unroll
             for (int j = 0; j < NXA; ++j) Pm[i][j] = Tg[oHN + i + NXA * j];
             pv[i] = Tg[ohN + i];
+        }
+        // Per-instance weights (copra_batch_set_cost_weights): the tables are linear in the weights.  An entry's coefficients are
+        // ch = -w0 c (stage) and cN = -w0 c (terminal) with the creation weight w0 (non-zero: axis_solver_wanted), so the instance's weight w
+        // adds (w - w0) c c' = (w / w0 - 1) / w0 ch ch' to H (cN cN' to HN), and the affine terms are rebuilt below from the coefficients
+        // scaled by w / w0.  Per-step costs repeat their weights at every step: the rebuilt tables stay the same along the horizon.
+        if constexpr (WTS) {
+            if (own_w) {
+#pragma unroll
+                for (int j = 0; j < MR; ++j) {
+                    const double rho = wn[j] / w0[j], g = (rho - 1.0) / w0[j];
+#pragma unroll
+                    for (int a = 0; a < NZ; ++a)
+#pragma unroll
+                        for (int b = 0; b < NZ; ++b) H[a][b] += (g * ch[j][a]) * ch[j][b];
+#pragma unroll
+                    for (int i = 0; i < NXA; ++i)
+#pragma unroll
+                        for (int l = 0; l < NXA; ++l) Pm[i][l] += (g * cN[j][i]) * cN[j][l];
+#pragma unroll
+                    for (int a = 0; a < NZ; ++a) ch[j][a] *= rho;
+#pragma unroll
+                    for (int i = 0; i < NXA; ++i) cN[j][i] *= rho;
+                }
+            }
         }
         // Per-instance cost references (copra_batch_set_cost_reference: every instance tracks its own goal -- one TrajectoryCost(M, p_b) per
         // LMPC in the reference, costFunctions.cpp:63-82): the affine terms h = -sum_t [M N]_t' W_t p_t and hN of this lane's axis are rebuilt

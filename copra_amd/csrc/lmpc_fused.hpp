@@ -45,6 +45,13 @@ COPRA_DEV const double* cost_reference(const FusedPlan& P, int t, int inst)
     const CostTerm& ct = P.cost[t];
     return P.cost_p[t] ? P.cost_p[t] + (size_t)inst * ct.prows : P.params + ct.offP;
 }
+// ... and its weights: the ones given at creation, or the instance's own (copra_batch_set_cost_weights).  A per-instance vector holds the
+// cost's rows as created (prows); a per-step entry made of a full-size cost (pstride) reads its first block, which the setter checks repeats
+COPRA_DEV const double* cost_weights(const FusedPlan& P, int t, int inst)
+{
+    const CostTerm& ct = P.cost[t];
+    return P.cost_w[t] ? P.cost_w[t] + (size_t)inst * ct.prows : P.params + ct.offW;
+}
 
 // Which instance does workgroup w of a first tier solve?  Without the one-instance-per-lane pass in front (lmpc_lane.hpp): instance w.  Behind
 // it: an entry of the list the pass left -- false when there is none for this workgroup.
@@ -389,7 +396,7 @@ struct StageRows {
 // Round 1 formed tmp row by row on the VALU (0.83 M solves/s at the headline shape, the matrix cores 0.7 % busy).
 // ------------------------------------------------------------------------------------------------
 template <int NX_, int NU_, int NH_, bool TRI_ = false>
-COPRA_DEV void full_size_cost_term(const FusedPlan& P, const CostTerm& ct, const double* p, const double* G,
+COPRA_DEV void full_size_cost_term(const FusedPlan& P, const CostTerm& ct, const double* p, const double* w, const double* G,
     const double* Xbar, double* Q, int ld, double* scratch, double& cj)
 {
     const int lane = lane_id();
@@ -398,7 +405,6 @@ COPRA_DEV void full_size_cost_term(const FusedPlan& P, const CostTerm& ct, const
     const int R = ct.rows;
     const double* Mr = (ct.offM >= 0) ? P.params + ct.offM : nullptr; // R x X, row-major
     const double* Nr = (ct.offN >= 0) ? P.params + ct.offN : nullptr; // R x n, row-major
-    const double* w = P.params + ct.offW;
     double* We = scratch; // R weighted residuals (only where they cannot ride in the product: ControlCost, or n == 64)
     // The residual  M xbar - p  RIDES in the product when the 64-column tile has a spare column (n < 64: the headline has 60):
     // column n of the B operand is xbar, so tmp(r, n) = M_r . xbar comes out of the same instructions.  (Round 3 walked every row of
@@ -704,7 +710,8 @@ COPRA_DEV void lmpc_fused_body(const FusedPlan& P, int inst)
             if constexpr (RP_ == 0) { // plans with full-size entries run the instantiations without padded cost rows (plan.hpp)
                 if (ct.full) {
                     wave_sync();
-                    full_size_cost_term<NX_, NU_, NH_, TRI_>(P, ct, cost_reference(P, t, inst), G, Xbar, Q, ld, lds + L.BldFull, cj);
+                    full_size_cost_term<NX_, NU_, NH_, TRI_>(P, ct, cost_reference(P, t, inst), cost_weights(P, t, inst), G, Xbar, Q, ld, lds + L.BldFull,
+                        cj);
                     continue;
                 }
             }
@@ -724,9 +731,10 @@ COPRA_DEV void lmpc_fused_body(const FusedPlan& P, int inst)
                 Nm[e] = (ct.offN >= 0 && row < rc) ? P.params[ct.offN + row + rc * c] : 0.0;
             }
             const double* pref = cost_reference(P, t, inst);
+            const double* wref = cost_weights(P, t, inst);
             for (int e = lane; e < r; e += kWave) {
                 p[e] = (e < rc) ? pref[e] : 0.0;
-                w[e] = (e < rc) ? P.params[ct.offW + e] : 0.0;
+                w[e] = (e < rc) ? wref[e] : 0.0;
             }
             wave_sync();
             COPRA_FINE("cost:params");

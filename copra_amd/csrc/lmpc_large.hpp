@@ -204,7 +204,7 @@ COPRA_DEV void large_costs(const FusedPlan& P, int inst, double* lds, double* F,
             const double* Mr = (ct.offM >= 0) ? P.params + ct.offM : nullptr; // R x X, row-major
             const double* Nr = (ct.offN >= 0) ? P.params + ct.offN : nullptr; // R x n, row-major
             const double* pp = cost_reference(P, t, inst);
-            const double* ww = P.params + ct.offW;
+            const double* ww = cost_weights(P, t, inst);
             double* rowbuf = lds + L.sol.stage; // 4 x n
             double* mphi = lds + L.sol.xs; // 4 x (nx + 1): (M Phi)(row, :) and the residual of the row
             const double* xfree = is ? Xi : Xbar;
@@ -278,7 +278,7 @@ COPRA_DEV void large_costs(const FusedPlan& P, int inst, double* lds, double* F,
         for (int e = tid; e < r * nu; e += T) Nm[e] = (ct.offN >= 0) ? P.params[ct.offN + e] : 0.0;
         for (int e = tid; e < r; e += T) {
             p[e] = cost_reference(P, t, inst)[e];
-            w[e] = P.params[ct.offW + e];
+            w[e] = cost_weights(P, t, inst)[e];
         }
         bt_sync();
         if (ct.kind == kCostControl) { // ControlCost::update (costFunctions.cpp:148-156): block-diagonal N'WN

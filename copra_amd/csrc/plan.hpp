@@ -320,6 +320,7 @@ struct FusedPlan {
     int ncost;
     CostTerm cost[kMaxCosts];
     const double* cost_p[kMaxCosts]; // per-instance references p of cost t: [batch][rows], or nullptr = the shared one
+    const double* cost_w[kMaxCosts]; // per-instance weights of cost t: [batch][prows], or nullptr = the ones given at creation (copra_batch_set_cost_weights)
     // sum of the COPRA_COST_DENSE terms (host-evaluated user cost functions): offsets into `params`, -1 = none.
     // Q (n x n, column-major, both triangles), c (n), E (nx x n), f (n)
     int denseQ, densec, denseE, densef;

@@ -338,7 +338,8 @@ class LMPC:
         """The reference evaluates every cost anew in every solve (LMPC.cpp:233-247): weights changed on a cost that is inside the
         controller, or a cost replaced by a new one, take effect at the next solve.  0: the costs are what the engine was built from;
         1: they are up to the references p -- the only way the reference's API has to move a reference trajectory is a NEW cost object
-        (M, N, p are constructor arguments) --, which go to the engine that exists (copra_batch_set_cost_reference); 2: anything else"""
+        (M, N, p are constructor arguments) -- and the weights (CostFunction::weights, costFunctions.h:49-76), which go to the engine that
+        exists (copra_batch_set_cost_reference, copra_batch_set_cost_weights); 2: anything else (or a setter that refuses)"""
         built = self._built_costs
         if built is None:  # (costs that are not the built-in classes: the list alone decides, as before)
             return 2 if self._costs_dirty else 0
@@ -348,10 +349,28 @@ class LMPC:
         for c, (kind, M, N, w, _) in zip(self._costs, built):
             if not all(hasattr(c, a) for a in ("_M", "_N", "_p", "_w")):  # (not one of the built-in classes)
                 return 2
-            if c.kind != kind or not same(c._w, w) or not same(c._M, M) or not same(c._N, N):
+            if c.kind != kind or not same(c._M, M) or not same(c._N, N):
+                return 2
+            if c._w is None or w is None or c._w.shape != w.shape:
+                return 2
+            # (new weights go to the engine for per-step costs; a full-size cost -- weights that may change along the horizon, which the
+            #  plan of a cost it evaluates step by step cannot take -- gets a new engine, as before)
+            full = (M is not None and M.shape[1] != self._ps.x_dim) or (N is not None and N.shape[1] != self._ps.u_dim)
+            if full and not same(c._w, w):
                 return 2
         rc = 0
         for t, c in enumerate(self._costs):
+            if not same(c._w, built[t][3]):
+                # (the engines that bake the weights into their tables route a controller with per-instance weights away, include/copra_hip.h;
+                #  the interior-point kernels refuse it: there a new engine)
+                if self._eng.lanes_per_instance() > 64 or self._eng.solver() == "riccati_ipm":
+                    return 2
+                try:  # (back to the creation weights: None, which gives the controller its fast kernels back)
+                    self._eng.set_cost_weights(t, None if same(c._w, self._created_w[t]) else c._w[None])
+                except Exception:
+                    return 2
+                built[t] = built[t][:3] + (c._w.copy(),) + built[t][4:]
+                rc = 1
             if not same(c._p, built[t][4]):
                 # (a controller past the one-wave kernels would leave its fast kernels in per-instance-reference mode -- the LDS-resident
                 #  interior-point kernel above all, include/copra_hip.h --: there a new engine is worth more than the engine build)
@@ -395,6 +414,7 @@ class LMPC:
         cp = lambda a: None if a is None else np.array(a, dtype=np.float64, copy=True)
         builtin = all(hasattr(c, a) for c in self._costs for a in ("_M", "_N", "_p", "_w"))
         self._built_costs = [(c.kind, cp(c._M), cp(c._N), cp(c._w), cp(c._p)) for c in self._costs] if builtin else None
+        self._created_w = [b[3] for b in self._built_costs] if builtin else None
         return self._eng
 
     def select_qp_solver(self, flag):

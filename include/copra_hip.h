@@ -68,7 +68,8 @@ typedef enum {
 
 /* A cost function exactly as handed to LMPC::addCost (src/LMPC.cpp:118-122), i.e. the constructor arguments of
  * include/costFunctions.h:112-118 / :142-148 / :171-177 / :203-210 plus CostFunction::weights (:54-67).
- * Host pointers; copied at copra_batch_create.  The parameters are shared by every instance of the batch. */
+ * Host pointers; copied at copra_batch_create.  The parameters are shared by every instance of the batch (references and weights can be
+ * set per instance later: copra_batch_set_cost_reference, copra_batch_set_cost_weights). */
 typedef struct {
     int kind; /* copra_cost_kind_t */
     int rows; /* rows of M / N / p / weights */
@@ -258,6 +259,23 @@ copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_ind
  *      Riccati-factor tier's shared mode, and every call broadcasts batch x rows doubles.  Where that matters -- InitialStateLMPC /
  *      long horizons, shared-model ticks -- create a new controller with the new reference instead; the C++ and Python mirrors do so
  *      for controllers with more than 64 decision variables. */
+/* ---- per-instance cost weights: the weights of cost `cost_index` (the order of the `costs` array given at creation) for EVERY instance,
+ *      [batch][rows] with the rows of that cost as created, after the tiling of CostFunction::weights (per-step entry: r, full-size
+ *      entry: r (N+1) or r N).  Replaces the reference's setter CostFunction::weights / weight (include/costFunctions.h:49-76), which a
+ *      user calls between solves (src/LMPC.cpp:233-247 evaluates every cost anew): each instance of the batch gets its own weights, no new
+ *      plan, no new handle.  w == NULL restores the weights given at creation.  on_device != 0: used in place (it must stay valid);
+ *      otherwise copied into a buffer of the library.  A dense (host-evaluated) cost: COPRA_ERR_UNSUPPORTED.  A full-size cost with
+ *      repeating blocks that the controller evaluates step by step (copra_options_t::no_stage_refs unset) needs weights that repeat
+ *      along the horizon too: COPRA_ERR_DOMAIN otherwise; such a cost takes host weights only (COPRA_ERR_UNSUPPORTED with on_device).
+ *      While any cost has per-instance weights, the (instance, axis)-per-lane solver runs its builds that rebuild their tables from each
+ *      instance's weights where it has them (the headline's shape: xDim 6, uDim 3, N <= 20, tables the same along the horizon, creation
+ *      weights non-zero); every other kernel that holds the creation weights in tables of the plan is not launched: other shapes of that
+ *      solver, the one-instance-per-lane pass and the Riccati-factor tier give way to the generic one-wave kernels, long horizons run the
+ *      Goldfarb-Idnani kernels; a controller that only the Riccati interior-point solver covers, or one
+ *      forced onto it (copra_batch_select_solver), and a controller in shared-model mode (copra_batch_set_shared_system) return
+ *      COPRA_ERR_UNSUPPORTED from copra_batch_solve -- a shared model written out per instance (the (instance, axis)-per-lane solver's
+ *      case) solves as a batch.  Restoring every cost's weights gives the controller its kernels back. ---- */
+copra_status_t copra_batch_set_cost_weights(copra_batch_t* h, int cost_index, const double* w, int on_device);
 
 /* ---- per-instance constraint data.  copra_batch_set_constraint_rhs: f of the Trajectory / Control / Mixed constraint
  *      `cstr_index` (position in the `cstrs` array given at creation) for every instance, [batch][rows] with the rows
