@@ -56,17 +56,8 @@ __global__ __launch_bounds__(64, 2) void copra_lmpc_fused_tri_kernel(const Fused
 }
 
 #include "ric_kernels.hpp" // copra_lmpc_fused_ric_kernel, copra_lmpc_lane_kernel
-#include "axis_kernels.hpp" // copra_lmpc_axis_kernel: instantiated in copra_hip_axis.hip
-#define COPRA_AXIS_DECL(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) extern template __global__ void copra_lmpc_axis_kernel<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(const FusedPlan);
-COPRA_AXIS_KERNELS(COPRA_AXIS_DECL)
-COPRA_AXIS_KERNELS_MORE(COPRA_AXIS_DECL)
-#define COPRA_AXIS_LIST_DECL(NXA, NU, NMAX, QMAX, CT, RPA) extern template __global__ void copra_lmpc_axis_list_kernel<NXA, NU, NMAX, QMAX, CT, RPA>(const FusedPlan);
-COPRA_AXIS_LIST_KERNELS(COPRA_AXIS_LIST_DECL)
-COPRA_AXIS_LIST_KERNELS_MORE(COPRA_AXIS_LIST_DECL)
-#define COPRA_AXIS_W_DECL(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) extern template __global__ void copra_lmpc_axis_w_kernel<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(const FusedPlan);
-COPRA_AXIS_W_KERNELS(COPRA_AXIS_W_DECL)
-#define COPRA_AXIS_LIST_W_DECL(NXA, NU, NMAX, QMAX, CT, RPA) extern template __global__ void copra_lmpc_axis_list_w_kernel<NXA, NU, NMAX, QMAX, CT, RPA>(const FusedPlan);
-COPRA_AXIS_LIST_W_KERNELS(COPRA_AXIS_LIST_W_DECL)
+#include "axis_kernels.hpp" // copra_lmpc_axis*_kernel: the builds of axis_builds.hpp, instantiated in copra_hip_axis*.hip
+COPRA_AXIS_BUILDS(COPRA_AXIS_DECL)
 // run-time-horizon builds (NH == 0) for the shapes of ric_aot_shape: instantiated in copra_hip_ric.hip, a translation unit of its own
 #define COPRA_RIC_RT_DECL(NX, NU)                                                                                      \
     extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, false>(const FusedPlan);      \
@@ -425,55 +416,18 @@ static bool plan_has_weights(const FusedPlan& P)
         if (P.cost_w[t]) return true;
     return false;
 }
-static fused_kernel_t select_axis_kernel(const FusedPlan& P)
+// The build the controller gets (axis_builds.hpp: pick_axis_build) and its kernel: kAxisKernels[k] runs kAxisBuilds[k]
+#define COPRA_AXIS_PTR(UNIT, FAMILY, ...) COPRA_AXIS_KERNEL_##FAMILY(__VA_ARGS__),
+static const fused_kernel_t kAxisKernels[] = { COPRA_AXIS_BUILDS(COPRA_AXIS_PTR) };
+#undef COPRA_AXIS_PTR
+static fused_kernel_t axis_kernel(const FusedPlan& P, bool list)
 {
-    const int nmax = axis_solver_nmax(P.nx, P.nu, P.N);
-    if (plan_has_weights(P)) { // (the builds that rebuild their tables from the instance's weights: the headline's shape, tables in registers)
-        if (nmax != 20 || P.nx != 6 || P.nu != 3 || !P.axis_const) return nullptr;
-        const bool exact = P.N == 20 && !P.stage_refs;
-        if (P.axis_rpa <= 1)
-            return exact ? copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, true, true, 1> : copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, false, true, 1>;
-        return exact ? copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, true, true, 2> : copra_lmpc_axis_w_kernel<2, 3, 20, kAxisQmax, false, true, 2>;
-    }
-    if (nmax == 31 && P.nx == P.nu) // (one state per control in the plane, horizons up to 31)
-        return (P.axis_const && P.axis_rpa <= 1) ? copra_lmpc_axis_kernel<1, 2, 31, kAxisQmax, false, true, 1> : copra_lmpc_axis_kernel<1, 2, 31, kAxisQmax, false, false, 2>;
-    if (nmax == 20 && (P.nx == 3 * P.nu || P.nx == P.nu)) { // (copra_hip_axis3.hip: tables in registers with one row per axis and step, or read from LDS)
-        const bool ct = P.axis_const && P.axis_rpa <= 1;
-#define COPRA_AXIS_PICK3(NXA, NU) (ct ? copra_lmpc_axis_kernel<NXA, NU, 20, kAxisQmax, false, true, 1> : copra_lmpc_axis_kernel<NXA, NU, 20, kAxisQmax, false, false, 2>)
-        if (P.nx == P.nu) return P.nu == 2 ? COPRA_AXIS_PICK3(1, 2) : COPRA_AXIS_PICK3(1, 3);
-        return P.nu == 2 ? COPRA_AXIS_PICK3(3, 2) : COPRA_AXIS_PICK3(3, 3);
-#undef COPRA_AXIS_PICK3
-    }
-    if (nmax == 21) // (three axes at the last horizon of the one-wave kernels: tables in registers with one row per axis and step, or read from LDS)
-        return (P.axis_const && P.axis_rpa <= 1) ? copra_lmpc_axis_kernel<2, 3, 21, kAxisQmax, false, true, 1> : copra_lmpc_axis_kernel<2, 3, 21, kAxisQmax, false, false, 2>;
-#define COPRA_AXIS_PICK(NU, NMAX, EXACT)                                                                                                     \
-    (P.axis_const ? (P.axis_rpa <= 1 ? copra_lmpc_axis_kernel<2, NU, NMAX, kAxisQmax, EXACT, true, 1> : copra_lmpc_axis_kernel<2, NU, NMAX, kAxisQmax, EXACT, true, 2>) \
-                  : copra_lmpc_axis_kernel<2, NU, NMAX, kAxisQmax, false, false, 2>)
-    if (nmax == 20) return P.nu == 3 ? (P.N == 20 && !P.stage_refs ? COPRA_AXIS_PICK(3, 20, true) : COPRA_AXIS_PICK(3, 20, false)) : COPRA_AXIS_PICK(2, 20, false); // (reference trajectories: the run-time-horizon builds)
-    if (nmax == 31) return COPRA_AXIS_PICK(2, 31, false);
-#undef COPRA_AXIS_PICK
-    return nullptr;
+    const AxisBuild* b = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, plan_has_weights(P), list);
+    return b ? kAxisKernels[b - kAxisBuilds] : nullptr;
 }
+static fused_kernel_t select_axis_kernel(const FusedPlan& P) { return axis_kernel(P, false); }
 // ... and the second chance of what it lists: room for kAxisQmaxBig active constraints per lane
-static fused_kernel_t select_axis_list_kernel(const FusedPlan& P)
-{
-    const int nmax = axis_solver_nmax(P.nx, P.nu, P.N);
-    if (plan_has_weights(P)) {
-        if (nmax != 20 || P.nx != 6 || P.nu != 3) return nullptr;
-        return P.axis_const ? copra_lmpc_axis_list_w_kernel<2, 3, 20, kAxisQmaxBig, true, 2> : copra_lmpc_axis_list_w_kernel<2, 3, 20, kAxisQmaxBig, false, 2>;
-    }
-    if (nmax == 31 && P.nx == P.nu) return copra_lmpc_axis_list_kernel<1, 2, 31, kAxisQmaxBig, false, 2>;
-    if (nmax == 20 && P.nx == P.nu)
-        return P.nu == 2 ? copra_lmpc_axis_list_kernel<1, 2, 20, kAxisQmaxBig, false, 2> : copra_lmpc_axis_list_kernel<1, 3, 20, kAxisQmaxBig, false, 2>;
-    if (nmax == 20 && P.nx == 3 * P.nu)
-        return P.nu == 2 ? copra_lmpc_axis_list_kernel<3, 2, 20, kAxisQmaxBig, false, 2> : copra_lmpc_axis_list_kernel<3, 3, 20, kAxisQmaxBig, false, 2>;
-    if (nmax == 21) return copra_lmpc_axis_list_kernel<2, 3, 21, kAxisQmaxBig, false, 2>;
-#define COPRA_AXIS_LPICK(NU, NMAX) (P.axis_const ? copra_lmpc_axis_list_kernel<2, NU, NMAX, kAxisQmaxBig, true, 2> : copra_lmpc_axis_list_kernel<2, NU, NMAX, kAxisQmaxBig, false, 2>)
-    if (nmax == 20) return P.nu == 3 ? COPRA_AXIS_LPICK(3, 20) : COPRA_AXIS_LPICK(2, 20);
-    if (nmax == 31) return COPRA_AXIS_LPICK(2, 31);
-#undef COPRA_AXIS_LPICK
-    return nullptr;
-}
+static fused_kernel_t select_axis_list_kernel(const FusedPlan& P) { return axis_kernel(P, true); }
 static size_t axis_list_lds_bytes(const FusedPlan& P)
 {
     int oB = 0, oR = 0, rcs = 0;

@@ -1,9 +1,9 @@
-// copra_hip_axis3.hip -- more instantiations of the one-(instance, axis)-per-lane solver (lmpc_axis.hpp): one chain of two states, and chains
-// of three states per control (the jerk-controlled CoM model) in one, two and three dimensions -- plan_builder.hpp::axis_solver_nmax.
+// copra_hip_axis3.hip -- more instantiations of the one-(instance, axis)-per-lane solver (lmpc_axis.hpp): the entries "axis3" of
+// axis_builds.hpp, one state per control, chains of two states at N = 21, and chains of three states per control (the jerk-controlled CoM model).
 // A translation unit of its own: it compiles next to copra_hip_axis.hip (make -j).
 #include "axis_kernels.hpp"
 
-#define COPRA_AXIS_INST(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) template __global__ void copra_lmpc_axis_kernel<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(const FusedPlan);
-COPRA_AXIS_KERNELS_MORE(COPRA_AXIS_INST)
-#define COPRA_AXIS_LIST_INST(NXA, NU, NMAX, QMAX, CT, RPA) template __global__ void copra_lmpc_axis_list_kernel<NXA, NU, NMAX, QMAX, CT, RPA>(const FusedPlan);
-COPRA_AXIS_LIST_KERNELS_MORE(COPRA_AXIS_LIST_INST)
+#define COPRA_AXIS_UNIT_axis(...)
+#define COPRA_AXIS_UNIT_axis3(...) __VA_ARGS__
+#define COPRA_AXIS_UNIT_axis_w(...)
+COPRA_AXIS_BUILDS(COPRA_AXIS_INST)

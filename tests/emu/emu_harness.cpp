@@ -2,6 +2,7 @@
 // See wave_prims.hpp in this directory.  Exposes a tiny C interface for ctypes.
 #include "wave_prims.hpp" // must come first: shadows copra_amd/csrc/wave_prims.hpp (same include guard name)
 
+#include "../../copra_amd/csrc/axis_builds.hpp"
 #include "../../copra_amd/csrc/islmpc_fused.hpp"
 #include "../../copra_amd/csrc/lmpc_fused.hpp"
 #include "../../copra_amd/csrc/lmpc_fused_ric.hpp"
@@ -162,6 +163,26 @@ using namespace copra_hip;
 
 static const double* g_cost_p[copra_hip::kMaxCosts]; // per-instance cost references for the next emu_lmpc_solve
 
+// The body of a build of the (instance, axis)-per-lane solver (axis_builds.hpp) for wave g -- in the tests' two-slot mode (small_q) the first
+// launch's build with room for two active constraints and without the horizon compiled in.  false: the emulator has no body for it (weights).
+static bool emu_axis_body(const AxisBuild* b, bool small_q, const FusedPlan& P, int g)
+{
+#define COPRA_EMU_AXIS_first(NXA, NU, NMAX, QMAX, EXACT, CT, RPA)                                                                  \
+    (small_q ? lmpc_axis_body<NXA, NU, NMAX, 2, false, CT, RPA>(P, g) : lmpc_axis_body<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(P, g)), true
+#define COPRA_EMU_AXIS_list(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) lmpc_axis_body<NXA, NU, NMAX, QMAX, false, CT, RPA, true>(P, g), true
+#define COPRA_EMU_AXIS_first_w(...) false
+#define COPRA_EMU_AXIS_list_w(...) false
+#define COPRA_EMU_AXIS_RUN(UNIT, FAMILY, ...) if (b == e++) return COPRA_EMU_AXIS_##FAMILY(__VA_ARGS__);
+    const AxisBuild* e = kAxisBuilds;
+    COPRA_AXIS_BUILDS(COPRA_EMU_AXIS_RUN)
+#undef COPRA_EMU_AXIS_RUN
+#undef COPRA_EMU_AXIS_first
+#undef COPRA_EMU_AXIS_list
+#undef COPRA_EMU_AXIS_first_w
+#undef COPRA_EMU_AXIS_list_w
+    return false;
+}
+
 extern "C" {
 
 static int g_lane_hist[copra_hip::kLaneHistBins]; // violated-row histogram of the last lane pass (FusedPlan::lane_hist)
@@ -183,6 +204,16 @@ void emu_set_instance_rows(const double* row_f, const double* lb, const double* 
     g_row_f_inst = row_f;
     g_lb_inst = lb;
     g_ub_inst = ub;
+}
+// the build of the (instance, axis)-per-lane solver a controller gets (axis_builds.hpp: pick_axis_build): 1 and out = (family, NXA, NU, NMAX,
+// QMAX, EXACT, CT, RPA), or 0: none
+int emu_axis_build(int nx, int nu, int N, int axis_const, int axis_rpa, int stage_refs, int weights, int list, int* out)
+{
+    const AxisBuild* b = pick_axis_build(nx, nu, N, axis_const, axis_rpa, stage_refs, weights, list);
+    if (!b) return 0;
+    const int v[8] = { (int)b->family, b->nxa, b->nu, b->nmax, b->qmax, b->exact, b->ct, b->rpa };
+    std::copy(v, v + 8, out);
+    return 1;
 }
 
 // Build the plan exactly as copra_batch_create does and run the fused kernel body for every instance.
@@ -378,34 +409,17 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         int oB = 0, oR = 0, rcs = 0;
         const size_t abytes = (size_t)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs) * sizeof(double); // (sized for the library's builds; the two-slot test build needs less)
         const bool small_q = std::getenv("COPRA_EMU_AXIS_QMAX2") != nullptr; // (tests: an active set that outgrows the lane -- the hand-over to the tier)
+        // the library's builds: the same pick as copra_hip.hip's select_axis_kernel and select_axis_list_kernel (no per-instance weights here)
+        const AxisBuild* first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, false, false);
+        const AxisBuild* second = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, false, true);
+        if (!first || !second) {
+            std::fprintf(stderr, "emu: the axis solver has no build for nx %d, nu %d, N %d, axis_rpa %d\n", P.nx, P.nu, P.N, P.axis_rpa);
+            return -100;
+        }
         for (int g = 0; g < groups; ++g) {
-            int r = emu::run_wave([&]() {
-#define COPRA_EMU_AXIS_B(NU, NMAX, Q, EXACT)                                                                                     \
-    (P.axis_const ? (P.axis_rpa <= 1 ? lmpc_axis_body<2, NU, NMAX, Q, EXACT, true, 1>(P, g) : lmpc_axis_body<2, NU, NMAX, Q, EXACT, true, 2>(P, g)) \
-                  : lmpc_axis_body<2, NU, NMAX, Q, false, false, 2>(P, g))
-#define COPRA_EMU_AXIS(NU)                                                                                                       \
-    (small_q ? COPRA_EMU_AXIS_B(NU, 20, 2, false)                                                                                \
-             : P.N == 20 && NU == 3 && !P.stage_refs ? COPRA_EMU_AXIS_B(NU, 20, kAxisQmax, true)                                  \
-             : P.N <= 20 ? COPRA_EMU_AXIS_B(NU, 20, kAxisQmax, false) : COPRA_EMU_AXIS_B(NU, 31, kAxisQmax, false))
-                if (P.nx == P.nu && P.N > 20) { // one state per control in the plane, horizons up to 31
-                    const bool ct = P.axis_const && P.axis_rpa <= 1;
-                    (small_q ? lmpc_axis_body<1, 2, 31, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<1, 2, 31, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<1, 2, 31, kAxisQmax, false, false, 2>(P, g));
-                } else if (P.nx == P.nu) { // one state per control (copra_hip_axis3.hip)
-                    const bool ct = P.axis_const && P.axis_rpa <= 1;
-                    if (P.nu == 3) (small_q ? lmpc_axis_body<1, 3, 20, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<1, 3, 20, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<1, 3, 20, kAxisQmax, false, false, 2>(P, g));
-                    else (small_q ? lmpc_axis_body<1, 2, 20, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<1, 2, 20, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<1, 2, 20, kAxisQmax, false, false, 2>(P, g));
-                } else if (P.nx == 3 * P.nu) { // chains of three states per control (copra_hip_axis3.hip)
-                    const bool ct = P.axis_const && P.axis_rpa <= 1;
-                    if (P.nu == 3) (small_q ? lmpc_axis_body<3, 3, 20, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<3, 3, 20, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<3, 3, 20, kAxisQmax, false, false, 2>(P, g));
-                    else (small_q ? lmpc_axis_body<3, 2, 20, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<3, 2, 20, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<3, 2, 20, kAxisQmax, false, false, 2>(P, g));
-                } else if (P.nu == 3 && P.N == 21) {
-                    const bool ct = P.axis_const && P.axis_rpa <= 1;
-                    (small_q ? lmpc_axis_body<2, 3, 21, 2, false, false, 2>(P, g) : ct ? lmpc_axis_body<2, 3, 21, kAxisQmax, false, true, 1>(P, g) : lmpc_axis_body<2, 3, 21, kAxisQmax, false, false, 2>(P, g));
-                } else if (P.nu == 3) COPRA_EMU_AXIS(3);
-                else COPRA_EMU_AXIS(2);
-#undef COPRA_EMU_AXIS
-            }, abytes, g, groups);
-            if (r != 0) return -100;
+            bool ran = false;
+            int r = emu::run_wave([&]() { ran = emu_axis_body(first, small_q, P, g); }, abytes, g, groups);
+            if (r != 0 || !ran) return -100;
         }
         P.lane_hist = nullptr;
         // the second chance of what it listed (copra_lmpc_axis_list_kernel): room for kAxisQmaxBig active constraints per lane, instances from the list
@@ -423,23 +437,9 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
             const size_t lbytes = (size_t)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmaxBig, oB, oR, rcs) * sizeof(double);
             const int ipw = 64 / P.nu;
             for (int g = 0; g * ipw < lane_count; ++g) {
-                int r = emu::run_wave([&]() {
-#define COPRA_EMU_AXIS_L(NU, NMAX)                                                                                       \
-    (Pl.axis_const ? lmpc_axis_body<2, NU, NMAX, kAxisQmaxBig, false, true, 2, true>(Pl, g) : lmpc_axis_body<2, NU, NMAX, kAxisQmaxBig, false, false, 2, true>(Pl, g))
-                    if (P.nx == P.nu && P.N > 20) lmpc_axis_body<1, 2, 31, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                    else if (P.nx == P.nu) {
-                        if (P.nu == 3) lmpc_axis_body<1, 3, 20, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                        else lmpc_axis_body<1, 2, 20, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                    } else if (P.nx == 3 * P.nu) {
-                        if (P.nu == 3) lmpc_axis_body<3, 3, 20, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                        else lmpc_axis_body<3, 2, 20, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                    } else if (P.nu == 3 && P.N == 21) lmpc_axis_body<2, 3, 21, kAxisQmaxBig, false, false, 2, true>(Pl, g);
-                    else if (P.nu == 3) COPRA_EMU_AXIS_L(3, 20);
-                    else if (P.N <= 20) COPRA_EMU_AXIS_L(2, 20);
-                    else COPRA_EMU_AXIS_L(2, 31);
-#undef COPRA_EMU_AXIS_L
-                }, lbytes, g, 1);
-                if (r != 0) return -100;
+                bool ran = false;
+                int r = emu::run_wave([&]() { ran = emu_axis_body(second, false, Pl, g); }, lbytes, g, 1);
+                if (r != 0 || !ran) return -100;
             }
             if (std::getenv("COPRA_EMU_AXIS_REPORT")) { // (tools: who is listed, and why)
                 int bad1 = 0, bad2 = 0;

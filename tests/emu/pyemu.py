@@ -32,6 +32,18 @@ def lib():
     return _lib
 
 
+AXIS_FAMILIES = ("first", "first_w", "list", "list_w")  # (axis_builds.hpp: AxisFamily)
+
+
+def axis_build(nx, nu, N, axis_const, axis_rpa, stage_refs, weights, list_):
+    """the build of the (instance, axis)-per-lane solver the library picks for a controller (axis_builds.hpp: pick_axis_build):
+    (family, NXA, NU, NMAX, QMAX, EXACT, CT, RPA), or None"""
+    out = (C.c_int * 8)()
+    if not lib().emu_axis_build(nx, nu, N, int(axis_const), axis_rpa, int(stage_refs), int(weights), int(list_), out):
+        return None
+    return (AXIS_FAMILIES[out[0]], out[1], out[2], out[3], out[4], bool(out[5]), bool(out[6]), out[7])
+
+
 def _sync_options():
     """hand _capi.OPTIONS (what BatchLMPC would pass to copra_batch_create_with_options) to the harness"""
     o = _capi.make_options()

@@ -1872,3 +1872,67 @@ def test_axis_solver_is_a_choice_of_kernels_not_of_results(emu, oracle, monkeypa
     rb = emu.lmpc_solve(*args)
     assert (ra["status"] == rb["status"]).all() and (ra["iter"] == rb["iter"]).all()
     assert _rel(ra["control"], rb["control"]) <= 1e-9 and _rel(ra["trajectory"], rb["trajectory"]) <= 1e-9
+
+
+# Which build of the solver a controller gets (copra_amd/csrc/axis_builds.hpp: pick_axis_build -- the library's select_axis_kernel and
+# select_axis_list_kernel, and the emulator above).  Per (nx, nu, N) and the stage_refs it is checked at: the first launch's build where the
+# tables are the same at every step (axis_const) at axis_rpa 0 and 1, and at 2; where they are not (axis_rpa 0 to 2); the second chance's where
+# they are and where they are not.
+AXIS_PICKS = [
+    # (NXA, NU, NMAX) = (2, 3, 20): the headline's horizon compiled in -- not with reference trajectories -- or not
+    (6, 3, 20, (False,), ("first", 2, 3, 20, 6, True, True, 1), ("first", 2, 3, 20, 6, True, True, 2), ("first", 2, 3, 20, 6, False, False, 2),
+     ("list", 2, 3, 20, 16, False, True, 2), ("list", 2, 3, 20, 16, False, False, 2)),
+    (6, 3, 20, (True,), ("first", 2, 3, 20, 6, False, True, 1), ("first", 2, 3, 20, 6, False, True, 2), ("first", 2, 3, 20, 6, False, False, 2),
+     ("list", 2, 3, 20, 16, False, True, 2), ("list", 2, 3, 20, 16, False, False, 2)),
+    (6, 3, 19, (False, True), ("first", 2, 3, 20, 6, False, True, 1), ("first", 2, 3, 20, 6, False, True, 2), ("first", 2, 3, 20, 6, False, False, 2),
+     ("list", 2, 3, 20, 16, False, True, 2), ("list", 2, 3, 20, 16, False, False, 2)),
+    (4, 2, 20, (False, True), ("first", 2, 2, 20, 6, False, True, 1), ("first", 2, 2, 20, 6, False, True, 2), ("first", 2, 2, 20, 6, False, False, 2),
+     ("list", 2, 2, 20, 16, False, True, 2), ("list", 2, 2, 20, 16, False, False, 2)),
+    (4, 2, 25, (False, True), ("first", 2, 2, 31, 6, False, True, 1), ("first", 2, 2, 31, 6, False, True, 2), ("first", 2, 2, 31, 6, False, False, 2),
+     ("list", 2, 2, 31, 16, False, True, 2), ("list", 2, 2, 31, 16, False, False, 2)),
+    # one row per axis and step in registers, else the tables from LDS; the second chance reads them from LDS
+    (6, 3, 21, (False, True), ("first", 2, 3, 21, 6, False, True, 1), ("first", 2, 3, 21, 6, False, False, 2), ("first", 2, 3, 21, 6, False, False, 2),
+     ("list", 2, 3, 21, 16, False, False, 2), ("list", 2, 3, 21, 16, False, False, 2)),
+    (2, 2, 31, (False, True), ("first", 1, 2, 31, 6, False, True, 1), ("first", 1, 2, 31, 6, False, False, 2), ("first", 1, 2, 31, 6, False, False, 2),
+     ("list", 1, 2, 31, 16, False, False, 2), ("list", 1, 2, 31, 16, False, False, 2)),
+    (2, 2, 20, (False, True), ("first", 1, 2, 20, 6, False, True, 1), ("first", 1, 2, 20, 6, False, False, 2), ("first", 1, 2, 20, 6, False, False, 2),
+     ("list", 1, 2, 20, 16, False, False, 2), ("list", 1, 2, 20, 16, False, False, 2)),
+    (3, 3, 20, (False, True), ("first", 1, 3, 20, 6, False, True, 1), ("first", 1, 3, 20, 6, False, False, 2), ("first", 1, 3, 20, 6, False, False, 2),
+     ("list", 1, 3, 20, 16, False, False, 2), ("list", 1, 3, 20, 16, False, False, 2)),
+    (6, 2, 20, (False, True), ("first", 3, 2, 20, 6, False, True, 1), ("first", 3, 2, 20, 6, False, False, 2), ("first", 3, 2, 20, 6, False, False, 2),
+     ("list", 3, 2, 20, 16, False, False, 2), ("list", 3, 2, 20, 16, False, False, 2)),
+    (9, 3, 14, (False, True), ("first", 3, 3, 20, 6, False, True, 1), ("first", 3, 3, 20, 6, False, False, 2), ("first", 3, 3, 20, 6, False, False, 2),
+     ("list", 3, 3, 20, 16, False, False, 2), ("list", 3, 3, 20, 16, False, False, 2)),
+]
+# ... and with per-instance cost weights: the headline's shape only; the first launch only with its tables in registers
+AXIS_PICKS_WEIGHTED = [
+    (6, 3, 20, (False,), ("first_w", 2, 3, 20, 6, True, True, 1), ("first_w", 2, 3, 20, 6, True, True, 2), None,
+     ("list_w", 2, 3, 20, 16, False, True, 2), ("list_w", 2, 3, 20, 16, False, False, 2)),
+    (6, 3, 20, (True,), ("first_w", 2, 3, 20, 6, False, True, 1), ("first_w", 2, 3, 20, 6, False, True, 2), None,
+     ("list_w", 2, 3, 20, 16, False, True, 2), ("list_w", 2, 3, 20, 16, False, False, 2)),
+    (6, 3, 12, (False, True), ("first_w", 2, 3, 20, 6, False, True, 1), ("first_w", 2, 3, 20, 6, False, True, 2), None,
+     ("list_w", 2, 3, 20, 16, False, True, 2), ("list_w", 2, 3, 20, 16, False, False, 2)),
+] + [(nx, nu, N, (False, True), None, None, None, None, None) for nx, nu, N in [(4, 2, 20), (4, 2, 25), (6, 3, 21), (2, 2, 20), (9, 3, 20)]]
+
+
+@pytest.mark.parametrize("weights,nx,nu,N,refs,ct1,ct2,lds,list_ct,list_lds",
+                         [(False,) + p for p in AXIS_PICKS] + [(True,) + p for p in AXIS_PICKS_WEIGHTED])
+def test_axis_solver_builds_a_controller_gets(emu, weights, nx, nu, N, refs, ct1, ct2, lds, list_ct, list_lds):
+    for stage_refs in refs:
+        for rpa in (0, 1, 2):
+            assert emu.axis_build(nx, nu, N, True, rpa, stage_refs, weights, False) == (ct1 if rpa <= 1 else ct2), (stage_refs, rpa)
+            assert emu.axis_build(nx, nu, N, False, rpa, stage_refs, weights, False) == lds, (stage_refs, rpa)
+            assert emu.axis_build(nx, nu, N, True, rpa, stage_refs, weights, True) == list_ct, (stage_refs, rpa)
+            assert emu.axis_build(nx, nu, N, False, rpa, stage_refs, weights, True) == list_lds, (stage_refs, rpa)
+
+
+@pytest.mark.parametrize("nx,nu,N", [(2, 1, 20), (4, 1, 10), (5, 2, 10), (7, 3, 10), (6, 3, 22), (4, 2, 32), (3, 3, 21), (9, 3, 21),
+                                     (8, 4, 10), (8, 2, 10), (6, 3, 0)])
+def test_axis_solver_has_no_build_for_other_shapes(emu, nx, nu, N):
+    """one control, states that do not split evenly over the controls, horizons past the builds', four axes, four states per axis"""
+    for axis_const in (False, True):
+        for rpa in (0, 1, 2):
+            for stage_refs in (False, True):
+                for weights in (False, True):
+                    for list_ in (False, True):
+                        assert emu.axis_build(nx, nu, N, axis_const, rpa, stage_refs, weights, list_) is None
