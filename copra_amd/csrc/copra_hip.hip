@@ -386,6 +386,36 @@ static hipError_t begin_overflow_queue(copra_batch* h, hipStream_t s, bool self_
     }
     return hipSuccess;
 }
+// Its mirror for the list of a front end (the one-instance-per-lane pass, the (instance, axis)-per-lane solver): two counters used in turn, the
+// front end zeroes the other one while it runs
+static void begin_lane_list(copra_batch* h, FusedPlan& P)
+{
+    h->lane_cur ^= 1;
+    P.lane_list = h->d_lane_list;
+    P.lane_count = h->d_lane_count + h->lane_cur;
+    P.lane_zero = h->d_lane_count + (h->lane_cur ^ 1);
+}
+// ... and the grid of a first tier that takes its instances from that list: it is dealt out in eighths (ric_tier_instance)
+static unsigned list_grid(int batch) { return ((unsigned)batch + 7u) & ~7u; }
+
+// One launch of a kernel of the library: the opt-in to its dynamic LDS, the launch, its error.  ext_timed: `start` / `stop` travel in the launch's
+// own dispatch packet (hipExtLaunchKernelGGL; nullptr: none) -- solve_one_wave, whose timing depends on WHICH packet carries which event.
+template <class K, class... Args>
+static hipError_t launch_timed(bool ext_timed, hipEvent_t start, hipEvent_t stop, K kernel, unsigned grid, unsigned threads, size_t lds, hipStream_t s, const Args&... args)
+{
+    const hipError_t e = lds_opt_in(reinterpret_cast<const void*>(kernel), lds);
+    if (e != hipSuccess) return e;
+    if (ext_timed)
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, start, stop, 0, args...);
+    else
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, args...);
+    return hipGetLastError();
+}
+template <class K, class... Args>
+static hipError_t launch(K kernel, unsigned grid, unsigned threads, size_t lds, hipStream_t s, const Args&... args)
+{
+    return launch_timed(false, nullptr, nullptr, kernel, grid, threads, lds, s, args...);
+}
 
 // ---- the one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp) ----
 static fused_kernel_t select_lane_kernel(const FusedPlan& P)
@@ -522,7 +552,7 @@ static copra_status_t ensure_lane_buffers(copra_batch* h, bool need_ws)
     }
     if (e == hipSuccess && need_ws && !h->d_lane_ws) // (the shared-model form of the pass has no sweep: no workspace)
         e = hipMalloc((void**)&h->d_lane_ws, (size_t)P.N * lane_ws_rows(P.nx, P.nu) * bp * sizeof(double));
-    const bool hand_over = P.lds.ricC && !h->hp.opt.no_lane_handover && (h->hp.opt.no_lane_spec || h->ad.lane_form_handover); // (solve_one_wave: the form of the pass that hands blocks over)
+    const bool hand_over = P.lds.ricC && !h->hp.opt.no_lane_handover && (h->hp.opt.no_lane_spec || h->ad.lane_form_handover); // (launch_lane_pass: the form of the pass that hands blocks over)
     if (e == hipSuccess && need_ws && hand_over && !h->d_lane_ws2) { // (the hand-over blocks: what only the first tier reads, instance-major)
         // (round-5 advisor: 126 MB at 65 536 instances -- without room for them the pass keeps its speculating form, which needs none, instead of
         //  being switched off for good with everything else freed)
@@ -546,6 +576,49 @@ static copra_status_t ensure_lane_buffers(copra_batch* h, bool need_ws)
     }
     return COPRA_OK;
 }
+// ... and what the (instance, axis)-per-lane solver needs on top of the pass's list, under the same contract.  false: no room on the device -- the
+// solver is off for this controller.  The pinned words the list lengths arrive in are not essential: without them no grid follows the lengths.
+static bool ensure_axis_buffers(copra_batch* h, const FusedPlan& P)
+{
+    bool ok = ensure_lane_buffers(h, false) == COPRA_OK;
+    hipError_t e = hipSuccess;
+    if (ok && (!h->d_axis_list2 || !h->d_axis_count2)) { // the second chance's own list (the first tier's, then) and its length
+        (void)hipFree(h->d_axis_list2);
+        (void)hipFree(h->d_axis_count2);
+        h->d_axis_list2 = h->d_axis_count2 = nullptr;
+        e = hipMalloc((void**)&h->d_axis_list2, ((size_t)P.batch + 64) * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_axis_count2, 4 * sizeof(int)); // ([0]: entries; [2]: instances its own steps ended, as d_lane_count)
+        if (e == hipSuccess) e = hipMemset(h->d_axis_count2, 0, 4 * sizeof(int));
+    }
+    if (ok && e == hipSuccess && !h->d_axis_acc) { // (one word per instance on spare lanes, at most one per nu waves: sized for the batch once)
+        int spare = 0;
+        const size_t words = (size_t)axis_grid(P.nu, P.batch, spare) / (size_t)P.nu + 2;
+        e = hipMalloc((void**)&h->d_axis_acc, words * sizeof(int));
+        if (e == hipSuccess) e = hipMemset(h->d_axis_acc, 0, words * sizeof(int));
+    }
+    if (!ok || e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(h->d_axis_list2);
+        (void)hipFree(h->d_axis_count2);
+        (void)hipFree(h->d_axis_acc);
+        h->d_axis_list2 = h->d_axis_count2 = h->d_axis_acc = nullptr;
+        h->ad.axis_off = true;
+        return false;
+    }
+    if (!h->h_lane_seen) {
+        if (hipHostMalloc((void**)&h->h_lane_seen, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            h->h_lane_seen = nullptr;
+        } else {
+            h->h_lane_seen[0] = h->h_lane_seen[1] = h->h_lane_seen[2] = h->h_lane_seen[3] = 0;
+            if (hipHostGetDevicePointer((void**)&h->d_lane_seen, h->h_lane_seen, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                h->d_lane_seen = nullptr;
+            }
+        }
+    }
+    return true;
+}
 // The pass pays when a fair share of the batch ends in it.  After each of the first solves that ran it: if fewer than one instance in
 // eight did, it is switched off for this controller (it costs about a tenth of the first tier per instance).
 static copra_status_t adapt_lane_pass(copra_batch* h)
@@ -562,7 +635,7 @@ static copra_status_t adapt_lane_pass(copra_batch* h)
         h->ad.lane_spec_shared_off = false;
     }
     if (!h->ad.lane_ran || h->ad.lane_adapt_left <= 0) return COPRA_OK;
-    // In front of the compact variant of the Riccati-factor tier the pass has two forms (solve_one_wave).  The one that hands the factor
+    // In front of the compact variant of the Riccati-factor tier the pass has two forms (launch_lane_pass).  The one that hands the factor
     // over pays for every instance -- it is the tier's sweep, done at several times the efficiency: nothing to decide.  The speculating form
     // (the default) hands nothing over: it pays where most instances END in it; where fewer than one in four do -- constraint-heavy
     // workloads: the first picks are state rows, or the iteration goes on after two bounds on u_0 -- the controller moves to the hand-over
@@ -595,12 +668,10 @@ static copra_status_t adapt_lane_pass(copra_batch* h)
     }
     // (... and a shared-model controller with per-instance references: the pass carries their delta sweep, without it the controller runs
     //  lmpc_shared.hpp, which the tier beats by 2 x whatever the share that ends in the pass)
-    if (h->shared && h->shared_ric)
-        for (int t = 0; t < kMaxCosts; ++t)
-            if (h->cost_p[t]) {
-                h->ad.lane_adapt_left -= 1; // (the decision about its own steps above was this sample's)
-                return COPRA_OK;
-            }
+    if (h->shared && h->shared_ric && own_references(h)) {
+        h->ad.lane_adapt_left -= 1; // (the decision about its own steps above was this sample's)
+        return COPRA_OK;
+    }
     h->ad.lane_adapt_left -= 1;
     int left = 0;
     HIP_TRY(hipStreamSynchronize(h->last_stream));
@@ -637,6 +708,17 @@ static copra_status_t adapt_axis_solver(copra_batch* h)
     return COPRA_OK;
 }
 
+// The ONE place that moves the layout of a controller's first launch after creation.  repack: the step may leave the factor-only layouts, so the
+// lanes per instance are chosen again as at creation (the packed bodies are square-layout)
+static void set_layout(copra_batch* h, const LdsLayout lds, bool repack)
+{
+    h->hp.plan.lds = lds;
+    h->hp.lds_bytes = (size_t)lds.total * sizeof(double);
+    h->lds_attr_set = false;
+    const FusedPlan& P = h->hp.plan;
+    if (repack) h->packed = (P.lds.tri || h->hp.opt.no_packed) ? 0 : packed_width(P.n, P.nx * (P.nx + P.nu + 1), P.rfull > 0, h->hp.lds_bytes);
+}
+
 // Compact LDS layouts (R capped, overflow finished by the second tier) bet on small active sets.  After each of the
 // first solves the overflow queue tells whether the bet holds; if more than one instance in eight had to be redone by
 // the second tier, step to the next safer layout: dense -> safe (quarter-CU compact or full) -> full.
@@ -656,25 +738,16 @@ static copra_status_t adapt_layout(copra_batch* h)
     if ((long long)count * share <= (long long)h->hp.plan.batch) return COPRA_OK;
     LdsLayout roomier {};
     if (next_tri_layout(h->hp.plan, h->hp.plan.lds, roomier, h->hp.opt.no_ladder != 0)) { // factor-only: one instance per CU fewer, more columns
-        h->hp.plan.lds = roomier;
-        h->hp.lds_bytes = (size_t)roomier.total * sizeof(double);
-        h->lds_attr_set = false;
+        set_layout(h, roomier, false);
         h->ad.adapt_left += 1; // (a step down the ladder does not use up the budget of attempts)
         if (h->hp.opt.debug)
             fprintf(stderr, "[copra] %d of %d instances overflowed the factor-only layout: next %zu B, %d columns\n", count,
                 h->hp.plan.batch, h->hp.lds_bytes, roomier.rcap);
         return COPRA_OK;
     }
-    if (h->hp.dense && h->hp.safe_two_tier) { // dense -> quarter-CU compact
-        h->hp.plan.lds = h->hp.lds_safe;
-        h->hp.two_tier = true;
-    } else { // -> full layout, single tier
-        h->hp.plan.lds = h->hp.lds_full;
-        h->hp.two_tier = false;
-    }
+    h->hp.two_tier = h->hp.dense && h->hp.safe_two_tier; // dense -> quarter-CU compact, else -> full layout, single tier
     h->hp.dense = false;
-    h->hp.lds_bytes = (size_t)h->hp.plan.lds.total * sizeof(double);
-    h->lds_attr_set = false;
+    set_layout(h, h->hp.two_tier ? h->hp.lds_safe : h->hp.lds_full, true);
     h->shared_attr_set = false;
     if (h->shared_ric || h->has_lds_ric) {
         // the ladder of Riccati-factor layouts is exhausted: a shared-model controller leaves that tier for good (its first
@@ -683,11 +756,8 @@ static copra_status_t adapt_layout(copra_batch* h)
         h->has_lds_ric = false;
         h->model_dirty = true;
     }
-    const FusedPlan& P = h->hp.plan;
-    h->packed = (P.lds.tri || h->hp.opt.no_packed) ? 0
-        : packed_width(P.n, P.nx * (P.nx + P.nu + 1), P.rfull > 0, h->hp.lds_bytes);
     if (h->hp.opt.debug)
-        fprintf(stderr, "[copra] %d of %d instances overflowed the compact LDS layout: next layout %zu B, %s\n", count, P.batch,
+        fprintf(stderr, "[copra] %d of %d instances overflowed the compact LDS layout: next layout %zu B, %s\n", count, h->hp.plan.batch,
             h->hp.lds_bytes, h->hp.two_tier ? "two-tier" : "single tier");
     return COPRA_OK;
 }
@@ -740,12 +810,84 @@ static copra_status_t rechoose_layout(copra_batch* h)
         if (h->hp.opt.debug)
             fprintf(stderr, "[copra] final active sets of the last solve: first tier from %d to %d columns (%zu B)\n", P.lds.rcap, pick.rcap,
                 (size_t)pick.total * sizeof(double));
-        h->hp.plan.lds = pick;
-        h->hp.lds_bytes = (size_t)pick.total * sizeof(double);
-        h->lds_attr_set = false;
+        set_layout(h, pick, false);
         if (h->ad.adapt_left < 2) h->ad.adapt_left = 2;
     }
     return COPRA_OK;
+}
+
+// First solve of a controller on a factor-only tier with a layout ladder: the pass has counted, per instance it leaves over, the rows its
+// unconstrained minimiser violates (FusedPlan::lane_hist); the layout the tier STARTS on is chosen from that histogram.
+// The size of an instance's final active set goes with the number of rows its unconstrained minimiser violates (~ 1.1 x, correlation 0.9 from the
+// headline's to the tightest workload of the tests): step down the ladder until at most one instance in `share` is expected to outgrow the first
+// tier -- BEFORE its first launch, with ONE synchronisation in the controller's life, instead of after each of the first solves (round 3: the
+// first solve of the tight workload took 10.4 ms, the steady state 2.8 ms).  adapt_layout keeps checking the real overflow counts of the first
+// solves behind this.
+static copra_status_t start_layout_from_histogram(copra_batch* h, FusedPlan& P, hipStream_t s)
+{
+    h->ad.lane_predict_left -= 1;
+    int hist[kLaneHistBins];
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(hist, h->d_lane_hist, sizeof hist, hipMemcpyDeviceToHost));
+    const long long share = h->hp.plan.lds.ric ? 64 : 8;
+    for (;;) {
+        long long over = 0;
+        for (int b = 0; b < kLaneHistBins; ++b)
+            if (b + (b + 3) / 4 > h->hp.plan.lds.rcap) over += hist[b]; // (a little above the mean: the tail decides)
+        LdsLayout roomier {};
+        if (over * share <= (long long)P.batch || !next_tri_layout(h->hp.plan, h->hp.plan.lds, roomier)) break;
+        set_layout(h, roomier, false);
+        if (h->hp.opt.debug)
+            fprintf(stderr, "[copra] %lld of %d instances are expected to outgrow the first tier: starting on %zu B, %d columns\n", over,
+                P.batch, h->hp.lds_bytes, roomier.rcap);
+    }
+    P.lds = h->hp.plan.lds;
+    P.lane_hist = nullptr;
+    return COPRA_OK;
+}
+
+// ---- the lengths of the (instance, axis)-per-lane solver's recent lists (AdaptState::lane_seen_*) and the three choices that follow them ----
+// The length of a solve's lists travels to the host behind it, into pinned words nobody waits for (no synchronisation: a solve takes whatever has
+// arrived).  They count where the tier's grid may follow them: a two-tier launch of the library's own one-wave kernels.
+static bool list_window_used(const copra_batch* h, bool jit_launch) { return h->hp.two_tier && !jit_launch && !h->packed && h->h_lane_seen; }
+// what the LAST solve left in the pinned words; the window starts again every 64 solves.  Called between the first-tier and the second-tier
+// launch of a solve on the solver (solve_one_wave): the choices below see a length one solve after it arrived
+static void adapt_list_window(copra_batch* h)
+{
+    AdaptState& ad = h->ad;
+    if (!h->h_lane_seen) return;
+    if (ad.lane_seen_solves > 0) {
+        const int seen = h->h_lane_seen[ad.lane_seen_slot], seen1 = h->h_lane_seen[2 + ad.lane_seen_slot];
+        const bool restart = ad.lane_seen_solves % 64 == 0;
+        ad.lane_seen_max = (restart || seen > ad.lane_seen_max) ? seen : ad.lane_seen_max;
+        ad.lane_seen_first_max = (restart || seen1 > ad.lane_seen_first_max) ? seen1 : ad.lane_seen_first_max;
+    }
+    ad.lane_seen_slot ^= 1;
+    ad.lane_seen_solves += 1;
+}
+// A controller whose solver has listed NOTHING in its recent solves (the headline: all 65 536 instances end in it) launches neither the
+// second chance nor the first tier -- three launches that find nothing cost 13 us of a 100 us step --: the tier-2 launch, a grid-stride
+// loop, walks the solver's own list from its first entry.  Should the list fill after all (a workload changes) that launch solves it,
+// slowly, and the next solves see the length that has travelled to the host in the meantime.
+static bool adapt_axis_quiet(const copra_batch* h, bool jit_launch)
+{
+    return list_window_used(h, jit_launch) && h->ad.lane_seen_solves >= 4 && h->ad.lane_seen_first_max == 0 && h->ad.lane_seen_max == 0;
+}
+// The second chance's grid: a few waves that walk the solver's list, however long it is
+static unsigned adapt_second_chance_grid(const copra_batch* h, int nu)
+{
+    const long long want = (4LL * h->ad.lane_seen_first_max) / (64 / nu) + 8;
+    return (unsigned)(want < 8 ? 8 : want > 512 ? 512 : want); // (one wave per CU at most: 256 CUs)
+}
+// The tier's grid: one workgroup per list entry -- and 65 536 workgroups that find none cost 15 us, a sixth of the headline's step.  Four times
+// the longest of the last lists + 256 workgroups are launched, entry w by workgroup w, and the second launch walks whatever lies beyond
+// (tier-2 kernel: a grid-stride loop -- slow, and only ever busy on the solve in which a workload changes).
+static void adapt_tier_cap(const copra_batch* h, FusedPlan& P, bool jit_launch, bool quiet)
+{
+    if (!list_window_used(h, jit_launch)) return;
+    const long long cap = 4LL * h->ad.lane_seen_max + 256;
+    if (h->ad.lane_seen_solves >= 2 && cap < (long long)P.batch) P.lane_cap = (int)((cap + 7) & ~7LL);
+    P.lane_rest = quiet ? 0 : P.lane_cap > 0 ? P.lane_cap : -1;
 }
 
 copra_status_t ensure_lds_attr(copra_batch* h)
@@ -776,8 +918,7 @@ copra_status_t ensure_lds_attr(copra_batch* h)
 copra_status_t prepare_riccati(copra_batch* h)
 {
     const bool all_bounds = h->d_lb_inst != nullptr;
-    bool refs = false; // per-instance cost references: q_k differs per instance, which only the streaming kernel evaluates
-    for (int t = 0; t < kMaxCosts; ++t) refs = refs || h->cost_p[t] != nullptr;
+    const bool refs = own_references(h); // per-instance cost references: q_k differs per instance, which only the streaming kernel evaluates
     if (h->ric_built && h->ric_all_bounds == all_bounds && h->ric_refs == refs) return COPRA_OK;
     h->ric_refs = refs;
     for (void* q : h->ric_dev) (void)hipFree(q);
@@ -1209,9 +1350,7 @@ copra_status_t copra_batch_set_shared_system(copra_batch_t* h, const double* A, 
     h->shared_ric = false;
     LdsLayout lq {};
     if (tri_layout_with_lds_q1(h->hp.plan, h->hp.plan.lds, lq)) { // the shared-model kernels keep Q1 in LDS
-        h->hp.plan.lds = lq;
-        h->hp.lds_bytes = (size_t)lq.total * sizeof(double);
-        h->lds_attr_set = false;
+        set_layout(h, lq, false);
         h->shared_attr_set = false;
     }
     return COPRA_OK;
@@ -1448,9 +1587,7 @@ static copra_status_t choose_shared_tier(copra_batch* h)
     // controller-wide references, an instance's own feed-forward terms come from the DELTA sweep of the shared lane pass
     // (lmpc_lane_shared_body) -- so the records form takes them where that pass runs; elsewhere lmpc_shared.hpp (reference columns of
     // the shared model), as for every such controller before round 4 (96 vs 200 M solves/s at the headline shape).
-    bool refs = false;
-    for (int t = 0; t < kMaxCosts; ++t) refs = refs || h->cost_p[t];
-    if (want && refs) {
+    if (want && own_references(h)) {
         const FusedPlan Pw = device_plan(h);
         want = !h->ad.lane_off && !h->hp.opt.no_lane_pass && lane_batch_ok(h->hp.opt, Pw.batch, true, true) && Pw.lane_tab >= 0 && Pw.lane_cref >= 0
             && h->lds_ric.ricC && !Pw.prof && !Pw.prof_fine && !Pw.row_f_inst && select_lane_shared_kernel(Pw) != nullptr;
@@ -1461,18 +1598,21 @@ static copra_status_t choose_shared_tier(copra_batch* h)
     }
     if (want != h->shared_ric) {
         LdsLayout lq {};
-        if (want) {
-            h->hp.plan.lds = h->lds_ric;
-        } else if (tri_layout_with_lds_q1(h->hp.plan, h->lds_ric, lq)) {
-            h->hp.plan.lds = lq;
-        }
-        h->hp.lds_bytes = (size_t)h->hp.plan.lds.total * sizeof(double);
+        set_layout(h, want ? h->lds_ric : tri_layout_with_lds_q1(h->hp.plan, h->lds_ric, lq) ? lq : h->hp.plan.lds, false);
         h->hp.two_tier = true;
-        h->lds_attr_set = false;
         h->shared_attr_set = false;
         h->shared_ric = want;
         h->model_dirty = true;
     }
+    return COPRA_OK;
+}
+
+// The end of a solve whose launches carry no events in their packets: one record behind the last of them
+static copra_status_t end_of_solve(copra_batch* h, hipStream_t s)
+{
+    HIP_TRY(hipEventRecord(h->ev1, s));
+    h->timed = true;
+    h->tier_timed = false;
     return COPRA_OK;
 }
 
@@ -1510,17 +1650,13 @@ static copra_status_t solve_shared_model(copra_batch* h, hipStream_t s)
         // in front of it the one-instance-per-lane pass in its shared-model form (lmpc_lane.hpp): the roll-out of every instance from
         // the batch-wide records; the tier solves what it leaves over, starting from the U and X it wrote
         unsigned g1 = (unsigned)P.batch;
-        bool refs_now = false; // (then the pass MUST run: the choice of this tier above has checked that it can)
-        for (int t = 0; t < kMaxCosts; ++t) refs_now = refs_now || h->cost_p[t];
+        const bool refs_now = own_references(h); // (then the pass MUST run: the choice of this tier above has checked that it can)
         bool pass_ran = false;
         if (!h->ad.lane_off && !h->hp.opt.no_lane_pass && lane_batch_ok(h->hp.opt, P.batch, true, refs_now) && P.lane_tab >= 0 && P.lds.ricC && !P.prof && !P.prof_fine
             && !P.row_f_inst && select_lane_shared_kernel(P) && (ensure_lane_buffers(h, refs_now) == COPRA_OK || (h->ad.lane_off = true, false))) {
             // (no room for the pass's list: the tier alone, from now on -- as on the per-instance path below)
-            h->lane_cur ^= 1;
+            begin_lane_list(h, Pr);
             h->ad.lane_ran = true;
-            Pr.lane_list = h->d_lane_list;
-            Pr.lane_count = h->d_lane_count + h->lane_cur;
-            Pr.lane_zero = h->d_lane_count + (h->lane_cur ^ 1);
             Pr.lane_bp = (int)(((size_t)P.batch + kWave - 1) / kWave * kWave);
             Pr.lane_ws = refs_now ? h->d_lane_ws : nullptr; // (the delta feed-forward terms of instances with their own references)
             Pr.lane_spec = (h->hp.opt.no_lane_spec || h->ad.lane_spec_shared_off) ? 0 : 1; // (the first steps of the iteration in the pass, lmpc_lane_shared_body: the tier then rolls out again)
@@ -1529,14 +1665,12 @@ static copra_status_t solve_shared_model(copra_batch* h, hipStream_t s)
             Pr.lane_from_list = 1;
             Pr.lane_handover = 1;
             Pr.lane_zero = nullptr;
-            g1 = ((unsigned)P.batch + 7u) & ~7u; // (the list is dealt out in eighths: ric_tier_instance)
+            g1 = list_grid(P.batch);
             pass_ran = true;
         }
         if (refs_now && !pass_ran)
             return fail(COPRA_ERR_RUNTIME, "copra_batch_solve: per-instance references on the shared-model records tier need the lane pass in front");
-        LDS_OPT_IN(select_fused_kernel(Pr), h->hp.lds_bytes);
-        hipLaunchKernelGGL(select_fused_kernel(Pr), dim3(g1), dim3(64), h->hp.lds_bytes, s, Pr);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(select_fused_kernel(Pr), g1, 64, h->hp.lds_bytes, s, Pr));
     } else if (h->jit_shared && h->jit_lanes == (h->packed ? h->packed : 64) && h->jit_tri == P.lds.tri) {
         FusedPlan Pj = P;
         void* args[] = { &Pj };
@@ -1547,23 +1681,16 @@ static copra_status_t solve_shared_model(copra_batch* h, hipStream_t s)
     } else if (h->packed) {
         HIP_TRY(h->packed == 16 ? packed_launch_w16(P, true, h->hp.lds_bytes, s) : packed_launch_w32(P, true, h->hp.lds_bytes, s));
     } else {
-        LDS_OPT_IN(select_shared_kernel(P, false), h->hp.lds_bytes);
-        hipLaunchKernelGGL(select_shared_kernel(P, false), dim3((unsigned)P.batch), dim3(64), h->hp.lds_bytes, s, P);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(select_shared_kernel(P, false), (unsigned)P.batch, 64, h->hp.lds_bytes, s, P));
     }
     if (h->hp.two_tier) {
         FusedPlan P2 = P;
         P2.lds = h->hp.lds_full;
         P2.from_list = 1;
         const unsigned g2 = (unsigned)(P.batch < 1024 ? P.batch : 1024);
-        LDS_OPT_IN(select_shared_kernel(P2, true), h->hp.lds_full_bytes);
-        hipLaunchKernelGGL(select_shared_kernel(P2, true), dim3(g2), dim3(64), h->hp.lds_full_bytes, s, P2);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(select_shared_kernel(P2, true), g2, 64, h->hp.lds_full_bytes, s, P2));
     }
-    HIP_TRY(hipEventRecord(h->ev1, s));
-    h->timed = true;
-    h->tier_timed = false;
-    return COPRA_OK;
+    return end_of_solve(h, s);
 }
 
 // more than 64 decision variables: the stage-wise interior-point kernel with the workgroup Goldfarb-Idnani kernel behind it, or the latter alone
@@ -1575,30 +1702,16 @@ static copra_status_t solve_large(copra_batch* h, FusedPlan& P, hipStream_t s)
         HIP_TRY(begin_overflow_queue(h, s, false, P));
         HIP_TRY(hipMemsetAsync(h->d_ric_next, 0, sizeof(int), s));
         const riccati_kernel_t ric_fn = h->ric_fast ? copra_lmpc_riccati_mfma_kernel : select_riccati_kernel(P.nx, P.nu);
-        LDS_OPT_IN(ric_fn, ric_lds);
-        hipLaunchKernelGGL(ric_fn, dim3((unsigned)h->ric_grid), dim3(64), ric_lds, s, P, h->hs.sp);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(ric_fn, (unsigned)h->ric_grid, 64, ric_lds, s, P, h->hs.sp));
         if (!h->hp.ric_only) { // (beyond the condensed kernels' sizes the instances that did not converge keep status 3)
             FusedPlan P2 = P;
             P2.from_list = 1;
-            LDS_OPT_IN(h->large_fn, h->hp.lds_bytes);
-            hipLaunchKernelGGL(h->large_fn, dim3((unsigned)h->large_grid), dim3((unsigned)P.large.threads),
-                h->hp.lds_bytes, s, P2);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch(h->large_fn, (unsigned)h->large_grid, (unsigned)P.large.threads, h->hp.lds_bytes, s, P2));
         }
-        HIP_TRY(hipEventRecord(h->ev1, s));
-        h->timed = true;
-        h->tier_timed = false;
-        return COPRA_OK;
+        return end_of_solve(h, s);
     }
-    LDS_OPT_IN(h->large_fn, h->hp.lds_bytes);
-    hipLaunchKernelGGL(h->large_fn, dim3((unsigned)h->large_grid), dim3((unsigned)P.large.threads),
-        h->hp.lds_bytes, s, P);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev1, s));
-    h->timed = true;
-    h->tier_timed = false;
-    return COPRA_OK;
+    HIP_TRY(launch(h->large_fn, (unsigned)h->large_grid, (unsigned)P.large.threads, h->hp.lds_bytes, s, P));
+    return end_of_solve(h, s);
 }
 
 // InitialStateLMPC up to 64 variables: one wave (or 16 / 32 lanes) per instance
@@ -1607,14 +1720,9 @@ static copra_status_t solve_initial_state(copra_batch* h, FusedPlan& P, hipStrea
     if (h->packed) {
         HIP_TRY(h->packed == 16 ? packed_launch_w16(P, false, h->hp.lds_bytes, s) : packed_launch_w32(P, false, h->hp.lds_bytes, s));
     } else {
-        LDS_OPT_IN(copra_islmpc_fused_kernel, h->hp.lds_bytes);
-        hipLaunchKernelGGL(copra_islmpc_fused_kernel, dim3((unsigned)P.batch), dim3(64), h->hp.lds_bytes, s, P);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch(copra_islmpc_fused_kernel, (unsigned)P.batch, 64, h->hp.lds_bytes, s, P));
     }
-    HIP_TRY(hipEventRecord(h->ev1, s));
-    h->timed = true;
-    h->tier_timed = false;
-    return COPRA_OK;
+    return end_of_solve(h, s);
 }
 
 // Per-instance weights (own_weights): the Riccati-factor tier reads its stage costs from tables the plan builder weighted with the creation
@@ -1627,306 +1735,198 @@ static void weights_route(copra_batch* h)
     if (own && !h->wt_saved && h->hp.plan.lds.ric && !h->hp.large && !h->hp.plan.initial_state) {
         h->wt_saved = true;
         h->wt_lds = h->hp.plan.lds;
-        h->wt_lds_bytes = h->hp.lds_bytes;
         h->wt_two_tier = h->hp.two_tier;
         h->wt_dense = h->hp.dense;
         h->wt_packed = h->packed;
-        if (h->hp.dense && h->hp.safe_two_tier && !h->hp.lds_safe.ric) {
-            h->hp.plan.lds = h->hp.lds_safe;
-            h->hp.two_tier = true;
-        } else {
-            h->hp.plan.lds = h->hp.lds_full;
-            h->hp.two_tier = false;
-        }
+        h->hp.two_tier = h->hp.dense && h->hp.safe_two_tier && !h->hp.lds_safe.ric;
         h->hp.dense = false;
-        h->hp.lds_bytes = (size_t)h->hp.plan.lds.total * sizeof(double);
-        const FusedPlan& P = h->hp.plan;
-        h->packed = (P.lds.tri || h->hp.opt.no_packed) ? 0 : packed_width(P.n, P.nx * (P.nx + P.nu + 1), P.rfull > 0, h->hp.lds_bytes);
-        h->lds_attr_set = false;
+        set_layout(h, h->hp.two_tier ? h->hp.lds_safe : h->hp.lds_full, true);
     } else if (!own && h->wt_saved) {
         h->wt_saved = false;
-        h->hp.plan.lds = h->wt_lds;
-        h->hp.lds_bytes = h->wt_lds_bytes;
+        set_layout(h, h->wt_lds, false); // (its size in bytes is the layout's total everywhere a layout is set)
         h->hp.two_tier = h->wt_two_tier;
         h->hp.dense = h->wt_dense;
         h->packed = h->wt_packed;
-        h->lds_attr_set = false;
     }
 }
 
-// The one-wave kernels: [one-instance-per-lane pass ->] first tier [-> second tier].  ext_timed: the launches carry their events in their
-// dispatch packets (hipExtLaunchKernelGGL): start of the first launch, end of the first tier (copra_batch_last_first_tier_seconds), end of
-// the solve -- no barrier packets in the stream: two hipEventRecord per solve cost ~ 20 us between consecutive solves, 3 % of a headline step.
-static copra_status_t solve_one_wave(copra_batch* h, FusedPlan& P, hipStream_t s, bool jit_launch, bool ext_timed)
+// ---- the stages of solve_one_wave, in the order they run.  ext_timed: the launches carry their events in their dispatch packets (launch_timed):
+//      start of the first launch, end of the first tier (copra_batch_last_first_tier_seconds), end of the solve -- no barrier packets in the
+//      stream: two hipEventRecord per solve cost ~ 20 us between consecutive solves, 3 % of a headline step. ----
+
+// Front end, where the controller's axes are decoupled: the one-(instance, axis)-per-lane solver (lmpc_axis.hpp) and the second chance of what
+// it lists.  Leaves P as the first tier behind them takes it; quiet: no second chance was launched and no first tier is to be (adapt_axis_quiet)
+static copra_status_t launch_axis_solver(copra_batch* h, FusedPlan& P, hipStream_t s, bool jit_launch, bool ext_timed, bool& quiet)
 {
-    // the one-instance-per-lane pass (lmpc_lane.hpp): every instance whose unconstrained minimiser violates nothing ends in it, the
-    // first tier below runs for the others only
-    bool lane_pass = lane_pass_wanted(h, P, jit_launch);
-    // ... or, where the controller's axes are decoupled, the one-(instance, axis)-per-lane solver (lmpc_axis.hpp): it finishes every instance
-    // whose axes keep their active sets within its lanes' room; the first tier below runs for what it lists
-    bool axis_pass = axis_solver_wanted(h, P), axis_quiet = false;
-    if (axis_pass && ensure_lane_buffers(h, false) != COPRA_OK) {
-        (void)hipGetLastError();
-        h->ad.axis_off = true;
-        axis_pass = false;
-    }
+    begin_lane_list(h, P);
+    h->ad.axis_ran = true;
     int axis_spare = 0;
-    const int axis_waves = axis_pass ? axis_grid(P.nu, P.batch, axis_spare) : 0;
-    if (axis_pass && !h->d_axis_list2) { // the second chance's own list (the first tier's, then) and its length
-        hipError_t e = hipMalloc((void**)&h->d_axis_list2, ((size_t)P.batch + 64) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_axis_count2, 4 * sizeof(int)); // ([0]: entries; [2]: instances its own steps ended, as d_lane_count)
-        if (e == hipSuccess) e = hipMemset(h->d_axis_count2, 0, 4 * sizeof(int));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(h->d_axis_list2);
-            (void)hipFree(h->d_axis_count2);
-            h->d_axis_list2 = h->d_axis_count2 = nullptr;
-            h->ad.axis_off = true;
-            axis_pass = false;
-        }
+    const int axis_waves = axis_grid(P.nu, P.batch, axis_spare);
+    P.axis_count2 = h->d_axis_count2;
+    P.axis_list_in = nullptr;
+    P.axis_list_count = nullptr;
+    P.axis_waves = axis_waves;
+    P.axis_pf = axis_waves > 1024 ? 1024 : 0; // (one wave per SIMD, 1024 SIMDs: the wave 1024 further on is the next on this one's SIMD, give or take)
+    P.axis_acc = h->d_axis_acc;
+    const fused_kernel_t ak = select_axis_kernel(P);
+    if (h->hp.opt.debug) {
+        int per_cu = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(ak), 64, axis_lds_bytes(P));
+        fprintf(stderr, "[copra] (instance, axis)-per-lane solver: %d waves, %zu B LDS per wave, %d instances on spare lanes, occupancy API: %d waves per CU\n", axis_waves,
+            axis_lds_bytes(P), axis_spare, per_cu);
     }
-    if (axis_pass && !h->d_axis_acc) { // (one word per instance on spare lanes, at most one per nu waves: sized for the batch once)
-        const size_t words = (size_t)axis_waves / (size_t)P.nu + 2;
-        hipError_t e = hipMalloc((void**)&h->d_axis_acc, words * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(h->d_axis_acc, 0, words * sizeof(int));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(h->d_axis_acc);
-            h->d_axis_acc = nullptr;
-            h->ad.axis_off = true;
-            axis_pass = false;
-        }
+    quiet = h->ad.axis_quiet = adapt_axis_quiet(h, jit_launch); // (the overflow queue's self-reset while quiet is kept as it is)
+    // (quiet: this IS the first launch and the last but one -- its end is what copra_batch_last_first_tier_seconds reports)
+    HIP_TRY(launch_timed(ext_timed, h->ev0, quiet ? h->evm : nullptr, ak, (unsigned)axis_waves, 64, axis_lds_bytes(P), s, P));
+    // the second chance of what it listed (active sets beyond its lanes' six constraints): the same solver with room for sixteen, instances
+    // from the list, appending what IT cannot finish to the list the first tier takes
+    if (!quiet) {
+        FusedPlan Pl = P;
+        Pl.axis_list_in = h->d_lane_list;
+        Pl.axis_list_count = h->d_lane_count + h->lane_cur;
+        Pl.lane_list = h->d_axis_list2;
+        Pl.lane_count = h->d_axis_count2;
+        Pl.lane_zero = nullptr;
+        Pl.lane_hist = nullptr;
+        Pl.axis_pf = 0;
+        Pl.prof = nullptr;
+        HIP_TRY(launch(select_axis_list_kernel(P), adapt_second_chance_grid(h, P.nu), 64, axis_list_lds_bytes(P), s, Pl));
+        P.lane_list = h->d_axis_list2;
+        P.lane_count = h->d_axis_count2;
+    } // (else: the solver's own list and counter, as they are)
+    P.lane_from_list = 1;
+    P.lane_handover = 0; // (nothing is handed over: the tier sweeps for itself)
+    P.lane_spec = P.lds.ricC ? 1 : 0;
+    P.lane_zero = nullptr;
+    adapt_tier_cap(h, P, jit_launch, quiet);
+    return COPRA_OK;
+}
+
+// Front end of every other controller that has one: the one-instance-per-lane pass (lmpc_lane.hpp) -- every instance whose unconstrained minimiser
+// violates nothing ends in it, the first tier runs for the others only.  Leaves P as that tier takes it (on its first solve: with the layout
+// start_layout_from_histogram chose)
+static copra_status_t launch_lane_pass(copra_batch* h, FusedPlan& P, hipStream_t s, bool jit_launch, bool ext_timed)
+{
+    begin_lane_list(h, P);
+    h->ad.lane_ran = true;
+    P.lane_ws = h->d_lane_ws;
+    P.lane_ws2 = h->d_lane_ws2;
+    P.lane_bp = (int)(((size_t)P.batch + kWave - 1) / kWave * kWave) + kWave;
+    // (64 instances per wave.  Half-waves -- twice the waves for a shard of BASELINE configs[3] -- were built in round 4 and measured no
+    //  faster, profiles/r04/lane_half_waves.txt: the switch and its code are gone.)
+    const unsigned g0 = (unsigned)(((long long)P.batch + kWave - 1) / kWave);
+    // Two forms of the pass in front of the compact variant of the Riccati-factor tier (results are the same):
+    //   speculation (default): it takes the first steps of the active-set iteration itself where bounds on u_0 are the picks -- at the
+    //     headline's constraint level 96 % of the batch ends in it -- and hands NOTHING over: the few instances it leaves sweep for themselves
+    //     (the hand-over blocks of 65 536 instances were 157 MB of writes for the 2 437 that read them);
+    //   hand-over (copra_options_t::no_lane_spec): Lam^-1 | kv | norm sums of every instance for a tier that takes the factor over.
+    P.lane_spec = (P.lds.ricC && !h->hp.opt.no_lane_spec && !h->ad.lane_form_handover) ? 1 : 0; // (adapt_lane_pass chooses between them by workload)
+    // (the speculating build has no hand-over code: a code object without the plain build -- an older cache entry -- only filters)
+    const bool plain_missing = jit_launch && !h->jit_lane_plain;
+    P.lane_handover = (P.lds.ricC && !h->hp.opt.no_lane_handover && !P.lane_spec && !plain_missing) ? 1 : 0;
+    if (h->ad.lane_predict_left > 0 && h->hp.two_tier && P.lds.tri && !h->shared && !h->hp.opt.no_ladder) { // (start_layout_from_histogram)
+        P.lane_hist = h->d_lane_hist;
+        HIP_TRY(hipMemsetAsync(h->d_lane_hist, 0, kLaneHistBins * sizeof(int), s)); // (the pass ADDS to it: a re-armed prediction -- copra_batch_specialise -- must not count the earlier solve's instances again)
     }
-    if (axis_pass) {
-        lane_pass = false;
-        h->lane_cur ^= 1;
-        h->ad.axis_ran = true;
-        P.lane_list = h->d_lane_list;
-        P.lane_count = h->d_lane_count + h->lane_cur;
-        P.lane_zero = h->d_lane_count + (h->lane_cur ^ 1);
-        const unsigned ga = (unsigned)axis_waves;
-        P.axis_count2 = h->d_axis_count2;
-        P.axis_list_in = nullptr;
-        P.axis_list_count = nullptr;
-        P.axis_waves = axis_waves;
-        P.axis_pf = axis_waves > 1024 ? 1024 : 0; // (one wave per SIMD, 1024 SIMDs: the wave 1024 further on is the next on this one's SIMD, give or take)
-        P.axis_acc = h->d_axis_acc;
-        const fused_kernel_t ak = select_axis_kernel(P);
-        LDS_OPT_IN(ak, axis_lds_bytes(P));
-        if (h->hp.opt.debug) {
-            int per_cu = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(ak), 64, axis_lds_bytes(P));
-            fprintf(stderr, "[copra] (instance, axis)-per-lane solver: %u waves, %zu B LDS per wave, %d instances on spare lanes, occupancy API: %d waves per CU\n", ga,
-                axis_lds_bytes(P), axis_spare, per_cu);
-        }
-        const bool quiet = h->hp.two_tier && !jit_launch && !h->packed && h->h_lane_seen && h->lane_seen_solves >= 4 && h->lane_seen_first_max == 0
-            && h->lane_seen_max == 0; // (see below)
-        if (ext_timed) // (quiet: this IS the first launch and the last but one -- its end is what copra_batch_last_first_tier_seconds reports)
-            hipExtLaunchKernelGGL(ak, dim3(ga), dim3(64), axis_lds_bytes(P), s, h->ev0, quiet ? h->evm : nullptr, 0, P);
-        else
-            hipLaunchKernelGGL(ak, dim3(ga), dim3(64), axis_lds_bytes(P), s, P);
-        HIP_TRY(hipGetLastError());
-        // A controller whose solver has listed NOTHING in its recent solves (the headline: all 65 536 instances end in it) launches neither the
-        // second chance nor the first tier -- three launches that find nothing cost 13 us of a 100 us step --: the tier-2 launch, a grid-stride
-        // loop, walks the solver's own list from its first entry.  Should the list fill after all (a workload changes) that launch solves it,
-        // slowly, and the next solves see the length that has travelled to the host in the meantime.
-        // the second chance of what it listed (active sets beyond its lanes' six constraints): the same solver with room for sixteen, instances
-        // from the list -- a few waves that walk it, however long it is -- appending what IT cannot finish to the list the first tier takes
-        if (!quiet) {
-            FusedPlan Pl = P;
-            Pl.axis_list_in = h->d_lane_list;
-            Pl.axis_list_count = h->d_lane_count + h->lane_cur;
-            Pl.lane_list = h->d_axis_list2;
-            Pl.lane_count = h->d_axis_count2;
-            Pl.lane_zero = nullptr;
-            Pl.lane_hist = nullptr;
-            Pl.axis_pf = 0;
-            Pl.prof = nullptr;
-            const fused_kernel_t lk = select_axis_list_kernel(P);
-            const long long want = (4LL * h->lane_seen_first_max) / (64 / P.nu) + 8;
-            const unsigned gl = (unsigned)(want < 8 ? 8 : want > 512 ? 512 : want); // (one wave per CU at most: 256 CUs)
-            LDS_OPT_IN(lk, axis_list_lds_bytes(P));
-            hipLaunchKernelGGL(lk, dim3(gl), dim3(64), axis_list_lds_bytes(P), s, Pl);
-            HIP_TRY(hipGetLastError());
-        }
-        if (!quiet) {
-            P.lane_list = h->d_axis_list2;
-            P.lane_count = h->d_axis_count2;
-        } // (else: the solver's own list and counter, as they are)
-        axis_quiet = quiet;
-        h->ad.axis_quiet = quiet;
-        P.lane_from_list = 1;
-        P.lane_handover = 0; // (nothing is handed over: the tier sweeps for itself)
-        P.lane_spec = P.lds.ricC ? 1 : 0;
-        P.lane_zero = nullptr;
-        // The tier's grid: one workgroup per list entry -- and 65 536 workgroups that find none cost 15 us, a sixth of the headline's step.  The
-        // length of a solve's list travels to the host behind it (no synchronisation: the next solve takes whatever has arrived); four times the
-        // longest of the last lists + 256 workgroups are launched, entry w by workgroup w, and the second launch walks whatever lies beyond
-        // (tier-2 kernel: a grid-stride loop -- slow, and only ever busy on the solve in which a workload changes).
-        if (h->hp.two_tier && !jit_launch && !h->packed && h->h_lane_seen) {
-            long long cap = 4LL * h->lane_seen_max + 256;
-            if (h->lane_seen_solves >= 2 && cap < (long long)P.batch) P.lane_cap = (int)((cap + 7) & ~7LL);
-            P.lane_rest = quiet ? 0 : P.lane_cap > 0 ? P.lane_cap : -1;
-        }
+    if (jit_launch) {
+        FusedPlan Pl = P;
+        void* largs[] = { &Pl };
+        const hipFunction_t jl = (P.lane_spec || !h->jit_lane_plain) ? h->jit_lane : h->jit_lane_plain;
+        LDS_OPT_IN(jl, lane_lds_bytes(P));
+        HIP_TRY(hipModuleLaunchKernel(jl, g0, 1, 1, 64, 1, 1, (unsigned)lane_lds_bytes(P), s, largs, nullptr));
+    } else {
+        HIP_TRY(launch_timed(ext_timed, h->ev0, nullptr, select_lane_kernel(P), g0, 64, lane_lds_bytes(P), s, P));
     }
-    if (lane_pass && ensure_lane_buffers(h, true) != COPRA_OK) { // (no room for its workspace: the tier alone, from now on)
-        (void)hipGetLastError();
-        h->ad.lane_off = true;
-        lane_pass = false;
+    if (P.lane_hist) {
+        const copra_status_t rc = start_layout_from_histogram(h, P, s);
+        if (rc != COPRA_OK) return rc;
     }
-    if (lane_pass) {
-        h->lane_cur ^= 1;
-        h->ad.lane_ran = true;
-        P.lane_ws = h->d_lane_ws;
-        P.lane_ws2 = h->d_lane_ws2;
-        P.lane_list = h->d_lane_list;
-        P.lane_count = h->d_lane_count + h->lane_cur;
-        P.lane_zero = h->d_lane_count + (h->lane_cur ^ 1);
-        P.lane_bp = (int)(((size_t)P.batch + kWave - 1) / kWave * kWave) + kWave;
-        // (64 instances per wave.  Half-waves -- twice the waves for a shard of BASELINE configs[3] -- were built in round 4 and measured no
-        //  faster, profiles/r04/lane_half_waves.txt: the switch and its code are gone.)
-        const unsigned g0 = (unsigned)(((long long)P.batch + kWave - 1) / kWave);
-        // Two forms of the pass in front of the compact variant of the Riccati-factor tier (results are the same):
-        //   speculation (default): it takes the first steps of the active-set iteration itself where bounds on u_0 are the picks -- at the
-        //     headline's constraint level 96 % of the batch ends in it -- and hands NOTHING over: the few instances it leaves sweep for themselves
-        //     (the hand-over blocks of 65 536 instances were 157 MB of writes for the 2 437 that read them);
-        //   hand-over (copra_options_t::no_lane_spec): Lam^-1 | kv | norm sums of every instance for a tier that takes the factor over.
-        P.lane_spec = (P.lds.ricC && !h->hp.opt.no_lane_spec && !h->ad.lane_form_handover) ? 1 : 0; // (adapt_lane_pass chooses between them by workload)
-        // (the speculating build has no hand-over code: a code object without the plain build -- an older cache entry -- only filters)
-        const bool plain_missing = jit_launch && !h->jit_lane_plain;
-        P.lane_handover = (P.lds.ricC && !h->hp.opt.no_lane_handover && !P.lane_spec && !plain_missing) ? 1 : 0;
-        // first solve of a controller on a factor-only tier with a layout ladder: the pass also counts, per instance it leaves over, the
-        // rows its unconstrained minimiser violates; the layout the tier STARTS on is chosen from that histogram (below)
-        const bool predict = h->ad.lane_predict_left > 0 && h->hp.two_tier && P.lds.tri && !h->shared && !h->hp.opt.no_ladder;
-        if (predict) {
-            P.lane_hist = h->d_lane_hist;
-            HIP_TRY(hipMemsetAsync(h->d_lane_hist, 0, kLaneHistBins * sizeof(int), s)); // (the pass ADDS to it: a re-armed prediction -- copra_batch_specialise -- must not count the earlier solve's instances again)
-        }
-        if (jit_launch) {
-            FusedPlan Pl = P;
-            void* largs[] = { &Pl };
-            const hipFunction_t jl = (P.lane_spec || !h->jit_lane_plain) ? h->jit_lane : h->jit_lane_plain;
-            LDS_OPT_IN(jl, lane_lds_bytes(P));
-            HIP_TRY(hipModuleLaunchKernel(jl, g0, 1, 1, 64, 1, 1, (unsigned)lane_lds_bytes(P), s, largs, nullptr));
-        } else {
-            LDS_OPT_IN(select_lane_kernel(P), lane_lds_bytes(P));
-            if (ext_timed)
-                hipExtLaunchKernelGGL(select_lane_kernel(P), dim3(g0), dim3(64), lane_lds_bytes(P), s, h->ev0, nullptr, 0, P);
-            else
-                hipLaunchKernelGGL(select_lane_kernel(P), dim3(g0), dim3(64), lane_lds_bytes(P), s, P);
-            HIP_TRY(hipGetLastError());
-        }
-        if (P.lane_hist) {
-            // The size of an instance's final active set goes with the number of rows its unconstrained minimiser violates (~ 1.1 x,
-            // correlation 0.9 from the headline's to the tightest workload of the tests): step down the ladder until at most one instance
-            // in `share` is expected to outgrow the first tier -- BEFORE its first launch, with ONE synchronisation in the controller's
-            // life, instead of after each of the first solves (round 3: the first solve of the tight workload took 10.4 ms, the
-            // steady state 2.8 ms).  adapt_layout keeps checking the real overflow counts of the first solves behind this.
-            h->ad.lane_predict_left -= 1;
-            int hist[kLaneHistBins];
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpy(hist, h->d_lane_hist, sizeof hist, hipMemcpyDeviceToHost));
-            const long long share = h->hp.plan.lds.ric ? 64 : 8;
-            for (;;) {
-                long long over = 0;
-                for (int b = 0; b < kLaneHistBins; ++b)
-                    if (b + (b + 3) / 4 > h->hp.plan.lds.rcap) over += hist[b]; // (a little above the mean: the tail decides)
-                LdsLayout roomier {};
-                if (over * share <= (long long)P.batch || !next_tri_layout(h->hp.plan, h->hp.plan.lds, roomier)) break;
-                h->hp.plan.lds = roomier;
-                h->hp.lds_bytes = (size_t)roomier.total * sizeof(double);
-                h->lds_attr_set = false;
-                if (h->hp.opt.debug)
-                    fprintf(stderr, "[copra] %lld of %d instances are expected to outgrow the first tier: starting on %zu B, %d columns\n", over,
-                        P.batch, h->hp.lds_bytes, roomier.rcap);
-            }
-            P.lds = h->hp.plan.lds;
-            P.lane_hist = nullptr;
-        }
-        P.lane_from_list = 1;
-        P.lane_zero = nullptr;
-    }
-    if (h->hp.two_tier) HIP_TRY(begin_overflow_queue(h, s, P.lds.ric && (!jit_launch || h->jit_ric) && !h->packed, P));
+    P.lane_from_list = 1;
+    P.lane_zero = nullptr;
+    return COPRA_OK;
+}
+
+// First tier: every instance, or (P.lane_from_list) what the front end listed
+static copra_status_t launch_first_tier(copra_batch* h, const FusedPlan& P, hipStream_t s, bool jit_launch, bool ext_timed)
+{
     if (jit_launch) {
         FusedPlan Pj = P;
         void* args[] = { &Pj };
         const unsigned per = 64u / (unsigned)h->jit_lanes;
         const hipFunction_t jfn = (h->jit_ric && P.lds.q1regs == 0) ? h->jit_fused_q0 : h->jit_fused;
         LDS_OPT_IN(jfn, (size_t)per * h->hp.lds_bytes);
-        const unsigned gj = (lane_pass || axis_pass) ? (((unsigned)P.batch + 7u) & ~7u) : ((unsigned)P.batch + per - 1) / per; // (the list is dealt out in eighths)
+        const unsigned gj = P.lane_from_list ? list_grid(P.batch) : ((unsigned)P.batch + per - 1) / per;
         HIP_TRY(hipModuleLaunchKernel(jfn, gj, 1, 1, 64, 1, 1, per * (unsigned)h->hp.lds_bytes, s, args, nullptr));
-    } else if (h->packed) {
+        return COPRA_OK;
+    }
+    if (h->packed) {
         HIP_TRY(h->packed == 16 ? packed_launch_w16(P, false, h->hp.lds_bytes, s) : packed_launch_w32(P, false, h->hp.lds_bytes, s));
-    } else if (axis_quiet) {
-        // (no first tier: see above -- the tier-2 launch below walks the list)
-    } else {
-        LDS_OPT_IN(select_fused_kernel(P), h->hp.lds_bytes);
-        if (h->hp.opt.debug) {
-            int per_cu = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(select_fused_kernel(P)), 64, h->hp.lds_bytes);
-            fprintf(stderr, "[copra] fused first tier: %zu B LDS per instance, %d columns, q1regs %d, occupancy API: %d instances per CU\n",
-                h->hp.lds_bytes, P.lds.rcap, P.lds.q1regs, per_cu);
-        }
-        const unsigned g1 = P.lane_cap > 0 ? (unsigned)P.lane_cap : (lane_pass || axis_pass) ? (((unsigned)P.batch + 7u) & ~7u) : (unsigned)P.batch; // (the list is dealt out in eighths)
-        if (ext_timed) // (start | end of the first launch; with a second launch the solve ends with THAT kernel's packet)
-            hipExtLaunchKernelGGL(select_fused_kernel(P), dim3(g1), dim3(64), h->hp.lds_bytes, s,
-                (lane_pass || axis_pass) ? nullptr : h->ev0, h->hp.two_tier ? h->evm : h->ev1, 0, P);
-        else
-            hipLaunchKernelGGL(select_fused_kernel(P), dim3(g1), dim3(64), h->hp.lds_bytes, s, P);
-        HIP_TRY(hipGetLastError());
+        return COPRA_OK;
     }
-    // the lengths of this solve's lists, for the grids of the next ones: pinned host words nobody waits for -- written by the tier-2 launch itself
-    // where there is one (two 4-byte copies behind the solve are two dispatches of the runtime's copy kernel, 4 us each: 8 % of the headline's step)
-    bool seen_by_kernel = false;
-    if (axis_pass) {
-        if (!h->h_lane_seen) {
-            if (hipHostMalloc((void**)&h->h_lane_seen, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                h->h_lane_seen = nullptr;
-            } else {
-                h->h_lane_seen[0] = h->h_lane_seen[1] = h->h_lane_seen[2] = h->h_lane_seen[3] = 0;
-                if (hipHostGetDevicePointer((void**)&h->d_lane_seen, h->h_lane_seen, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    h->d_lane_seen = nullptr;
-                }
-            }
-        }
-        if (h->h_lane_seen) {
-            if (h->lane_seen_solves > 0) { // (what the LAST solve left there)
-                const int seen = h->h_lane_seen[h->lane_seen_slot], seen1 = h->h_lane_seen[2 + h->lane_seen_slot];
-                h->lane_seen_max = h->lane_seen_solves % 64 == 0 ? seen : (seen > h->lane_seen_max ? seen : h->lane_seen_max); // (the window starts again every 64 solves)
-                h->lane_seen_first_max = h->lane_seen_solves % 64 == 0 ? seen1 : (seen1 > h->lane_seen_first_max ? seen1 : h->lane_seen_first_max);
-            }
-            h->lane_seen_slot ^= 1;
-            h->lane_seen_solves += 1;
-        }
+    if (h->hp.opt.debug) {
+        int per_cu = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(select_fused_kernel(P)), 64, h->hp.lds_bytes);
+        fprintf(stderr, "[copra] fused first tier: %zu B LDS per instance, %d columns, q1regs %d, occupancy API: %d instances per CU\n",
+            h->hp.lds_bytes, P.lds.rcap, P.lds.q1regs, per_cu);
     }
-    if (h->hp.two_tier) {
-        // second tier: same kernel, full LDS layout, instances taken from the overflow queue (usually empty)
-        FusedPlan P2 = P;
-        P2.lds = h->hp.lds_full;
-        P2.from_list = 1;
-        P2.lane_from_list = 0; // (its body takes the instance it is given)
-        if (axis_pass && h->h_lane_seen && h->d_lane_seen && !jit_launch) {
-            P2.seen_out = h->d_lane_seen + h->lane_seen_slot;
-            P2.seen_src0 = axis_quiet ? h->d_lane_count + h->lane_cur : h->d_axis_count2; // (what the tier got)
-            P2.seen_src1 = h->d_lane_count + h->lane_cur; // (what the second chance got)
-            seen_by_kernel = true;
-        }
-        const unsigned g2 = (unsigned)(P.batch < 1024 ? P.batch : 1024);
-        LDS_OPT_IN(select_tier2_kernel(P2), h->hp.lds_full_bytes);
-        if (ext_timed)
-            hipExtLaunchKernelGGL(select_tier2_kernel(P2), dim3(g2), dim3(64), h->hp.lds_full_bytes, s, nullptr, h->ev1, 0, P2);
-        else
-            hipLaunchKernelGGL(select_tier2_kernel(P2), dim3(g2), dim3(64), h->hp.lds_full_bytes, s, P2);
-        HIP_TRY(hipGetLastError());
+    const unsigned g1 = P.lane_cap > 0 ? (unsigned)P.lane_cap : P.lane_from_list ? list_grid(P.batch) : (unsigned)P.batch;
+    // (start | end of the first launch; with a second launch the solve ends with THAT kernel's packet)
+    HIP_TRY(launch_timed(ext_timed, P.lane_from_list ? nullptr : h->ev0, h->hp.two_tier ? h->evm : h->ev1, select_fused_kernel(P), g1, 64, h->hp.lds_bytes, s, P));
+    return COPRA_OK;
+}
+
+// Second tier: same kernel, full LDS layout, instances taken from the overflow queue (usually empty).  carries_lengths: its first lanes also write
+// the lengths of this solve's lists to the pinned words, for the grids of the next solves (two 4-byte copies behind the solve are two dispatches
+// of the runtime's copy kernel, 4 us each: 8 % of the headline's step)
+static copra_status_t launch_second_tier(copra_batch* h, const FusedPlan& P, hipStream_t s, bool ext_timed, bool carries_lengths, bool axis_quiet)
+{
+    FusedPlan P2 = P;
+    P2.lds = h->hp.lds_full;
+    P2.from_list = 1;
+    P2.lane_from_list = 0; // (its body takes the instance it is given)
+    if (carries_lengths) {
+        P2.seen_out = h->d_lane_seen + h->ad.lane_seen_slot;
+        P2.seen_src0 = axis_quiet ? h->d_lane_count + h->lane_cur : h->d_axis_count2; // (what the tier got)
+        P2.seen_src1 = h->d_lane_count + h->lane_cur; // (what the second chance got)
     }
-    if (axis_pass && h->h_lane_seen && !seen_by_kernel) {
-        HIP_TRY(hipMemcpyAsync(h->h_lane_seen + h->lane_seen_slot, axis_quiet ? h->d_lane_count + h->lane_cur : h->d_axis_count2, sizeof(int), hipMemcpyDeviceToHost, s)); // (what the tier got)
-        HIP_TRY(hipMemcpyAsync(h->h_lane_seen + 2 + h->lane_seen_slot, h->d_lane_count + h->lane_cur, sizeof(int), hipMemcpyDeviceToHost, s)); // (what the second chance got)
+    const unsigned g2 = (unsigned)(P.batch < 1024 ? P.batch : 1024);
+    HIP_TRY(launch_timed(ext_timed, nullptr, h->ev1, select_tier2_kernel(P2), g2, 64, h->hp.lds_full_bytes, s, P2));
+    return COPRA_OK;
+}
+// ... and where no launch can carry them: two copies behind the solve
+static copra_status_t copy_list_lengths(copra_batch* h, hipStream_t s, bool axis_quiet)
+{
+    if (!h->h_lane_seen) return COPRA_OK;
+    HIP_TRY(hipMemcpyAsync(h->h_lane_seen + h->ad.lane_seen_slot, axis_quiet ? h->d_lane_count + h->lane_cur : h->d_axis_count2, sizeof(int), hipMemcpyDeviceToHost, s)); // (what the tier got)
+    HIP_TRY(hipMemcpyAsync(h->h_lane_seen + 2 + h->ad.lane_seen_slot, h->d_lane_count + h->lane_cur, sizeof(int), hipMemcpyDeviceToHost, s)); // (what the second chance got)
+    return COPRA_OK;
+}
+
+// The one-wave kernels: [front end ->] first tier [-> second tier]
+static copra_status_t solve_one_wave(copra_batch* h, FusedPlan& P, hipStream_t s, bool jit_launch, bool ext_timed)
+{
+    // which front end, if any (the solver before the pass), and its buffers: without room for them the controller does without it from now on
+    const bool axis_pass = axis_solver_wanted(h, P) && ensure_axis_buffers(h, P);
+    bool lane_pass = !axis_pass && lane_pass_wanted(h, P, jit_launch), axis_quiet = false;
+    if (lane_pass && ensure_lane_buffers(h, true) != COPRA_OK) {
+        (void)hipGetLastError();
+        h->ad.lane_off = true;
+        lane_pass = false;
     }
-    if (!ext_timed) HIP_TRY(hipEventRecord(h->ev1, s));
-    h->tier_timed = ext_timed && h->hp.two_tier;
+    copra_status_t rc = COPRA_OK;
+    if (axis_pass) rc = launch_axis_solver(h, P, s, jit_launch, ext_timed, axis_quiet);
+    if (lane_pass) rc = launch_lane_pass(h, P, s, jit_launch, ext_timed);
+    if (rc != COPRA_OK) return rc;
+    if (h->hp.two_tier) HIP_TRY(begin_overflow_queue(h, s, P.lds.ric && (!jit_launch || h->jit_ric) && !h->packed, P));
+    if (!axis_quiet) rc = launch_first_tier(h, P, s, jit_launch, ext_timed);
+    if (rc != COPRA_OK) return rc;
+    if (axis_pass) adapt_list_window(h); // (the lengths of the LAST solve's lists: here, behind this solve's choices)
+    const bool by_kernel = axis_pass && h->hp.two_tier && h->h_lane_seen && h->d_lane_seen && !jit_launch;
+    if (h->hp.two_tier) rc = launch_second_tier(h, P, s, ext_timed, by_kernel, axis_quiet);
+    if (rc == COPRA_OK && axis_pass && !by_kernel) rc = copy_list_lengths(h, s, axis_quiet);
+    if (rc != COPRA_OK) return rc;
+    if (!ext_timed) return end_of_solve(h, s);
+    h->tier_timed = h->hp.two_tier;
     h->timed = true;
     return COPRA_OK;
 }
@@ -1966,12 +1966,6 @@ copra_status_t copra_batch_solve(copra_batch_t* h, void* hip_stream)
     if (P.initial_state) return solve_initial_state(h, P, s);
     return solve_one_wave(h, P, s, jit_launch, ext_timed);
 }
-
-
-
-
-
-
 
 copra_status_t copra_batch_dump_qp(copra_batch_t* h, int instance, double* Q, double* c, double* Aeq, double* beq,
     double* Aineq, double* bineq, double* lb, double* ub)
@@ -2046,11 +2040,5 @@ copra_status_t copra_batch_dump_qp(copra_batch_t* h, int instance, double* Q, do
     (void)hipFree(db);
     return COPRA_OK;
 }
-
-
-
-
-
-
 
 } // extern "C"

@@ -60,7 +60,8 @@ constexpr size_t kSmallSlab = 1u << 20; // result slabs up to this size are fetc
 
 // What the engine has LEARNT about a controller's workload.  Every decision that makes the choice of kernels (never their results) depend on
 // earlier solves reads and writes this struct and nothing else: round-4 verdict -- four adaptive controllers spread over the handle were the
-// place where the variants interacted.  copra_hip.hip: adapt_lane_pass, adapt_layout, rechoose_layout, the pass's histogram, the shared tier's choice.
+// place where the variants interacted.  copra_hip.hip: adapt_lane_pass, adapt_axis_solver, the list-length window (adapt_list_window and what
+// reads it), adapt_layout, rechoose_layout, start_layout_from_histogram, the shared tier's choice.
 struct AdaptState {
     bool solved_once = false;
     // the layout ladder of the first tier
@@ -80,11 +81,15 @@ struct AdaptState {
     long long lane_solves = 0; // solves seen by adapt_lane_pass
     // the one-(instance, axis)-per-lane solver (lmpc_axis.hpp)
     bool axis_ran = false; // the last solve ran it
-    bool axis_quiet = false; // ... without a second chance and a first tier behind it (its recent lists were empty: solve_one_wave)
+    bool axis_quiet = false; // ... without a second chance and a first tier behind it (its recent lists were empty: adapt_axis_quiet)
     bool axis_off = false; // switched off for this controller: it leaves more than half of the batch to the tier (adapt_axis_solver), or no memory for its list
     bool axis_off_by_share = false; // ... the former: sampled again every 256 solves
     int axis_adapt_left = 2; // solves after which its share is still looked at
     long long axis_solves = 0;
+    // ... and the lengths of its recent lists, as they arrive in the handle's pinned words (h_lane_seen; adapt_list_window): the second chance's
+    // grid, the first tier's grid and whether both are launched at all follow them
+    int lane_seen_slot = 0, lane_seen_max = 0, lane_seen_first_max = 0; // (of the tier's list | of the first launch's list, which the second chance walks)
+    long long lane_seen_solves = 0;
     // shared-model tick on the records tier
     long long shared_ric_solves = 0; // solves launched on the tier's shared-model mode
     bool shared_ric_off = false; // ... which a small, constraint-heavy controller leaves after its first solve
@@ -142,7 +147,6 @@ struct copra_batch {
     // weights): the layout it had is kept here and given back once the weights are restored (weights_route, copra_hip.hip)
     bool wt_saved = false;
     LdsLayout wt_lds {};
-    size_t wt_lds_bytes = 0;
     bool wt_two_tier = false, wt_dense = false;
     int wt_packed = 0;
     // copra_batch_specialise: this controller's shape compiled into its own kernels (hipcc --genco, cached on disk)
@@ -159,9 +163,7 @@ struct copra_batch {
     int* d_lane_hist = nullptr; // histogram of the violated-row counts the pass leaves (kLaneHistBins; read once, before the first tier launch)
     double* d_lane_ws = nullptr;
     int* d_lane_seen = nullptr; // ... the same words as the device sees them
-    int* h_lane_seen = nullptr; // pinned: [2] the lengths of the last solves' first-tier lists as they arrive (solve_one_wave: the tier's grid follows them)
-    int lane_seen_slot = 0, lane_seen_max = 0, lane_seen_first_max = 0; // (of the tier's list | of the first launch's list, which the second chance walks)
-    long long lane_seen_solves = 0;
+    int* h_lane_seen = nullptr; // pinned: [2] the lengths of the last solves' first-tier lists as they arrive (ensure_axis_buffers; read by adapt_list_window into AdaptState)
     int *d_axis_list2 = nullptr, *d_axis_count2 = nullptr; // the list the second chance of the (instance, axis)-per-lane solver appends to (the first tier's, then) and its length
     int* d_axis_acc = nullptr; // lmpc_axis.hpp: the words in which the counters of instances on spare lanes meet (FusedPlan::axis_acc; zero between solves)
     double* d_lane_ws2 = nullptr; // the instance-major hand-over blocks of the pass (FusedPlan::lane_ws2)
@@ -200,6 +202,13 @@ inline bool own_weights(const copra_batch* h)
 {
     for (int t = 0; t < kMaxCosts; ++t)
         if (h->cost_w[t]) return true;
+    return false;
+}
+// ... and per-instance cost references (copra_batch_set_cost_reference): an instance's affine terms are its own
+inline bool own_references(const copra_batch* h)
+{
+    for (int t = 0; t < kMaxCosts; ++t)
+        if (h->cost_p[t]) return true;
     return false;
 }
 
