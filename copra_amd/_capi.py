@@ -56,6 +56,12 @@ class Options(C.Structure):
                 + [("debug", C.c_int), ("no_axis_solver", C.c_int)])
 
 
+class PlantStep(C.Structure):
+    """copra_plant_step_t (include/copra_hip.h): what copra_batch_advance / copra_batch_rollout apply the first control to; device pointers"""
+    _fields_ = [("struct_size", C.c_int), ("A", C.c_void_p), ("B", C.c_void_p), ("d", C.c_void_p), ("shared", C.c_int),
+                ("w", C.c_void_p), ("fallback_u", C.c_void_p), ("x_out", C.c_void_p), ("u_out", C.c_void_p), ("status_out", C.c_void_p)]
+
+
 OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_size")
 
 
@@ -345,6 +351,16 @@ def lib():
         L.copra_batch_select_solver.argtypes = [vp, C.c_int]
         L.copra_batch_solver_info.restype = C.c_int
         L.copra_batch_solver_info.argtypes = [vp]
+        L.copra_plant_step_init.restype = None
+        L.copra_plant_step_init.argtypes = [C.POINTER(PlantStep)]
+        L.copra_batch_advance.restype = C.c_int
+        L.copra_batch_advance.argtypes = [vp, C.POINTER(PlantStep), vp]
+        L.copra_batch_rollout.restype = C.c_int
+        L.copra_batch_rollout.argtypes = [vp, C.POINTER(PlantStep), C.c_int, vp, vp, vp, vp, vp]
+        L.copra_batch_x0_device.restype = vp
+        L.copra_batch_x0_device.argtypes = [vp]
+        L.copra_batch_get_x0.restype = C.c_int
+        L.copra_batch_get_x0.argtypes = [vp, vp]
         _lib = L
     return _lib
 

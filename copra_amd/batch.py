@@ -276,6 +276,102 @@ class BatchLMPC:
         """LMPC::solve for the whole batch; asynchronous on `stream` (an integer hipStream_t handle or None)"""
         _capi.check(self._lib.copra_batch_solve(self._h, C.c_void_p(stream or 0)))
 
+    # ---- the receding-horizon tick (copra_batch_advance / copra_batch_rollout): u = control().head(nu); x = plant(x, u); xInit(x) ----
+    def _device(self, a, shape, what, dtype="float64"):
+        """a device pointer for `a`, which must have `shape`: a torch CUDA tensor is used in place, anything else is copied to the device
+        (through torch); (pointer, the object that keeps the memory alive)"""
+        if a is None:
+            return None, None
+        if _is_torch(a):
+            if not (a.is_cuda and a.is_contiguous() and str(a.dtype) == "torch." + dtype):
+                raise ValueError("%s: a contiguous CUDA %s tensor is needed" % (what, dtype))
+            t = a
+        else:
+            import torch
+            t = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+        if tuple(t.shape) != tuple(shape):
+            raise _capi.CopraDomainError("%s: expected %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+        return t.data_ptr(), t
+
+    def _output(self, a, shape, what, dtype="float64"):
+        """an output of the tick: a torch CUDA tensor written in place; True: one is allocated here"""
+        if a is None or a is False:
+            return None, None
+        if a is True:
+            import torch
+            a = torch.empty(tuple(shape), dtype=getattr(torch, dtype), device="cuda")
+        elif not _is_torch(a):
+            raise ValueError("%s: outputs stay on the device -- a torch CUDA tensor (or True: allocated for you)" % what)
+        return self._device(a, shape, what, dtype)
+
+    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep):
+        st = _capi.PlantStep()
+        self._lib.copra_plant_step_init(C.byref(st))
+        b, nx, nu = self.batch, self.nx, self.nu
+        if plant is not None:
+            A, B, d = plant
+            lead = () if shared else (b,)
+            for name, arr, shape in (("A", A, lead + (nx, nx)), ("B", B, lead + (nu, nx)), ("d", d, lead + (nx,))):
+                if arr is not None and not _is_torch(arr) and name != "d":  # natural indexing -> the ABI's column-major blocks (torch
+                    arr = np.swapaxes(np.asarray(arr, dtype=np.float64), -1, -2)  # tensors are in ABI layout already, as for set_system)
+                ptr, t = self._device(arr, shape, "plant " + name)  # (some but not all of them: the library's COPRA_ERR_ARG)
+                setattr(st, name, ptr)
+                keep.append(t)
+            st.shared = 1 if shared else 0
+        st.w, t1 = self._device(disturbance, (b, nx), "disturbance")
+        st.fallback_u, t2 = self._device(fallback_control, (b, nu), "fallback_control")
+        st.x_out, xo = self._output(x_out, (b, nx), "x_out")
+        st.u_out, uo = self._output(u_out, (b, nu), "u_out")
+        st.status_out, so = self._output(status_out, (b,), "status_out", "int32")
+        keep.extend([t1, t2, xo, uo, so])
+        return st, dict(x_out=xo, u_out=uo, status_out=so)
+
+    def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None):
+        """The second half of a tick (copra_batch_advance): apply the first control of the last solve to the plant and make the result the next
+        initial state -- x+ = A x0 + B u + d (+ disturbance) where the solve succeeded (or fallback_control (batch, nu) is given); an instance
+        whose solve failed keeps its state otherwise.  Asynchronous on `stream`, behind the solve.
+        plant: (A, B, d) -- numpy in natural indexing ((batch, nx, nx), (batch, nx, nu), (batch, nx); with shared=True ONE system (nx, nx),
+        (nx, nu), (nx,)): copied to the device; torch CUDA tensors in ABI layout (as set_system): used in place; None: the controller's model.
+        x_out / u_out / status_out: torch CUDA tensors (batch, nx) / (batch, nu) / int32 (batch,) that receive copies, or True (allocated
+        here).  Returns dict(x_out, u_out, status_out) of those tensors (None where not asked for).  The state lives in a buffer of the
+        library afterwards (state(), state_ptr()): a tensor given to set_x0 is not written."""
+        keep = []
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep)
+        _capi.check(self._lib.copra_batch_advance(self._h, C.byref(st), C.c_void_p(stream or 0)))
+        self._tick_keep = keep
+        return outs
+
+    def rollout(self, ticks, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None,
+                disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None):
+        """`ticks` x (solve(), advance(...)) enqueued on `stream` by ONE call (copra_batch_rollout): the closed loop never returns to the host.
+        disturbances: (ticks, batch, nx), tick t's replaces `disturbance`; x_hist (ticks + 1, batch, nx) -- [0] is the state the first solve
+        read --, u_hist (ticks, batch, nu), status_hist int32 (ticks, batch): torch CUDA tensors written in place, or True (allocated here).
+        Returns dict(x_hist, u_hist, status_hist, x_out, u_out, status_out)."""
+        ticks = int(ticks)
+        if ticks < 0:
+            raise ValueError("rollout: ticks < 0")
+        keep = []
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep)
+        b, nx, nu = self.batch, self.nx, self.nu
+        wp, wt = self._device(disturbances, (ticks, b, nx), "disturbances")
+        xp, xt = self._output(x_hist, (ticks + 1, b, nx), "x_hist")
+        up, ut = self._output(u_hist, (ticks, b, nu), "u_hist")
+        sp, stt = self._output(status_hist, (ticks, b), "status_hist", "int32")
+        keep.extend([wt, xt, ut, stt])
+        _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, wp, xp, up, sp, C.c_void_p(stream or 0)))
+        self._tick_keep = keep
+        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt)
+
+    def state(self):
+        """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""
+        out = np.empty((self.batch, self.nx))
+        _capi.check(self._lib.copra_batch_get_x0(self._h, out.ctypes.data))
+        return out
+
+    def state_ptr(self):
+        """device pointer of the controller's current initial states (copra_batch_x0_device): after advance() a buffer of the library"""
+        return int(self._lib.copra_batch_x0_device(self._h) or 0)
+
     def synchronize(self):
         _capi.check(self._lib.copra_batch_synchronize(self._h))
 

@@ -1034,7 +1034,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 6; } // 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 7; } // 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 
 
@@ -1225,6 +1225,7 @@ void copra_batch_destroy(copra_batch_t* h)
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evm) (void)hipEventDestroy(h->evm);
+    if (h->ev_plant) (void)hipEventDestroy(h->ev_plant);
     delete h;
 }
 
@@ -1309,6 +1310,7 @@ copra_status_t copra_batch_set_shared_system(copra_batch_t* h, const double* A, 
     HIP_TRY(hipMemcpy(h->shA.data(), A, nA * sizeof(double), kind));
     HIP_TRY(hipMemcpy(h->shB.data(), B, nB * sizeof(double), kind));
     HIP_TRY(hipMemcpy(h->shd.data(), d, nd * sizeof(double), kind));
+    h->sh_dev_stale = true;
     h->shared_as_batch = false;
     see_axis_order(h, h->shA.data(), h->shB.data(), false);
     if (!h->shared && shared_model_runs_as_batch(h)) { // (a handle that is in shared-model mode stays there: its layouts have moved)
@@ -1551,6 +1553,7 @@ static void remember_outputs(copra_batch* h, const FusedPlan& P)
 {
     h->ad.last_iter = P.iter;
     h->ad.last_status = P.status;
+    h->ad.last_control = P.control;
 }
 
 // Shared-model tick: WHICH first tier -- the Riccati-factor tier in shared-model mode, or lmpc_shared.hpp.  May move the plan's layout.

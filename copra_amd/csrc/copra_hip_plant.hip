@@ -1,0 +1,178 @@
+// copra_hip_plant.hip -- the receding-horizon tick of the C ABI (include/copra_hip.h): copra_batch_advance applies the first control of the
+// last solve to a plant and makes the result the controller's next initial state (kernel: plant_step.hpp), copra_batch_rollout enqueues
+// `ticks` x (solve, advance) on one stream, copra_batch_x0_device / copra_batch_get_x0 hand the current state out.
+#include "engine.hpp"
+#include "plant_step.hpp"
+
+#include <cstring>
+
+namespace {
+
+constexpr size_t kPlantLdsTarget = 24 * 1024; // a group's image: small enough for several workgroups per CU
+constexpr size_t kPlantLdsMax = 160 * 1024; // one instance's image at most (the CU's LDS)
+constexpr int kPlantGroupMax = 32;
+
+// the caller's struct as THIS library knows it: fields beyond the caller's struct_size keep their defaults (all zero)
+copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_t& out, const char* who)
+{
+    std::memset(&out, 0, sizeof out);
+    out.struct_size = (int)sizeof out;
+    if (!step) return COPRA_OK;
+    if (step->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_plant_step_t::struct_size is not set (copra_plant_step_init)");
+    const size_t known = (size_t)step->struct_size < sizeof out ? (size_t)step->struct_size : sizeof out;
+    std::memcpy(&out, step, known);
+    out.struct_size = (int)sizeof out;
+    const int given = (out.A != nullptr) + (out.B != nullptr) + (out.d != nullptr);
+    if (given != 0 && given != 3) return fail(COPRA_ERR_ARG, std::string(who) + ": a plant needs all of A, B and d (or none of them: the controller's model)");
+    return COPRA_OK;
+}
+
+// what can be said before any solve: the handle takes part in closed-loop ticks at all
+copra_status_t check_handle(const copra_batch* h, const char* who)
+{
+    if (h->hp.plan.initial_state)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": the initial state of an InitialStateLMPC controller is a decision variable, not the plant's state");
+    return COPRA_OK;
+}
+
+// the shared model of copra_batch_set_shared_system on the device (the solve keeps it on the host and in its prepared model)
+copra_status_t shared_model_on_device(copra_batch* h)
+{
+    if (h->d_shA && !h->sh_dev_stale) return COPRA_OK;
+    const size_t nA = h->shA.size(), nB = h->shB.size(), nd = h->shd.size();
+    if (!h->d_shA) {
+        HIP_TRY(hipMalloc((void**)&h->d_shA, nA * sizeof(double)));
+        HIP_TRY(hipMalloc((void**)&h->d_shB, nB * sizeof(double)));
+        HIP_TRY(hipMalloc((void**)&h->d_shd, nd * sizeof(double)));
+    }
+    HIP_TRY(hipStreamSynchronize(h->last_stream)); // (an advance that still reads the old model: once per model)
+    HIP_TRY(hipMemcpy(h->d_shA, h->shA.data(), nA * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_shB, h->shB.data(), nB * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_shd, h->shd.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+    h->sh_dev_stale = false;
+    return COPRA_OK;
+}
+
+// one plant step behind the last launched solve; `st` has been through read_step
+copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const double* w, double* x_out, double* u_out, int* status_out, hipStream_t s,
+    const char* who)
+{
+    const FusedPlan& HP = h->hp.plan;
+    if (!h->ad.solved_once) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no solve has been launched (copra_batch_solve)");
+    if (HP.batch == 0) return COPRA_OK;
+    if (!h->ad.last_status || !h->ad.last_control)
+        return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no solve has been launched into the current result buffers (copra_batch_set_outputs, then copra_batch_solve)");
+    if (!h->x0) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no initial states set");
+    PlantStepArgs P {};
+    P.batch = HP.batch;
+    P.nx = HP.nx;
+    P.nu = HP.nu;
+    P.ctrl_stride = HP.n;
+    if (st.A) {
+        P.A = st.A, P.B = st.B, P.d = st.d;
+        P.shared = st.shared != 0;
+    } else if (h->shared) { // the model the last solve read: ONE system ...
+        const copra_status_t rc = shared_model_on_device(h);
+        if (rc != COPRA_OK) return rc;
+        P.A = h->d_shA, P.B = h->d_shB, P.d = h->d_shd;
+        P.shared = 1;
+    } else { // ... or every instance's own (a shared model written out per instance included)
+        if (!h->A || !h->B || !h->d) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no preview system set (copra_batch_set_system)");
+        P.A = h->A, P.B = h->B, P.d = h->d;
+    }
+    const size_t nd = (size_t)HP.batch * HP.nx;
+    if (!h->own_x0) HIP_TRY(hipMalloc((void**)&h->own_x0, nd * sizeof(double)));
+    P.x0 = h->x0; // (a caller's device buffer is read this once more, never written)
+    P.x0_next = h->own_x0;
+    P.w = w;
+    P.fallback_u = st.fallback_u;
+    P.status = h->ad.last_status;
+    P.control = h->ad.last_control;
+    P.x_out = x_out;
+    P.u_out = u_out;
+    P.status_out = status_out;
+    // instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes
+    const size_t one = (size_t)plant_lds(P.nx, P.nu, 1, 0, 1).total * sizeof(double);
+    if (one > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's plant does not fit the LDS (xDim beyond about 130)");
+    int group = (int)(kPlantLdsTarget / one);
+    group = group > kPlantGroupMax ? kPlantGroupMax : group < 1 ? 1 : group;
+    if (group > 1) group &= ~1;
+    P.group = group;
+    P.vec2 = plant_vec2_ok(P);
+    const size_t lds_bytes = (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr).total * sizeof(double);
+    if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_plant_step_kernel, lds_bytes);
+    if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
+        if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
+    }
+    const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
+    hipLaunchKernelGGL(copra_plant_step_kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
+    HIP_TRY(hipGetLastError());
+    h->x0 = h->own_x0;
+    h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
+    return COPRA_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void copra_plant_step_init(copra_plant_step_t* step)
+{
+    if (!step) return;
+    std::memset(step, 0, sizeof *step);
+    step->struct_size = (int)sizeof *step;
+}
+
+copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* step, void* hip_stream)
+{
+    if (!h) return fail(COPRA_ERR_ARG, "copra_batch_advance: null handle");
+    copra_plant_step_t st;
+    copra_status_t rc = read_step(step, st, "copra_batch_advance");
+    if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_advance");
+    if (rc != COPRA_OK) return rc;
+    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, (hipStream_t)hip_stream, "copra_batch_advance");
+}
+
+copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* step, int ticks, const double* w_seq, double* x_hist, double* u_hist,
+    int* status_hist, void* hip_stream)
+{
+    if (!h) return fail(COPRA_ERR_ARG, "copra_batch_rollout: null handle");
+    if (ticks < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative number of ticks");
+    copra_plant_step_t st;
+    copra_status_t rc = read_step(step, st, "copra_batch_rollout");
+    if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_rollout");
+    if (rc != COPRA_OK) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const FusedPlan& HP = h->hp.plan;
+    const size_t nd = (size_t)HP.batch * HP.nx, nc = (size_t)HP.batch * HP.nu, nb = (size_t)HP.batch;
+    if (x_hist && nd) { // the state the first solve reads
+        if (!h->x0) return fail(COPRA_ERR_RUNTIME, "copra_batch_rollout: no initial states set");
+        HIP_TRY(hipMemcpyAsync(x_hist, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    for (int t = 0; t < ticks; ++t) {
+        rc = copra_batch_solve(h, hip_stream);
+        if (rc != COPRA_OK) return rc;
+        rc = advance(h, st, w_seq ? w_seq + (size_t)t * nd : st.w, x_hist ? x_hist + (size_t)(t + 1) * nd : st.x_out, u_hist ? u_hist + (size_t)t * nc : st.u_out,
+            status_hist ? status_hist + (size_t)t * nb : st.status_out, s, "copra_batch_rollout");
+        if (rc != COPRA_OK) return rc;
+    }
+    return COPRA_OK;
+}
+
+const double* copra_batch_x0_device(const copra_batch_t* h)
+{
+    return h ? h->x0 : nullptr;
+}
+
+copra_status_t copra_batch_get_x0(copra_batch_t* h, double* x0)
+{
+    if (!h || !x0) return fail(COPRA_ERR_ARG, "copra_batch_get_x0: null argument");
+    if (!h->x0) return fail(COPRA_ERR_RUNTIME, "copra_batch_get_x0: no initial states set");
+    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    HIP_TRY(hipMemcpy(x0, h->x0, (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double), hipMemcpyDeviceToHost));
+    return COPRA_OK;
+}
+
+} // extern "C"

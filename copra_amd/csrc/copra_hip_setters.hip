@@ -432,6 +432,7 @@ copra_status_t copra_batch_set_outputs(copra_batch_t* h, double* control, double
         h->ad.last_iter = nullptr;
         h->ad.last_status = nullptr;
     }
+    if (control != h->ext_control) h->ad.last_control = nullptr;
     h->ext_control = control;
     h->ext_traj = trajectory;
     h->ext_status = status;

@@ -7,6 +7,7 @@
 //   copra_hip_jit.hip      copra_batch_specialise, copra_qp_dense_specialise (hipcc --genco at run time)
 //   copra_hip_qp.hip       plug-in point 1: copra_qp_solve_dense_batch and its kernels
 //   copra_hip_packed16/32.hip  the one-wave bodies with 16 / 32 lanes per instance
+//   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -97,6 +98,7 @@ struct AdaptState {
     // the NEXT solve -- with rotating result slabs an uninitialised one)
     const int* last_iter = nullptr;
     const int* last_status = nullptr;
+    const double* last_control = nullptr; // ... and its controls: what copra_batch_advance applies to the plant (copra_hip_plant.hip)
 };
 
 struct copra_batch {
@@ -138,6 +140,7 @@ struct copra_batch {
     int model_rtot = 0; // columns of C2 / K2 as prepared
     double *d_shA = nullptr, *d_shB = nullptr, *d_shd = nullptr, *d_model = nullptr;
     std::vector<double> shA, shB, shd;
+    bool sh_dev_stale = true; // d_shA / d_shB / d_shd (the shared model as a plant, copra_hip_plant.hip) are older than shA / shB / shd
     double *d_row_f_inst = nullptr, *d_lb_inst = nullptr, *d_ub_inst = nullptr; // per-instance rhs / control bounds
     double* d_cost_p[kMaxCosts] = {}; // per-instance cost references (owned copies) ...
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
@@ -190,6 +193,7 @@ struct copra_batch {
     long long* d_prof = nullptr; // optional per-instance phase cycle counts (copra_batch_enable_phase_profile)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr; // start | end of the solve | end of its first launch (packet-borne timing)
     bool tier_timed = false; // evm was written by the last solve
+    hipEvent_t ev_plant = nullptr; // orders copra_batch_advance on another stream behind the solve
     hipStream_t last_stream = nullptr;
     bool timed = false;
     bool lds_attr_set = false;

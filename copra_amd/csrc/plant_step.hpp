@@ -1,0 +1,173 @@
+// plant_step.hpp -- the second half of a receding-horizon tick, on the device: apply the first control of the last solve to a plant and make the
+// result the next initial state (copra_batch_advance / copra_batch_rollout, copra_hip_plant.hip).  Replaces the reference's
+//   u = lmpc.control().head(nu);  x = plant(x, u);  ps->xInit(x);            (include/LMPC.h:108, include/PreviewSystem.h:52)
+// for every instance b of the batch:
+//   ok = status[b] == COPRA_QP_OK;   u = ok ? control[b][0 .. nu) : fallback_u ? fallback_u[b] : none
+//   x+ = (ok || fallback_u) ? Ap[b] x0[b] + Bp[b] u + dp[b] (+ w[b]) : x0[b]            (no fallback: the state is HELD, bit for bit)
+// A failed instance's control holds NaN: the status is looked at FIRST, the control of a failed instance is never loaded.
+//
+// A streaming kernel (about 600 B read, 50-130 B written per instance at xDim 6, uDim 3).  One workgroup takes `group` consecutive instances:
+// their A, B, d, x0, w blocks are ONE contiguous range per array, copied into LDS with wide coalesced loads (16 B per lane where the
+// pointers allow it); then one thread per (instance, row) forms its sum from LDS and the new states leave as one contiguous range again.
+// No lane walks a column with stride nx in global memory; only `control` is read with its stride nu N (its first nu entries).  No scratch, no
+// atomics, nothing depends on the grid beyond the bounds of the last group.  In place (x0_next == x0) is the normal case: an instance belongs
+// to one workgroup, whose old states are all in LDS (phase 1) before the barrier that precedes the first store (phase 2).
+//
+// The two phases are COPRA_DEV functions of (workgroup, thread) that also compile on the host: tests/emu/emu_plant.cpp walks them thread by
+// thread with a host buffer in the place of LDS.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+#ifndef COPRA_DEV
+#if defined(__HIPCC__)
+#define COPRA_DEV __device__ __forceinline__
+#else
+#define COPRA_DEV inline
+#endif
+#endif
+
+#if defined(__HIPCC__)
+#define COPRA_PLANT_HD __host__ __device__ inline // (the launch sizes the LDS image with the function the kernel lays it out with)
+#else
+#define COPRA_PLANT_HD inline
+#endif
+
+namespace copra_hip {
+
+struct PlantStepArgs {
+    int batch, nx, nu;
+    int ctrl_stride; // doubles between two instances' controls: nu N
+    int group; // instances per workgroup (even wherever vec2 is set)
+    int shared; // A, B, d hold ONE system for the batch
+    int vec2; // every pointer below is 16-byte aligned and every group's range starts on 16 bytes: copy two doubles per lane and load
+    const double *A, *B, *d; // the plant, layout of copra_batch_set_system
+    const double* x0; // [batch][nx]
+    const double* w; // [batch][nx] or null
+    const double* fallback_u; // [batch][nu] or null
+    const int* status; // [batch], of the last launched solve
+    const double* control; // [batch][ctrl_stride], of the last launched solve
+    double* x0_next; // [batch][nx]; may be x0
+    double *x_out, *u_out; // optional copies
+    int* status_out;
+};
+
+struct alignas(16) PlantPair {
+    double a, b;
+};
+
+// (host) whether a launch may copy two doubles per lane: an even group -- every group's range then starts on 16 bytes -- and aligned arrays
+inline bool plant_vec2_ok(const PlantStepArgs& P)
+{
+    const auto ok = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    return P.group % 2 == 0 && ok(P.A) && ok(P.B) && ok(P.d) && ok(P.x0) && ok(P.w);
+}
+
+COPRA_PLANT_HD int plant_even(int v) { return (v + 1) & ~1; }
+
+// LDS image of one workgroup, in doubles: A | B | d | x0 | w | u | status (ints); every part starts on 16 bytes
+struct PlantLds {
+    int oA, oB, od, ox, ow, ou, ost, total;
+};
+COPRA_PLANT_HD PlantLds plant_lds(int nx, int nu, int group, int shared, int has_w)
+{
+    const int gs = shared ? 1 : group;
+    PlantLds L;
+    L.oA = 0;
+    L.oB = L.oA + plant_even(gs * nx * nx);
+    L.od = L.oB + plant_even(gs * nx * nu);
+    L.ox = L.od + plant_even(gs * nx);
+    L.ow = L.ox + plant_even(group * nx);
+    L.ou = L.ow + (has_w ? plant_even(group * nx) : 0);
+    L.ost = L.ou + plant_even(group * nu);
+    L.total = L.ost + plant_even((group + 1) / 2);
+    return L;
+}
+
+// dst[0 .. count) = src[0 .. count), thread `tid` of `T`: consecutive lanes, consecutive addresses
+COPRA_DEV void plant_copy(double* dst, const double* src, int count, int tid, int T, int vec2)
+{
+    if (vec2) {
+        const int pairs = count >> 1;
+        const PlantPair* s2 = reinterpret_cast<const PlantPair*>(src);
+        PlantPair* d2 = reinterpret_cast<PlantPair*>(dst);
+        for (int e = tid; e < pairs; e += T) d2[e] = s2[e];
+        if ((count & 1) && tid == 0) dst[count - 1] = src[count - 1];
+    } else {
+        for (int e = tid; e < count; e += T) dst[e] = src[e];
+    }
+}
+
+// row r of  A x + B u + d (+ w)  for one instance: A [nx x nx], B [nx x nu] column-major
+COPRA_DEV double plant_row(int nx, int nu, int r, const double* A, const double* B, const double* d, const double* w, const double* x, const double* u)
+{
+    double acc = d[r];
+    for (int j = 0; j < nx; ++j) acc += A[r + nx * j] * x[j];
+    for (int c = 0; c < nu; ++c) acc += B[r + nx * c] * u[c];
+    if (w) acc += w[r];
+    return acc;
+}
+
+// phase 1: everything workgroup `wg` reads, into its image `lds`
+COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+{
+    const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr);
+    const size_t s0 = P.shared ? 0 : (size_t)b0;
+    const int scnt = P.shared ? 1 : cnt;
+    plant_copy(lds + L.oA, P.A + s0 * nx * nx, scnt * nx * nx, tid, T, P.vec2);
+    plant_copy(lds + L.oB, P.B + s0 * nx * nu, scnt * nx * nu, tid, T, P.vec2);
+    plant_copy(lds + L.od, P.d + s0 * nx, scnt * nx, tid, T, P.vec2);
+    plant_copy(lds + L.ox, P.x0 + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+    if (P.w) plant_copy(lds + L.ow, P.w + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+    int* st = reinterpret_cast<int*>(lds + L.ost);
+    for (int i = tid; i < cnt; i += T) st[i] = P.status[b0 + i];
+    for (int e = tid; e < cnt * nu; e += T) { // the control that is applied: the status decides BEFORE anything of `control` is touched
+        const int i = e / nu, c = e - i * nu;
+        const size_t b = (size_t)b0 + i;
+        double u = NAN;
+        if (P.status[b] == 0) u = P.control[b * P.ctrl_stride + c];
+        else if (P.fallback_u) u = P.fallback_u[b * nu + c];
+        lds[L.ou + e] = u;
+    }
+}
+
+// phase 2 (behind a barrier): the new states and the optional copies
+COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
+{
+    const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr);
+    const int* st = reinterpret_cast<const int*>(lds + L.ost);
+    for (int e = tid; e < cnt * nx; e += T) {
+        const int i = e / nx, r = e - i * nx, is = P.shared ? 0 : i;
+        double xn = lds[L.ox + e]; // held
+        if (st[i] == 0 || P.fallback_u)
+            xn = plant_row(nx, nu, r, lds + L.oA + is * nx * nx, lds + L.oB + is * nx * nu, lds + L.od + is * nx, P.w ? lds + L.ow + i * nx : nullptr,
+                lds + L.ox + i * nx, lds + L.ou + i * nu);
+        const size_t o = (size_t)b0 * nx + e;
+        P.x0_next[o] = xn;
+        if (P.x_out) P.x_out[o] = xn;
+    }
+    if (P.u_out)
+        for (int e = tid; e < cnt * nu; e += T) P.u_out[(size_t)b0 * nu + e] = lds[L.ou + e];
+    if (P.status_out)
+        for (int i = tid; i < cnt; i += T) P.status_out[b0 + i] = st[i];
+}
+
+#if defined(__HIPCC__)
+constexpr int kPlantThreads = 256;
+__global__ __launch_bounds__(kPlantThreads) void copra_plant_step_kernel(const PlantStepArgs P)
+{
+    extern __shared__ __align__(16) double plant_image[];
+    plant_stage(P, (int)blockIdx.x, (int)threadIdx.x, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_apply(P, (int)blockIdx.x, (int)threadIdx.x, kPlantThreads, plant_image);
+}
+#endif
+
+} // namespace copra_hip

@@ -343,6 +343,45 @@ const int* copra_batch_status_device(const copra_batch_t* h);
 const int* copra_batch_iter_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_results(copra_batch_t* h, double* control, double* trajectory, int* status, int* iter);
 
+/* ---- the receding-horizon tick.  The reference's closed loop is  ps->xInit(x); lmpc.solve(); u = lmpc.control().head(nu); x = plant(x, u)
+ *      (include/PreviewSystem.h:52, include/LMPC.h:108): copra_batch_advance replaces its last two steps and the xInit of the next tick for
+ *      every instance, on the device.  With status / control the buffers the LAST LAUNCHED solve wrote (copra_batch_set_outputs honoured):
+ *        ok = status[b] == COPRA_QP_OK;    u = ok ? control[b][0 .. nu) : fallback_u ? fallback_u[b] : none
+ *        x+ = (ok || fallback_u) ? A[b] x0[b] + B[b] u + d[b] (+ w[b]) : x0[b]       -- no fallback: a failed instance KEEPS its state, bit for bit
+ *        x0[b] <- x+;   x_out[b] = x+;   u_out[b] = u (NaN where the state was kept);   status_out[b] = status[b]
+ *      The NaN a failed instance holds in `control` never reaches a state: the status is looked at first.  x+ always comes from the plant,
+ *      never from trajectory[:, nx .. 2 nx): one rule whether or not plant and model differ.
+ *      copra_plant_step_t: A, B, d are the plant -- device arrays in the layout of copra_batch_set_system, or ONE system for the batch
+ *      (`shared`), or all NULL: the model the last solve read (per instance, or the one of copra_batch_set_shared_system).  Every pointer is
+ *      a device pointer, used in place.  struct_size as in copra_options_t (set by copra_plant_step_init; fields are only ever appended).
+ *      copra_batch_advance is asynchronous on `hip_stream` and ordered behind the solve.  The new state goes into a buffer of the LIBRARY,
+ *      which becomes the controller's x0 (copra_batch_x0_device; copra_batch_get_x0 waits and copies it to the host): a device buffer the
+ *      caller handed to copra_batch_set_x0 / copra_batch_set_system is read once more and never written.  A later copra_batch_set_x0 /
+ *      copra_batch_set_system replaces the state as before.  `step` NULL: the model as plant, no disturbance, failed instances keep their state.
+ *      copra_batch_rollout: `ticks` x (copra_batch_solve, copra_batch_advance) enqueued on one stream -- a Monte-Carlo closed-loop run in one
+ *      call, no host synchronisation of its own (what copra_batch_solve does on a controller's first solves stays).  x_hist[0] is the state
+ *      the first solve read, x_hist[t + 1] / u_hist[t] / status_hist[t] are x_out / u_out / status_out of tick t (a NULL history: the step's
+ *      own pointer, overwritten every tick); w_seq[t] replaces step->w.  Device pointers.
+ *      COPRA_ERR_RUNTIME: copra_batch_advance before any solve into the current result buffers; COPRA_ERR_UNSUPPORTED: an InitialStateLMPC
+ *      controller (its x0 is a decision variable), a plant too wide for the LDS (xDim beyond about 130); COPRA_ERR_ARG: some but not all of
+ *      A, B, d, ticks < 0, a NULL handle. ---- */
+typedef struct {
+    int struct_size; /* sizeof(copra_plant_step_t): append-only, as copra_options_t */
+    const double *A, *B, *d; /* plant, device pointers; all NULL: the controller's model */
+    int shared; /* A, B, d hold ONE system for the whole batch */
+    const double* w; /* additive disturbance [batch][nx], device; NULL: none */
+    const double* fallback_u; /* [batch][nu] applied where the solve failed; NULL: such an instance keeps its state */
+    double* x_out; /* optional copies for the caller: [batch][nx], [batch][nu], [batch] */
+    double* u_out;
+    int* status_out;
+} copra_plant_step_t;
+void copra_plant_step_init(copra_plant_step_t* step);
+copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* step, void* hip_stream);
+copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* step, int ticks, const double* w_seq, double* x_hist,
+    double* u_hist, int* status_hist, void* hip_stream);
+const double* copra_batch_x0_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_x0(copra_batch_t* h, double* x0);
+
 /* ---- parity hooks: the dense QP of one instance as LMPC exposes it (include/LMPC.h:112-127: Q c Aineq bineq Aeq
  *      beq lb ub), rebuilt ON THE DEVICE by the same condense code the solver runs.  Any pointer may be NULL.
  *      Q [n x n], c [n], Aeq [neq x n], beq [neq], Aineq [nineq x n], bineq [nineq], lb [n], ub [n]. ---- */
