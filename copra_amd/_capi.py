@@ -361,6 +361,12 @@ def lib():
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int
         L.copra_batch_get_x0.argtypes = [vp, vp]
+        L.copra_batch_set_reference_schedule.restype = C.c_int
+        L.copra_batch_set_reference_schedule.argtypes = [vp, C.c_int, vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.copra_batch_schedule_seek.restype = C.c_int
+        L.copra_batch_schedule_seek.argtypes = [vp, C.c_longlong]
+        L.copra_batch_schedule_tick.restype = C.c_longlong
+        L.copra_batch_schedule_tick.argtypes = [vp]
         _lib = L
     return _lib
 

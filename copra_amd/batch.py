@@ -41,6 +41,7 @@ class BatchLMPC:
         self._keep = []
         self._ref_keep = {}  # torch tensors used in place as per-instance cost references, by cost index
         self._w_keep = {}  # ... and as per-instance cost weights
+        self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
         self._cost_rows = [None if cc[i].kind == _capi.COST_KINDS["dense"] else int(cc[i].rows) for i in range(len(costs))]
@@ -171,6 +172,7 @@ class BatchLMPC:
         place); p of shape (rows,): ONE new reference for every instance (copra_batch_set_cost_reference_all: copied); None
         restores the controller-wide reference given at creation"""
         self._ref_keep.pop(int(cost_index), None)  # one slot per cost: the previous tensor is released
+        self._sched_keep.pop(int(cost_index), None)  # (the library ends the cost's schedule)
         if p is not None and getattr(p, "ndim", np.ndim(p)) == 1:
             if _is_torch(p):
                 assert p.is_cuda and p.is_contiguous() and str(p.dtype) == "torch.float64"
@@ -188,6 +190,44 @@ class BatchLMPC:
             pb = np.ascontiguousarray(p, dtype=np.float64)
             assert pb.shape[0] == self.batch
             _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), pb.ctypes.data, 0))
+
+    def set_reference_schedule(self, cost_index, schedule, rows_per_step, offset=0):
+        """The reference of cost `cost_index` follows a signal (copra_batch_set_reference_schedule): schedule of shape (steps, r) -- one for the
+        batch -- or (batch, steps, r) -- one per instance --, r = rows_per_step; numpy: copied; a torch CUDA float64 tensor: used in place and
+        kept alive, never written.  With S = rows of the cost / r the solve at tick tau reads the blocks min(tau + offset + s, steps - 1),
+        s = 0 .. S-1: a reference trajectory has r = nx and S = N + 1, a moving goal S = 1, a TargetCost offset = N.  advance() / rollout()
+        move the window by one step per tick, on the device (schedule_tick(), schedule_seek()).  None ends the schedule and keeps the last
+        window; set_cost_reference on that cost ends it too."""
+        k, r = int(cost_index), int(rows_per_step)
+        if schedule is None:
+            _capi.check(self._lib.copra_batch_set_reference_schedule(self._h, k, None, 0, 0, 0, 0, 0))
+            self._sched_keep.pop(k, None)
+            return
+        torch_in = _is_torch(schedule)
+        if torch_in:
+            if not (schedule.is_cuda and schedule.is_contiguous() and str(schedule.dtype) == "torch.float64"):
+                raise ValueError("set_reference_schedule: a contiguous CUDA float64 tensor is needed")
+            sb, ptr = schedule, schedule.data_ptr()
+        else:
+            sb = np.ascontiguousarray(schedule, dtype=np.float64)
+            ptr = sb.ctypes.data
+        shape = tuple(sb.shape)
+        if len(shape) not in (2, 3) or shape[-1] != r or (len(shape) == 3 and shape[0] != self.batch):
+            raise _capi.CopraDomainError("set_reference_schedule: expected (steps, %d) or (%d, steps, %d), got %s" % (r, self.batch, r, shape))
+        _capi.check(self._lib.copra_batch_set_reference_schedule(self._h, k, ptr, shape[-2], r, int(offset), 1 if len(shape) == 3 else 0,
+                                                                 1 if torch_in else 0))
+        self._ref_keep.pop(k, None)  # (the cost's reference is the library's window now)
+        self._sched_keep.pop(k, None)
+        if torch_in:
+            self._sched_keep[k] = schedule
+
+    def schedule_seek(self, tick):
+        """the controller's tick counter <- tick, the windows of all scheduled costs rewritten (copra_batch_schedule_seek; asynchronous)"""
+        _capi.check(self._lib.copra_batch_schedule_seek(self._h, int(tick)))
+
+    def schedule_tick(self):
+        """the controller's tick counter: the advances so far, or what schedule_seek set (copra_batch_schedule_tick)"""
+        return int(self._lib.copra_batch_schedule_tick(self._h))
 
     def set_cost_weights(self, cost_index, w):
         """per-instance weights of cost `cost_index` (copra_batch_set_cost_weights): w of shape (batch, rows) with the rows of that

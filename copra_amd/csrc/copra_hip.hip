@@ -1034,7 +1034,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 7; } // 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 8; } // 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 
 
@@ -1198,7 +1198,7 @@ void copra_batch_destroy(copra_batch_t* h)
     (void)hipFree(h->own_x0lb);
     (void)hipFree(h->own_x0ub);
     if (h->jit_module) (void)hipModuleUnload(h->jit_module);
-    for (int k = 0; k < kMaxCosts; ++k) (void)hipFree(h->d_cost_p[k]), (void)hipFree(h->d_cost_w[k]);
+    for (int k = 0; k < kMaxCosts; ++k) (void)hipFree(h->d_cost_p[k]), (void)hipFree(h->d_cost_w[k]), (void)hipFree(h->ref_sched[k].own);
     (void)hipFree(h->d_row_f_inst);
     (void)hipFree(h->d_lb_inst);
     (void)hipFree(h->d_ub_inst);

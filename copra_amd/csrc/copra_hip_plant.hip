@@ -1,8 +1,10 @@
 // copra_hip_plant.hip -- the receding-horizon tick of the C ABI (include/copra_hip.h): copra_batch_advance applies the first control of the
 // last solve to a plant and makes the result the controller's next initial state (kernel: plant_step.hpp), copra_batch_rollout enqueues
-// `ticks` x (solve, advance) on one stream, copra_batch_x0_device / copra_batch_get_x0 hand the current state out.
+// `ticks` x (solve, advance) on one stream, copra_batch_x0_device / copra_batch_get_x0 hand the current state out.  A cost whose reference
+// follows a schedule (copra_batch_set_reference_schedule) gets the window of the new tick behind every plant step (kernel: ref_window.hpp).
 #include "engine.hpp"
 #include "plant_step.hpp"
+#include "ref_window.hpp"
 
 #include <cstring>
 
@@ -50,6 +52,32 @@ copra_status_t shared_model_on_device(copra_batch* h)
     HIP_TRY(hipMemcpy(h->d_shB, h->shB.data(), nB * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->d_shd, h->shd.data(), nd * sizeof(double), hipMemcpyHostToDevice));
     h->sh_dev_stale = false;
+    return COPRA_OK;
+}
+
+// the windows of every scheduled cost at the controller's tick counter, one launch on `s`: no synchronisation, no allocation
+copra_status_t write_windows(copra_batch* h, hipStream_t s, const char* who)
+{
+    RefWindowArgs W {};
+    W.batch = h->hp.plan.batch;
+    W.group = kRefWindowGroup;
+    for (int t = 0; t < kMaxCosts; ++t) {
+        const RefSchedule& rs = h->ref_sched[t];
+        if (!rs.sched) continue;
+        if (W.ncost == kRefWindowMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": more scheduled costs than one launch serves");
+        RefWindowCost& c = W.c[W.ncost++];
+        c.sched = rs.sched;
+        c.out = h->d_cost_p[t];
+        c.steps = rs.steps;
+        c.first = h->sched_tick + rs.offset;
+        c.r = rs.r, c.S = rs.S;
+        c.per_instance = rs.per_instance;
+    }
+    if (W.ncost == 0 || W.batch <= 0) return COPRA_OK;
+    ref_window_prepare(W, kRefWindowThreads);
+    const unsigned grid = (unsigned)((W.batch + W.group - 1) / W.group);
+    hipLaunchKernelGGL(copra_ref_window_kernel, dim3(grid), dim3(kRefWindowThreads), 0, s, W);
+    HIP_TRY(hipGetLastError());
     return COPRA_OK;
 }
 
@@ -111,7 +139,8 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
     HIP_TRY(hipGetLastError());
     h->x0 = h->own_x0;
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
-    return COPRA_OK;
+    h->sched_tick += 1; // time moves on for every instance, a failed one included: the next solve reads the next window
+    return write_windows(h, s, who);
 }
 
 } // namespace
@@ -159,6 +188,60 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
         if (rc != COPRA_OK) return rc;
     }
     return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_index, const double* sched, long long steps, int r, int offset, int per_instance,
+    int on_device)
+{
+    const char* const who = "copra_batch_set_reference_schedule";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const FusedPlan& P = h->hp.plan;
+    if (cost_index < 0 || cost_index >= (int)h->hp.cost_slot.size()) return fail(COPRA_ERR_ARG, std::string(who) + ": no such cost");
+    const int t = h->hp.cost_slot[(size_t)cost_index]; // (dense costs are not among the kernel-evaluated terms)
+    if (t < 0) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": a dense (host-evaluated) cost has no reference p");
+    RefSchedule& rs = h->ref_sched[t];
+    if (!sched) { // the schedule ends, the window stays (cost_p keeps pointing at it)
+        rs.sched = nullptr;
+        return COPRA_OK;
+    }
+    if (steps < 1 || offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
+    const CostTerm& ct = P.cost[t];
+    if (r < 1 || ct.prows % r != 0) return fail(COPRA_ERR_DOMAIN, std::string(who) + ": r does not divide the rows of the cost");
+    if (ct.pstride && r != ct.pstride)
+        return fail(COPRA_ERR_DOMAIN, std::string(who) + ": the controller evaluates this full-size cost step by step: r must be the rows of one step");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    if (!h->d_cost_p[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_p[t], b * ct.prows * sizeof(double)));
+    if (!on_device) { // the library's copy: a window launch that still reads the old one first
+        const size_t count = (per_instance ? b : 1) * (size_t)steps * r;
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        if (rs.own_doubles < count) {
+            (void)hipFree(rs.own);
+            rs.own = nullptr, rs.own_doubles = 0, rs.sched = nullptr;
+            HIP_TRY(hipMalloc((void**)&rs.own, count * sizeof(double)));
+            rs.own_doubles = count;
+        }
+        HIP_TRY(hipMemcpy(rs.own, sched, count * sizeof(double), hipMemcpyHostToDevice));
+        sched = rs.own;
+    }
+    rs.sched = sched;
+    rs.steps = steps;
+    rs.r = r, rs.S = ct.prows / r, rs.offset = offset, rs.per_instance = per_instance != 0;
+    if (!h->cost_p[t]) h->model_dirty = true; // shared model: c0 / C2 change
+    h->cost_p[t] = h->d_cost_p[t];
+    return write_windows(h, h->last_stream, who);
+}
+
+copra_status_t copra_batch_schedule_seek(copra_batch_t* h, long long tick)
+{
+    if (!h) return fail(COPRA_ERR_ARG, "copra_batch_schedule_seek: null handle");
+    if (tick < 0) return fail(COPRA_ERR_ARG, "copra_batch_schedule_seek: negative tick");
+    h->sched_tick = tick;
+    return write_windows(h, h->last_stream, "copra_batch_schedule_seek");
+}
+
+long long copra_batch_schedule_tick(const copra_batch_t* h)
+{
+    return h ? h->sched_tick : -1;
 }
 
 const double* copra_batch_x0_device(const copra_batch_t* h)

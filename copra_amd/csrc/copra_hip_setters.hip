@@ -271,6 +271,7 @@ copra_status_t copra_batch_set_cost_reference(copra_batch_t* h, int cost_index, 
     if (cost_index < 0 || cost_index >= (int)h->hp.cost_slot.size()) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference: no such cost");
     cost_index = h->hp.cost_slot[(size_t)cost_index]; // (dense costs are not among the kernel-evaluated terms)
     if (cost_index < 0) return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_reference: a dense (host-evaluated) cost has no reference p");
+    h->ref_sched[cost_index].sched = nullptr; // (a reference given by hand ends the cost's schedule)
     if ((p != nullptr) != (h->cost_p[cost_index] != nullptr)) h->model_dirty = true; // shared model: c0 / C2 change
     if (!p) { // back to the controller-wide reference given at creation
         h->cost_p[cost_index] = nullptr;
@@ -335,6 +336,7 @@ copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_ind
     if (!h->d_cost_p[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_p[t], b * rows * sizeof(double)));
     double* const out = h->d_cost_p[t];
     if (p == out) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference_all: p aliases the library's buffer");
+    h->ref_sched[t].sched = nullptr; // (a reference given by hand ends the cost's schedule)
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a solve that still reads the buffer)
     const double* src = p;
     if (!on_device) {

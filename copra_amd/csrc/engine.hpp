@@ -7,7 +7,8 @@
 //   copra_hip_jit.hip      copra_batch_specialise, copra_qp_dense_specialise (hipcc --genco at run time)
 //   copra_hip_qp.hip       plug-in point 1: copra_qp_solve_dense_batch and its kernels
 //   copra_hip_packed16/32.hip  the one-wave bodies with 16 / 32 lanes per instance
-//   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp)
+//   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp); reference
+//                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -101,6 +102,15 @@ struct AdaptState {
     const double* last_control = nullptr; // ... and its controls: what copra_batch_advance applies to the plant (copra_hip_plant.hip)
 };
 
+// A cost whose reference follows a schedule (copra_batch_set_reference_schedule): the tick writes its window into d_cost_p (copra_hip_plant.hip)
+struct RefSchedule {
+    const double* sched = nullptr; // device: the caller's, or `own`; null: the cost has no schedule
+    double* own = nullptr; // the library's copy of a host schedule
+    size_t own_doubles = 0;
+    long long steps = 0;
+    int r = 0, S = 0, offset = 0, per_instance = 0;
+};
+
 struct copra_batch {
     HostPlan hp;
     AdaptState ad;
@@ -144,6 +154,8 @@ struct copra_batch {
     double *d_row_f_inst = nullptr, *d_lb_inst = nullptr, *d_ub_inst = nullptr; // per-instance rhs / control bounds
     double* d_cost_p[kMaxCosts] = {}; // per-instance cost references (owned copies) ...
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
+    RefSchedule ref_sched[kMaxCosts]; // ... which the tick rewrites for the costs that follow a schedule,
+    long long sched_tick = 0; // at the controller's tick counter tau: the advances so far, or what copra_batch_schedule_seek set
     double* d_cost_w[kMaxCosts] = {}; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation

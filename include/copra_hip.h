@@ -382,6 +382,34 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
 const double* copra_batch_x0_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_x0(copra_batch_t* h, double* x0);
 
+/* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
+ *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
+ *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
+ *      sched [per_instance ? batch : 1][steps][r] doubles, and the library moves the window the horizon sees by one step per tick, on the
+ *      device, in stream order.  With S = (rows of that cost as created) / r and tau the controller's tick counter, the next solve reads for
+ *      instance b
+ *        p[b][s r + i] = sched[b or 0][min(tau + offset + s, steps - 1)][i],   s = 0 .. S-1
+ *      (the last block is held beyond the end of the schedule).  A reference trajectory -- a full-size TrajectoryCost -- has r = xDim,
+ *      S = N + 1, offset 0; a full-size ControlCost / MixedCost S = N; a per-step cost (a goal that moves) S = 1; a TargetCost S = 1 and
+ *      offset = N (the goal of the horizon's end).
+ *      The window is written into the library's per-instance reference buffer, which becomes the cost's reference: the state
+ *      copra_batch_set_cost_reference_all leaves (same remarks on the per-instance-reference mode), every kernel reads it unchanged.
+ *      copra_batch_set_reference_schedule writes the window of the current tau at once, on the stream of the last solve / tick; it
+ *      synchronises that stream once when it copies a host schedule, never with on_device != 0 (the schedule is then used in place and
+ *      must stay valid).  sched == NULL ends the schedule and keeps the last window; copra_batch_set_cost_reference and
+ *      copra_batch_set_cost_reference_all on that cost end it too (p == NULL: back to the creation reference).
+ *      The tick: copra_batch_advance does tau += 1 for the controller -- all instances share tau; a failed instance keeps its state, but
+ *      time moves on -- and writes, behind the plant step on the same stream, the new windows of all scheduled costs with ONE launch: no
+ *      host synchronisation, no allocation.  copra_batch_rollout therefore tracks.  copra_batch_schedule_seek: tau <- tick and the windows
+ *      rewritten, ordered on the stream of the last solve / tick, no synchronisation.  copra_batch_schedule_tick: tau (-1: NULL handle).
+ *      COPRA_ERR_DOMAIN: r does not divide the cost's rows, or the controller evaluates a full-size cost step by step and r is not the rows
+ *      of one step; COPRA_ERR_ARG: steps < 1, offset < 0, no such cost, a NULL handle, a negative tick; COPRA_ERR_UNSUPPORTED: a dense
+ *      (host-evaluated) cost, more than 8 scheduled costs. ---- */
+copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_index, const double* sched, long long steps, int r, int offset,
+    int per_instance, int on_device);
+copra_status_t copra_batch_schedule_seek(copra_batch_t* h, long long tick);
+long long copra_batch_schedule_tick(const copra_batch_t* h);
+
 /* ---- parity hooks: the dense QP of one instance as LMPC exposes it (include/LMPC.h:112-127: Q c Aineq bineq Aeq
  *      beq lb ub), rebuilt ON THE DEVICE by the same condense code the solver runs.  Any pointer may be NULL.
  *      Q [n x n], c [n], Aeq [neq x n], beq [neq], Aineq [nineq x n], bineq [nineq], lb [n], ub [n]. ---- */
