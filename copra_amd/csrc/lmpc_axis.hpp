@@ -584,6 +584,11 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
         double sU = thr, sL = thr, sR = 0.0, nR = 1.0; // slack of the worst upper bound | lower bound | row, and that row's squared norm
         int kU = -1, kL = -1, cR = -1, lR = posSpare | kEmpty; // their stages | the row's index in the stacked order and where it lives
         const unsigned mb = mact[0] | mact[1]; // (the twin of an active bound is its negative: never a candidate -- boxes are not empty here, see below)
+        // CT: a slot's index in the stacked order is ridx0 + k ridxd with ridxd >= 0, or -1 at every step (FusedPlan::axis_const) -- whether the
+        // slot holds a row is decided once, the index itself is made only where a row is violated
+        bool rowon[RPA];
+#pragma unroll
+        for (int j = 0; j < RPA; ++j) rowon[j] = ridx0[j] >= 0;
         double x[NXA], xi[NXA], G[NXA], W[NXA][NXA], nrow[RPA]; // iterate's state | the step's state | A^k B | sum_{t < k} G_t G_t' (row norms; CT: nrow, per row)
 #pragma unroll
         for (int i = 0; i < NXA; ++i) {
@@ -599,20 +604,18 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
 #pragma unroll
             for (int j = 0; j < RPA; ++j) {
                 if (j < rpa) {
-                    double e[NXA], gq = 0.0, f, ax = 0.0, n2 = 0.0;
-                    int cid;
+                    double e[NXA], gq = 0.0, f, ax = 0.0, n2 = 0.0, cidd = 0.0;
                     if (CT) {
 #pragma unroll
                         for (int i = 0; i < NXA; ++i) e[i] = re[j][i];
                         f = rf[j];
-                        cid = ridx0[j] + k * ridxd[j];
                     } else {
                         const double* const rw = T + oRows + (k * rpa + j) * RW;
 #pragma unroll
                         for (int i = 0; i < NXA; ++i) e[i] = rw[i];
                         gq = with_u ? rw[NXA] : 0.0;
                         f = rw[NXA + 1];
-                        cid = (int)rw[NXA + 2];
+                        cidd = rw[NXA + 2]; // (a whole number, -1: the slot is empty)
                     }
 #pragma unroll
                     for (int i = 0; i < NXA; ++i) ax += e[i] * x[i];
@@ -627,10 +630,13 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                         n2 += gq * gq;
                     }
                     const double s = f - ax;
-                    const bool neg = (s < thr) & (cid >= 0);
-                    if (FIRST && count_viol) nviol += neg ? 1 : 0;
-                    const bool v = neg & (((mact[2 + j] >> k) & 1u) == 0u);
-                    if (wave_any(v)) { // (a violated row is the exception: nothing below runs where no lane has one at this step)
+                    // (a violated row is the exception: nothing below runs where no lane has one at this step -- an empty slot has f = inf, its
+                    //  slack is not below thr: whether the slot holds a row is looked at behind the test as well)
+                    if (wave_any(s < thr)) {
+                        const bool neg = (s < thr) & (CT ? rowon[j] : (cidd >= 0.0));
+                        if (FIRST && count_viol) nviol += neg ? 1 : 0;
+                        const bool v = neg & ((mact[2 + j] & (1u << k)) == 0u);
+                        const int cid = CT ? ridx0[j] + k * ridxd[j] : (int)cidd;
                         const double l = s * s * nR, r = sR * sR * n2;
                         const bool better = v & ((cR < 0) | (l > r) | ((l == r) & (cid < cR)));
                         sR = better ? s : sR;
@@ -671,10 +677,13 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                 rows_of(k, u, true);
                 {
                     const double su = (CT ? ubc : UB[k]) - u, sl = u - (CT ? lbc : UB[NH + k]);
-                    const bool free_k = ((mb >> k) & 1u) == 0u;
-                    if (FIRST && count_viol) nviol += ((su < thr) ? 1 : 0) + ((sl < thr) ? 1 : 0);
-                    const bool tu = free_k & (su < sU), tl = free_k & (sl < sL);
-                    if (wave_any(tu | tl)) {
+                    // (sU, sL <= thr: a candidate is a violated bound -- the exception, like a violated row; whether it is free to be picked, whether
+                    //  it beats the worst so far and the first solve's count of violated constraints are looked at behind that test only)
+                    const bool vu = su < thr, vl = sl < thr;
+                    if (wave_any(vu | vl)) {
+                        const bool free_k = (mb & (1u << k)) == 0u;
+                        if (FIRST && count_viol) nviol += (vu ? 1 : 0) + (vl ? 1 : 0);
+                        const bool tu = free_k & (su < sU), tl = free_k & (sl < sL);
                         sU = tu ? su : sU;
                         kU = tu ? k : kU;
                         sL = tl ? sl : sL;
@@ -886,6 +895,17 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
         RC[loc_pos(ploc)] = have ? psg : 0.0; // (lanes without a pick: the spare entry)
         const double nqn = backward(rows_live, kp, true);
         if (ka >= 0) forward_resp(rows_live, ka);
+        // The largest active set among the lanes that have a pick: beyond slot qw every such lane's row of S is the identity's, and g, r and
+        // the multiplier are zero there -- the small dense algebra below stops at qw, behind wave-uniform branches.  What it leaves out are
+        // products with those rows' exact zeros and ones, which change no bit of the slots below q.  No NaN or Inf can hide behind them: the
+        // rows of the factor and the entries of w and r beyond qw are not formed from S at all but set to the identity's and to zero -- the
+        // second substitution's sums still run over them, 0 x 0 --; g r there is 0 x 0; and tm r is left out only for multiplier slots beyond
+        // q, which are overwritten before they are read (alam[q] when a pick joins; the minimum ratio looks at a < q only).
+        // (A lane WITHOUT a pick may hold more than qw constraints: its r is then not that of its own S, but it takes no step -- tt = tm = 0,
+        //  nothing of its active set changes -- and r stays finite, so U + 0 z is U.)
+        int qw = 0;
+#pragma unroll
+        for (int a = 0; a < QMAX; ++a) qw += wave_any(have & (q > a)) ? 1 : 0;
         double g[BIG ? 1 : QMAX], r[BIG ? 1 : QMAX];
 #pragma unroll
         for (int a = 0; a < (BIG ? 1 : QMAX); ++a) g[a] = r[a] = 0.0;
@@ -908,7 +928,6 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                 // r = S^-1 g from the factor S = L L' the lane KEEPS (L below the diagonal, 1 / L(i, i) on it, the identity beyond q): two
                 // substitutions over the whole padded triangle -- every address a constant, the reads travel together.  (The factor grows by
                 // a row when a constraint joins -- the row IS w = L^-1 g, see below -- and is made again from S when one leaves.)
-                const int qw = wave_top(have ? q : 0); // (the largest active set among the wave's lanes: beyond it every row is the identity's)
 #pragma unroll
                 for (int i = 0; i < QMAX; ++i) {
                     if (i < qw) {
@@ -936,61 +955,74 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                 }
             } else {
 #pragma unroll
-                for (int a = 0; a < QMAX; ++a) {
+                for (int a = 0; a < QMAX; ++a) { // (every slot: the reads travel together)
                     const double v = RC[loc_pos(aloc[a])];
                     g[BIG ? 0 : a] = (a < q) ? loc_sg(aloc[a]) * v : 0.0;
                 }
-                // r = S^-1 g by Cholesky (S is the identity beyond q, g is zero there: so is r)
+                // r = S^-1 g by Cholesky (S is the identity beyond q, g is zero there: so is r), rows and columns below qw only
                 constexpr int QS = BIG ? 1 : QMAX;
-                double L[QS][QS], di[QS], w[QS];
+                double Sv[QS * (QS + 1) / 2], L[QS][QS], di[QS], w[QS];
+#pragma unroll
+                for (int e = 0; e < QS * (QS + 1) / 2; ++e) Sv[e] = Sl[e]; // (requested together, whatever qw: one trip to LDS)
 #pragma unroll
                 for (int i = 0; i < QS; ++i) {
+                    di[i] = 1.0;
+                    w[i] = 0.0;
 #pragma unroll
-                    for (int j = 0; j <= i; ++j) {
-                        double sacc = Sl[i * (i + 1) / 2 + j];
+                    for (int j = 0; j < QS; ++j) L[i][j] = 0.0;
+                }
 #pragma unroll
-                        for (int t = 0; t < j; ++t) sacc -= L[i][t] * L[j][t];
-                        if (j < i) {
-                            L[i][j] = sacc * di[j];
-                        } else {
-                            AX_WHY(2, have & !(sacc > 0.0));
-                            giveup = giveup | (have & !(sacc > 0.0));
-                            di[i] = fast_rsqrt(sacc > 0.0 ? sacc : 1.0);
-                            L[i][i] = sacc * di[i];
+                for (int i = 0; i < QS; ++i) {
+                    if (i < qw) {
+#pragma unroll
+                        for (int j = 0; j <= i; ++j) {
+                            double sacc = Sv[i * (i + 1) / 2 + j];
+#pragma unroll
+                            for (int t = 0; t < j; ++t) sacc -= L[i][t] * L[j][t];
+                            if (j < i) {
+                                L[i][j] = sacc * di[j];
+                            } else {
+                                AX_WHY(2, have & !(sacc > 0.0));
+                                giveup = giveup | (have & !(sacc > 0.0));
+                                di[i] = fast_rsqrt(sacc > 0.0 ? sacc : 1.0);
+                                L[i][i] = sacc * di[i];
+                            }
                         }
+                        double sacc = g[i]; // (the first substitution, row by row behind the factor's)
+#pragma unroll
+                        for (int t = 0; t < i; ++t) sacc -= L[i][t] * w[t];
+                        w[i] = sacc * di[i];
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < QS; ++i) {
-                    double sacc = g[i];
-#pragma unroll
-                    for (int t = 0; t < i; ++t) sacc -= L[i][t] * w[t];
-                    w[i] = sacc * di[i];
-                }
-#pragma unroll
                 for (int i = QS - 1; i >= 0; --i) {
-                    double sacc = w[i];
+                    if (i < qw) {
+                        double sacc = w[i];
 #pragma unroll
-                    for (int t = i + 1; t < QS; ++t) sacc -= L[t][i] * r[t];
-                    r[i] = sacc * di[i];
+                        for (int t = i + 1; t < QS; ++t) sacc -= L[t][i] * r[t];
+                        r[i] = sacc * di[i];
+                    }
                 }
             }
         }
         double zn = nqn;
 #pragma unroll
-        for (int a = 0; a < QMAX; ++a) zn -= AX_G(a) * AX_R(a);
+        for (int a = 0; a < QMAX; ++a)
+            if (a < qw) zn -= AX_G(a) * AX_R(a);
         // t1 = min lambda_i / r_i over r_i > 0, the lowest position among equals (cross-multiplied: one division)
         int l1 = -1;
         double lb_ = 0.0, rb_ = 1.0;
 #pragma unroll
         for (int a = 0; a < QMAX; ++a) {
-            const double ra = AX_R(a);
-            const bool ok = (a < q) & (ra > 0.0);
-            const double la = alam[a];
-            const bool better = ok & ((l1 < 0) | (la * rb_ < lb_ * ra));
-            lb_ = better ? la : lb_;
-            rb_ = better ? ra : rb_;
-            l1 = better ? a : l1;
+            if (a < qw) {
+                const double ra = AX_R(a);
+                const bool ok = (a < q) & (ra > 0.0);
+                const double la = alam[a];
+                const bool better = ok & ((l1 < 0) | (la * rb_ < lb_ * ra));
+                lb_ = better ? la : lb_;
+                rb_ = better ? ra : rb_;
+                l1 = better ? a : l1;
+            }
         }
         const double t1 = lb_ / rb_;
         // t2 = -s / z'n; a direction that is zero (n+ in the span of the active normals: |z|^2 <= vsmall is checked behind the step) or not a
@@ -1011,13 +1043,14 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
         // z = Q^-1 (n+ - N r): the coefficients over the responses, the recursions again, U += tt z and the next scan
         if (ka >= 0) { // (else: the combined normal IS n+, its recursion has been done)
 #pragma unroll
-            for (int a = 0; a < QMAX; ++a) RC[loc_pos(aloc[a])] = -AX_R(a) * loc_sg(aloc[a]); // (empty slots: the spare entry)
+            for (int a = 0; a < QMAX; ++a)
+                if (a < qw) RC[loc_pos(aloc[a])] = -AX_R(a) * loc_sg(aloc[a]); // (empty slots: the spare entry)
             (void)backward(rows_live, kp, false);
         }
         forward_scan(std::false_type {}, tt);
         if (ka >= 0) {
 #pragma unroll
-            for (int a = 0; a < QMAX; ++a) RC[loc_pos(aloc[a])] = 0.0;
+            for (int a = 0; a < QMAX; ++a) RC[loc_pos(aloc[a])] = 0.0; // (every slot: a lane without a pick may hold responses beyond qw)
         }
         RC[loc_pos(ploc)] = 0.0;
         // qpgen2's test: |z|^2 <= vsmall -- no step in primal space.  Where z'n+ said so too and a multiplier blocks: the dual step.  Without one:
@@ -1029,7 +1062,8 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
         have = have & !giveup;
         if (have) {
 #pragma unroll
-            for (int a = 0; a < QMAX; ++a) alam[a] -= tm * AX_R(a);
+            for (int a = 0; a < QMAX; ++a)
+                if (a < qw) alam[a] -= tm * AX_R(a);
             plam += tm;
             if (full) {
                 // the pick joins the active set: slot q, S grows by the row [g' | n+' Q^-1 n+]
@@ -1045,7 +1079,7 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                         double* const row = Sl + q * (q + 1) / 2;
 #pragma unroll
                         for (int b = 0; b < QMAX; ++b)
-                            if (b <= q) row[b] = (b == q) ? nqn : AX_G(b);
+                            if (b <= qw && b <= q) row[b] = (b == q) ? nqn : AX_G(b); // (q <= qw here: the lane has a pick)
                     }
                     if constexpr (BIG) { // the factor's new row: [w' | sqrt(n+' Q^-1 n+ - w'w)], its diagonal kept as the reciprocal
                         double* const lrow = Ll + q * (q + 1) / 2;
