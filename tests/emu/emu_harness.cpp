@@ -162,16 +162,25 @@ namespace emu {
 using namespace copra_hip;
 
 static const double* g_cost_p[copra_hip::kMaxCosts]; // per-instance cost references for the next emu_lmpc_solve
+static const double* g_cost_w[copra_hip::kMaxCosts]; // per-instance cost weights, by the USER's cost index (emu_set_cost_weights)
+static bool emu_weights_set()
+{
+    for (int k = 0; k < copra_hip::kMaxCosts; ++k)
+        if (g_cost_w[k]) return true;
+    return false;
+}
 
 // The body of a build of the (instance, axis)-per-lane solver (axis_builds.hpp) for wave g -- in the tests' two-slot mode (small_q) the first
-// launch's build with room for two active constraints and without the horizon compiled in.  false: the emulator has no body for it (weights).
+// launch's build with room for two active constraints and without the horizon compiled in.  The families first_w and list_w are the same bodies
+// with WTS (per-instance cost weights: axis_kernels.hpp, copra_lmpc_axis_w_kernel and copra_lmpc_axis_list_w_kernel).
 static bool emu_axis_body(const AxisBuild* b, bool small_q, const FusedPlan& P, int g)
 {
 #define COPRA_EMU_AXIS_first(NXA, NU, NMAX, QMAX, EXACT, CT, RPA)                                                                  \
     (small_q ? lmpc_axis_body<NXA, NU, NMAX, 2, false, CT, RPA>(P, g) : lmpc_axis_body<NXA, NU, NMAX, QMAX, EXACT, CT, RPA>(P, g)), true
 #define COPRA_EMU_AXIS_list(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) lmpc_axis_body<NXA, NU, NMAX, QMAX, false, CT, RPA, true>(P, g), true
-#define COPRA_EMU_AXIS_first_w(...) false
-#define COPRA_EMU_AXIS_list_w(...) false
+#define COPRA_EMU_AXIS_first_w(NXA, NU, NMAX, QMAX, EXACT, CT, RPA)                                                                \
+    (small_q ? lmpc_axis_body<NXA, NU, NMAX, 2, false, CT, RPA, false, true>(P, g) : lmpc_axis_body<NXA, NU, NMAX, QMAX, EXACT, CT, RPA, false, true>(P, g)), true
+#define COPRA_EMU_AXIS_list_w(NXA, NU, NMAX, QMAX, EXACT, CT, RPA) lmpc_axis_body<NXA, NU, NMAX, QMAX, false, CT, RPA, true, true>(P, g), true
 #define COPRA_EMU_AXIS_RUN(UNIT, FAMILY, ...) if (b == e++) return COPRA_EMU_AXIS_##FAMILY(__VA_ARGS__);
     const AxisBuild* e = kAxisBuilds;
     COPRA_AXIS_BUILDS(COPRA_EMU_AXIS_RUN)
@@ -186,8 +195,27 @@ static bool emu_axis_body(const AxisBuild* b, bool small_q, const FusedPlan& P, 
 extern "C" {
 
 static int g_lane_hist[copra_hip::kLaneHistBins]; // violated-row histogram of the last lane pass (FusedPlan::lane_hist)
+// what the axis solver of the last emu_lmpc_solve ran: the entries of kAxisBuilds of its two launches (-1: it did not run), the instances its
+// first launch listed for the second, and the instances the second listed for the tier
+static int g_axis_last[4] = { -1, -1, 0, 0 };
+void emu_last_axis_run(int* out) { std::copy(g_axis_last, g_axis_last + 4, out); }
+// entry k of kAxisBuilds as emu_axis_build reports a pick; 0: no such entry
+int emu_axis_build_entry(int k, int* out)
+{
+    if (k < 0 || k >= (int)(sizeof(kAxisBuilds) / sizeof(kAxisBuilds[0]))) return 0;
+    const AxisBuild* b = kAxisBuilds + k;
+    const int v[8] = { (int)b->family, b->nxa, b->nu, b->nmax, b->qmax, b->exact, b->ct, b->rpa };
+    std::copy(v, v + 8, out);
+    return 1;
+}
 void emu_last_lane_hist(int* out) { std::copy(g_lane_hist, g_lane_hist + copra_hip::kLaneHistBins, out); }
 void emu_set_cost_reference(int cost_index, const double* p) { g_cost_p[cost_index] = p; }
+// per-instance weights [batch][prows] of the user's cost `cost_index` for the next emu_lmpc_solve (copra_batch_set_cost_weights); nullptr: the
+// ones given at creation
+void emu_set_cost_weights(int cost_index, const double* w)
+{
+    if (cost_index >= 0 && cost_index < copra_hip::kMaxCosts) g_cost_w[cost_index] = w;
+}
 // the engine options of the next calls (copra_options_t; what copra_batch_create_with_options takes): every HostPlan built here starts
 // from them, and the launch decisions this harness restates from copra_batch_solve consult them
 void emu_set_options(const copra_options_t* opts)
@@ -229,6 +257,8 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         fprintf(stderr, "emu: %s\n", hp.error.c_str());
         return (int)rc;
     }
+    g_axis_last[0] = g_axis_last[1] = -1;
+    g_axis_last[2] = g_axis_last[3] = 0;
     if (std::getenv("COPRA_EMU_WANT_RIC")) (void)take_ric_layout(hp); // (what copra_batch_specialise does once the shape's kernel is compiled)
     if (const char* steps = std::getenv("COPRA_EMU_LADDER_STEPS")) { // (what adapt_layout does after solves that overflowed: steps down the tier's ladder)
         for (int q = 0; q < std::atoi(steps); ++q) {
@@ -257,6 +287,26 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
     P.x0ub = x0ub;
     P.x0_opt = x0_opt;
     for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = g_cost_p[k];
+    // per-instance weights, as copra_batch_set_cost_weights places them: the user's cost k is the kernel-evaluated term cost_slot[k]; a dense
+    // (host-evaluated) cost has no weights the kernels read
+    bool weights = false;
+    for (int k = 0; k < kMaxCosts; ++k) {
+        if (!g_cost_w[k]) continue;
+        if (k >= (int)hp.cost_slot.size()) return (int)COPRA_ERR_ARG;
+        const int t = hp.cost_slot[(size_t)k];
+        if (t < 0) return (int)COPRA_ERR_UNSUPPORTED;
+        P.cost_w[t] = g_cost_w[k];
+        weights = true;
+    }
+    // (copra_hip.hip, weights_route: the Riccati-factor tier's tables hold the creation weights -- a controller with per-instance weights runs
+    //  the generic one-wave kernels on the layout that tier's ladder ends on)
+    LdsLayout lds_own = P.lds; // (the controller's own first tier, before the weights route it away: what the front ends' conditions look at)
+    if (weights && P.lds.ric && !hp.large && !P.initial_state) {
+        hp.two_tier = hp.dense && hp.safe_two_tier && !hp.lds_safe.ric;
+        hp.dense = false;
+        P.lds = hp.two_tier ? hp.lds_safe : hp.lds_full;
+        hp.lds_bytes = (size_t)P.lds.total * sizeof(double);
+    }
     P.row_f_inst = g_row_f_inst;
     P.lb_inst = g_lb_inst;
     P.ub_inst = g_ub_inst;
@@ -311,6 +361,11 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         LdsLayout lq {};
         if (tri_layout_with_lds_q1(P, P.lds, lq)) P.lds = lq;
     }
+    if (!s6 && !sfull && !(use_specialised && lds_own.ric) && lds_own.q1regs > 0) { // (the same step on the layout the weights routed away)
+        LdsLayout lq {};
+        if (tri_layout_with_lds_q1(P, lds_own, lq)) lds_own = lq;
+    }
+    const bool ric_layout = lds_own.ric != 0;
     bool lane_failed = false; // (the instance comes from the one-instance-per-lane pass with a failed factorisation)
     auto body = [&](const FusedPlan& PP, int b) {
         // the library's builds with a RUN-TIME horizon (copra_hip_ric.hip; select_fused_kernel) for the shapes of ric_aot_shape -- unless the
@@ -368,9 +423,11 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
     const size_t bytes1 = (size_t)P.lds.total * sizeof(double);
     // the one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp), as copra_batch_solve runs it
     // (copra_hip.hip: lane_pass_wanted): the instances it does not finish go through the first tier
-    bool lane_pass = P.lane_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && (P.lds.ric || std::getenv("COPRA_EMU_LANE_FILTER")) && !default_options().no_lane_pass
+    bool lane_pass = P.lane_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && (ric_layout || std::getenv("COPRA_EMU_LANE_FILTER")) && !default_options().no_lane_pass
         && ((P.nx == 6 && P.nu == 3) || (P.nx == 4 && P.nu == 2) || (P.nx == 5 && P.nu == 3) || (P.nx == 2 && P.nu == 1));
     for (int k = 0; k < kMaxCosts; ++k) lane_pass = lane_pass && (!P.cost_p[k] || P.lane_cref >= 0);
+    const bool lane_shape = lane_pass; // (what the axis solver's condition below asks of the pass: its shape, not whether it runs)
+    lane_pass = lane_pass && !weights; // (lane_pass_wanted: its tables hold the creation weights)
     std::vector<int> lane_list((size_t)dims->batch + 64, -1);
     std::vector<double> lane_ws, lane_ws2;
     int lane_cnt[4] = { 0, 0, 0, 0 }; // (as the device's: [left over | the next solve's] [+ 2: ended by the pass's own steps])
@@ -385,10 +442,22 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         P.axis_const = hp.axis1_const;
     }
     // (independent of the pass: chains of three states per control have no build of it)
-    bool axis_pass = P.axis_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && !default_options().no_lane_pass && (lane_pass || P.nx == 3 * P.nu || P.nx == P.nu)
+    bool axis_pass = P.axis_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && !default_options().no_lane_pass && (lane_shape || P.nx == 3 * P.nu || P.nx == P.nu)
         && !default_options().no_axis_solver && axis_solver_nmax(P.nx, P.nu, P.N) > 0
         && (!(P.row_f_inst || P.lb_inst || P.ub_inst) || (P.axis_const && (P.lb_inst == nullptr) == (P.ub_inst == nullptr)));
     for (int k = 0; k < kMaxCosts; ++k) axis_pass = axis_pass && (!P.cost_p[k] || (P.axis_cref >= 0 && k < P.ncost));
+    if (axis_pass && weights) { // (per-instance weights: copra_hip.hip, axis_solver_wanted -- both launches need a build that reads them, the lane
+        // divides by the creation weight, and a full-size cost has no coefficients in FusedPlan::axis_cref)
+        axis_pass = P.axis_cref >= 0 && pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, true, false)
+            && pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, true, true);
+        for (int t = 0; t < P.ncost && axis_pass; ++t) {
+            if (!P.cost_w[t]) continue;
+            const CostTerm& ct = P.cost[t];
+            if (ct.full) axis_pass = false;
+            for (int r = 0; r < ct.rows; ++r)
+                if (P.params[(size_t)ct.offW + r] == 0.0) axis_pass = false;
+        }
+    }
     if (axis_pass && P.stage_refs) { // (reference trajectories: copra_hip.hip, axis_solver_wanted)
         int oB = 0, oR = 0, rcs = 0;
         (void)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs);
@@ -409,9 +478,9 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         int oB = 0, oR = 0, rcs = 0;
         const size_t abytes = (size_t)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs) * sizeof(double); // (sized for the library's builds; the two-slot test build needs less)
         const bool small_q = std::getenv("COPRA_EMU_AXIS_QMAX2") != nullptr; // (tests: an active set that outgrows the lane -- the hand-over to the tier)
-        // the library's builds: the same pick as copra_hip.hip's select_axis_kernel and select_axis_list_kernel (no per-instance weights here)
-        const AxisBuild* first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, false, false);
-        const AxisBuild* second = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, false, true);
+        // the library's builds: the same pick as copra_hip.hip's select_axis_kernel and select_axis_list_kernel
+        const AxisBuild* first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, false);
+        const AxisBuild* second = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, true);
         if (!first || !second) {
             std::fprintf(stderr, "emu: the axis solver has no build for nx %d, nu %d, N %d, axis_rpa %d\n", P.nx, P.nu, P.N, P.axis_rpa);
             return -100;
@@ -422,6 +491,9 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
             if (r != 0 || !ran) return -100;
         }
         P.lane_hist = nullptr;
+        g_axis_last[0] = (int)(first - kAxisBuilds);
+        g_axis_last[1] = (int)(second - kAxisBuilds);
+        g_axis_last[2] = g_axis_last[3] = lane_count;
         // the second chance of what it listed (copra_lmpc_axis_list_kernel): room for kAxisQmaxBig active constraints per lane, instances from the list
         std::vector<int> list2((size_t)dims->batch + 64, -1);
         int cnt2[4] = { 0, 0, 0, 0 }; // (as the first launch's: [left over | - | ended by its steps | -])
@@ -452,6 +524,7 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
             }
             lane_list = list2;
             lane_count = count2;
+            g_axis_last[3] = count2;
         }
         P.lane_from_list = 1;
         P.lane_spec = P.lds.ricC ? 1 : 0; // (nothing is handed over: the tier sweeps for itself)
@@ -539,6 +612,7 @@ int emu_lmpc_solve_riccati(const copra_dims_t* dims, int n_costs, const copra_co
     }
     point_plan_to_host(hp);
     FusedPlan& P = hp.plan;
+    if (emu_weights_set()) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_solve: the stage plan holds the creation weights)
     HostStagePlan hs;
     build_stage_plan(hp, hs, g_lb_inst != nullptr);
     if (!hs.eligible) {
@@ -604,6 +678,7 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
         return (int)rc;
     }
     if (hp.large) return (int)COPRA_ERR_UNSUPPORTED;
+    if (emu_weights_set()) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_set_cost_weights: the shared model holds the creation weights)
     point_plan_to_host(hp);
     FusedPlan P = hp.plan;
     const int nx = P.nx, nu = P.nu, N = P.N, n = P.n, X = P.X, np1 = nx + 1;

@@ -44,6 +44,22 @@ def axis_build(nx, nu, N, axis_const, axis_rpa, stage_refs, weights, list_):
     return (AXIS_FAMILIES[out[0]], out[1], out[2], out[3], out[4], bool(out[5]), bool(out[6]), out[7])
 
 
+def last_axis_run():
+    """what the (instance, axis)-per-lane solver of the last lmpc_solve ran: dict(first, second: the builds of its two launches as axis_build
+    reports them, listed_first: instances the first launch left to the second, listed_second: instances the second left to the tier), or None:
+    the solver did not run"""
+    v = (C.c_int * 4)()
+    lib().emu_last_axis_run(v)
+    if v[0] < 0:
+        return None
+    picks = []
+    for k in (v[0], v[1]):
+        out = (C.c_int * 8)()
+        assert lib().emu_axis_build_entry(k, out)
+        picks.append((AXIS_FAMILIES[out[0]], out[1], out[2], out[3], out[4], bool(out[5]), bool(out[6]), out[7]))
+    return dict(first=picks[0], second=picks[1], listed_first=v[2], listed_second=v[3])
+
+
 def _sync_options():
     """hand _capi.OPTIONS (what BatchLMPC would pass to copra_batch_create_with_options) to the harness"""
     o = _capi.make_options()
@@ -55,6 +71,20 @@ def last_lane_hist():
     out = (C.c_int * 32)()
     lib().emu_last_lane_hist(out)
     return np.array(list(out))
+
+
+def _set_weights(cost_weights):
+    """hand per-instance weights {cost_index: (batch, prows)} to the harness (emu_set_cost_weights); returns the arrays, to be kept alive
+    until _clear_weights()"""
+    ws = {int(k): np.ascontiguousarray(v, dtype=np.float64) for k, v in (cost_weights or {}).items() if v is not None}
+    for k in range(8):
+        lib().emu_set_cost_weights(k, _capi.dptr(ws[k]) if k in ws else C.c_void_p())
+    return ws
+
+
+def _clear_weights():
+    for k in range(8):
+        lib().emu_set_cost_weights(k, C.c_void_p())
 
 
 def _batchify(A, B, d, x0):
@@ -70,7 +100,16 @@ def _batchify(A, B, d, x0):
 
 
 def lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance=-1, specialised=True, initial_state=None, cost_refs=None,
-               row_rhs=None, bounds=None):
+               row_rhs=None, bounds=None, cost_weights=None):
+    """cost_weights: {cost_index: array (batch, prows)} per-instance weights (copra_batch_set_cost_weights), cleared again after the solve"""
+    ws = _set_weights(cost_weights)
+    try:
+        return _lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance, specialised, initial_state, cost_refs, row_rhs, bounds, ws)
+    finally:
+        _clear_weights()
+
+
+def _lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance, specialised, initial_state, cost_refs, row_rhs, bounds, ws):
     """cost_refs: {cost_index: array (batch, rows)} per-instance references (copra_batch_set_cost_reference);
     row_rhs: (batch, mgen) per-instance right-hand sides in stacked row order; bounds: (lower, upper) each (batch, n)"""
     _sync_options()
@@ -85,6 +124,10 @@ def lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance=-1, specialised=True,
     for k in range(8):
         lib().emu_set_cost_reference(k, _capi.dptr(refs[k]) if k in refs else C.c_void_p())
     batch, nu, nx = Bb.shape[0], Bb.shape[1], Bb.shape[2]
+    for k, w in ws.items():  # (the kernels index [instance][row of the whole reference]: a wrong shape would read past the array)
+        rows = np.atleast_1d(np.asarray(costs[k]["p"])).size if k < len(costs) and costs[k].get("p") is not None else w.shape[-1]
+        if w.shape != (batch, rows):
+            raise ValueError("cost_weights[%d]: shape %r, expected %r" % (k, w.shape, (batch, rows)))
     keep = []
     cc = _capi.pack_costs(costs, keep)
     kk = _capi.pack_cstrs(cstrs, keep)
@@ -127,6 +170,8 @@ def lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance=-1, specialised=True,
                               dump_instance, p(dQ), p(dc), p(dA), p(db_), sizes, 1 if specialised else 0, isd,
                               p(x0lb) if x0lb is not None else vp(), p(x0ub) if x0ub is not None else vp(),
                               p(x0o) if x0o is not None else vp())
+    if rc == _capi.COPRA_ERR_UNSUPPORTED:
+        raise _capi.CopraUnsupported("emu")
     if rc != 0:
         raise RuntimeError("emulator failed rc=%d" % rc)
     out = dict(control=u, trajectory=tr, status=st, iter=it, lds_bytes=sizes[3], overflowed=sizes[4], rcap=sizes[5], factor_only=bool(sizes[6]),
@@ -139,9 +184,18 @@ def lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance=-1, specialised=True,
     return out
 
 
-def lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state=None, cost_refs=None, row_rhs=None, bounds=None):
+def lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state=None, cost_refs=None, row_rhs=None, bounds=None, cost_weights=None):
     """lmpc_riccati.hpp (stage-wise interior-point body) for every instance; returns None when the controller is not
-    stage-wise.  Arguments as lmpc_solve."""
+    stage-wise.  Arguments as lmpc_solve.  cost_weights: refused (CopraUnsupported), as copra_batch_solve refuses them for this solver."""
+    ws = _set_weights(cost_weights)
+    try:
+        return _lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state, cost_refs, row_rhs, bounds)
+    finally:
+        del ws
+        _clear_weights()
+
+
+def _lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state, cost_refs, row_rhs, bounds):
     _sync_options()
     rr = None if row_rhs is None else np.ascontiguousarray(row_rhs, dtype=np.float64)
     lo = None if bounds is None else np.ascontiguousarray(bounds[0], dtype=np.float64)
@@ -180,6 +234,8 @@ def lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state=None, cost_re
                                       p(x0o) if x0o is not None else vp(), nc)
     if rc == -200:
         return None
+    if rc == _capi.COPRA_ERR_UNSUPPORTED:
+        raise _capi.CopraUnsupported("emu")
     if rc != 0:
         raise RuntimeError("emulator failed rc=%d" % rc)
     out = dict(control=u, trajectory=tr, status=st, iter=it, not_converged=nc[0], lds_resident=bool(nc[1]))
@@ -191,7 +247,17 @@ def lmpc_solve_riccati(A, B, d, x0, N, costs, cstrs, initial_state=None, cost_re
 WARM_CAP = 32  # plan.hpp::kWarmCap
 
 
-def lmpc_solve_shared(A, B, d, x0, N, costs, cstrs, warm=None, cost_refs=None):
+def lmpc_solve_shared(A, B, d, x0, N, costs, cstrs, warm=None, cost_refs=None, cost_weights=None):
+    """cost_weights: refused (CopraUnsupported): the shared model holds the creation weights (copra_batch_set_cost_weights)"""
+    ws = _set_weights(cost_weights)
+    try:
+        return _lmpc_solve_shared(A, B, d, x0, N, costs, cstrs, warm, cost_refs, bool(ws))
+    finally:
+        del ws
+        _clear_weights()
+
+
+def _lmpc_solve_shared(A, B, d, x0, N, costs, cstrs, warm, cost_refs, weighted):
     """shared-model fast path: ONE system (A, B, d), x0 of shape (batch, nx).  warm: int32 array (batch, WARM_CAP) kept by
     the caller across receding-horizon ticks (initialised to -1): the active set of the previous tick, shifted by one step.
     cost_refs: {cost_index: array (batch, rows)} per-instance references -- the records form with the pass in front only"""
@@ -221,6 +287,8 @@ def lmpc_solve_shared(A, B, d, x0, N, costs, cstrs, warm=None, cost_refs=None):
                                      warm.ctypes.data_as(C.POINTER(C.c_int)) if warm is not None else C.c_void_p())
     for k in range(8):
         lib().emu_set_cost_reference(k, C.c_void_p())
+    if rc == _capi.COPRA_ERR_UNSUPPORTED and weighted:
+        raise _capi.CopraUnsupported("emu")
     if rc != 0:
         raise RuntimeError("emulator failed rc=%d" % rc)
     return dict(control=u, trajectory=tr, status=st, iter=it, overflowed=sizes[0], riccati_factor=bool(sizes[1]), lane_pass_finished=sizes[2])

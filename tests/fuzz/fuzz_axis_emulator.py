@@ -1,5 +1,5 @@
 """Random controllers on the shapes of the (instance, axis)-per-lane solver (tests/random_controllers.py: make_integrator, make_chain3, make_chain1; now and then
-in axis-major state order, with a goal per instance) through the CPU wave emulator of the kernel bodies against the oracle: statuses, iteration
+in axis-major state order, with a goal per instance, with cost weights per instance) through the CPU wave emulator of the kernel bodies against the oracle: statuses, iteration
 counters, U and X.   python tests/fuzz/fuzz_axis_emulator.py [first_seed [count [batch]]]"""
 import os
 import sys
@@ -35,11 +35,24 @@ for seed in range(first, first + count):
     if plain_goal and rng.random() < 0.4:
         refs = {0: np.tile(c["costs"][0]["p"], (b, 1)) + 0.1 * rng.standard_normal((b, c["nx"]))}
         what.append("own goals")
-    re = pyemu.lmpc_solve(c["A"], c["B"], c["d"], c["x0"], c["N"], c["costs"], c["cstrs"], cost_refs=refs)
+    # weights per instance on a third of the controllers: log-uniform in [0.1, 10] x the creation weights, row by row (the headline's shape runs the
+    # solver's weight-reading builds, the other shapes and zero creation weights the generic tier: pyemu.last_axis_run() says which)
+    wts = None
+    if rng.random() < 0.33:
+        wts = {t: np.asarray(cs["weights"], dtype=float)[None, :] * np.exp(rng.uniform(np.log(0.1), np.log(10.0), (b, np.size(cs["weights"]))))
+               for t, cs in enumerate(c["costs"]) if cs.get("weights") is not None and cs["kind"] != "dense"
+               and np.size(cs["weights"]) == np.size(cs["p"]) and np.size(cs["p"]) in (c["nx"], c["nu"])}
+        what.append("own weights on %s" % sorted(wts))
+    re = pyemu.lmpc_solve(c["A"], c["B"], c["d"], c["x0"], c["N"], c["costs"], c["cstrs"], cost_refs=refs, cost_weights=wts)
+    run = pyemu.last_axis_run()
+    if wts:
+        what.append("builds %s" % (run["first"][0] if run else "generic"))
     bad = tie = 0
     worst = 0.0
     for k in range(b):
         costs = c["costs"] if refs is None else [dict(c["costs"][0], p=refs[0][k])] + c["costs"][1:]
+        if wts:
+            costs = [dict(cs, weights=wts[t][k]) if t in wts else cs for t, cs in enumerate(costs)]
         ro = pyoracle.lmpc_solve(c["A"][k], c["B"][k], c["d"][k], c["x0"][k], c["N"], costs, c["cstrs"])
         if re["status"][k] != ro["status"]:
             bad += 1
@@ -47,7 +60,11 @@ for seed in range(first, first + count):
         if ro["status"] != 0:
             continue
         tie += int(tuple(re["iter"][k]) != tuple(ro["iter"]))
-        worst = max(worst, rel(re["control"][k], ro["control"]), rel(re["trajectory"][k], ro["trajectory"]))
+        if wts:  # (scattered weights: norm-wise per instance, tests/cost_weights_cases.py::rel_inst)
+            worst = max(worst, np.abs(re["control"][k] - ro["control"]).max() / max(np.abs(ro["control"]).max(), 1e-3),
+                        np.abs(re["trajectory"][k] - ro["trajectory"]).max() / max(np.abs(ro["trajectory"]).max(), 1e-3))
+        else:
+            worst = max(worst, rel(re["control"][k], ro["control"]), rel(re["trajectory"][k], ro["trajectory"]))
     axis = re.get("lane_pass_finished", 0)
     naxis += int(axis > 0)
     flag = "   <<<<<<" if bad or worst > 1e-6 else ("   < counters" if tie else "")

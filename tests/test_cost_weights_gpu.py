@@ -13,11 +13,13 @@ import pytest
 
 from copra_amd._capi import OPTIONS
 
+import cost_weights_cases as W
+
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-6
-ABS_FLOOR = 1e-3
-K = 64
+RTOL = W.RTOL
+ABS_FLOOR = W.ABS_FLOOR
+K = W.K
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -33,38 +35,10 @@ def _engine(wl, batch, **kw):
     return eng
 
 
-def _grouped_weights(wl, batch, seed):
-    """per cost: (batch, rows) weights, log-uniform in [0.1, 10] x the creation weights, drawn from K vectors; and the group of each instance"""
-    rng = np.random.default_rng(seed)
-    group = rng.integers(0, K, batch)
-    ws = []
-    for c in wl["costs"]:
-        w0 = np.asarray(c["weights"], dtype=np.float64)
-        table = w0[None, :] * np.exp(rng.uniform(np.log(0.1), np.log(10.0), (K, w0.size)))
-        ws.append(table[group])
-    return ws, group
-
-
-def _oracle_grouped(oracle, wl, ws, group, **kw):
-    """the oracle's results for every instance, one oracle batch per group of instances that share their weights"""
-    batch = group.size
-    nx, nu, N = wl["B"].shape[1], wl["B"].shape[2], wl["N"]
-    out = dict(control=np.full((batch, nu * N), np.nan), trajectory=np.full((batch, nx * (N + 1)), np.nan),
-               status=np.zeros(batch, dtype=np.int32), iter=np.zeros((batch, 2), dtype=np.int32))
-    for g in np.unique(group):
-        idx = np.nonzero(group == g)[0]
-        costs = [dict(c, weights=w[idx[0]]) for c, w in zip(wl["costs"], ws)]
-        r = oracle.lmpc_solve_batch(wl["A"][idx], wl["B"][idx], wl["d"][idx], wl["x0"][idx], N, costs, wl["cstrs"], nthreads=8, **kw)
-        for k in out:
-            out[k][idx] = r[k]
-    return out
-
-
-def _rel_inst(a, b, floor=ABS_FLOOR):
-    """per instance (row), norm-wise: max_i |a_i - b_i| / max(max_i |b_i|, floor) -- the scattered weights (a ratio of up to 1e4 between
-    the state and the control weights) leave the oracle's own Goldfarb-Idnani arithmetic that far from the optimum in its small entries;
-    the parity suite's measure for comparisons set by the conditioning of the whole problem (tests/test_gpu_parity.py::_rel_vec)"""
-    return np.nanmax(np.nanmax(np.abs(a - b), axis=1) / np.maximum(np.nanmax(np.abs(b), axis=1), floor))
+# (inputs and measures shared with the CPU tests of the same paths: tests/cost_weights_cases.py)
+_grouped_weights = W.grouped_weights
+_oracle_grouped = W.oracle_grouped
+_rel_inst = W.rel_inst
 
 
 def _assert_matches(res, ref):
@@ -347,3 +321,231 @@ def test_cpp_mirror_hands_new_weights_to_its_handle(oracle):
     ref = pyoracle.lmpc_solve(pb["A"], pb["B"], pb["d"], pb["x0"], 12, [dict(pb["costs"][0], weights=w2)] + list(pb["costs"][1:]), pb["cstrs"])
     assert ref["status"] == 0
     assert _rel(u, ref["control"]) <= RTOL
+
+
+# ---- weights next to the other per-instance inputs, on the other builds of the (instance, axis)-per-lane solver, on ragged batches ----
+def _set_weights(eng, ws):
+    for t, w in enumerate(ws):
+        if w is not None:
+            eng.set_cost_weights(t, w)
+
+
+def test_weights_with_per_instance_references(oracle):
+    from copra_amd import workloads
+    b = 512
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=31)
+    ws, group = _grouped_weights(wl, b, 37)
+    goals = wl["costs"][0]["p"][None, :] + 0.3 * np.random.default_rng(21).standard_normal((K, 6))
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.set_cost_reference(0, goals[group])
+    eng.solve()
+    assert eng.axis_solver_ran()
+    _assert_matches(eng.results(), _oracle_grouped(oracle, wl, ws, group, costs_of=lambda k, costs: [dict(costs[0], p=goals[group[k]]), costs[1]]))
+
+
+def test_weights_with_per_instance_limits(oracle):
+    """every instance its own velocity limit (a TrajectoryConstraint's right-hand side) and actuator limits, the same along the horizon"""
+    from copra_amd import workloads
+    b = 512
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=13)
+    N = wl["N"]
+    vsel = np.hstack([np.zeros((3, 3)), np.eye(3)])
+    wl["cstrs"] = [dict(kind="trajectory", E=vsel, f=[0.5] * 3, ineq=True), wl["cstrs"][1]]
+    ws, group = _grouped_weights(wl, b, 41)
+    rng = np.random.default_rng(33)
+    vlim, ulim = (0.5 * rng.uniform(0.6, 1.3, K))[group], (2.5 * rng.uniform(0.6, 1.3, K))[group]
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.set_constraint_rhs(0, np.repeat(vlim[:, None], 3, axis=1))
+    eng.set_control_bounds(-np.repeat(ulim[:, None], 3 * N, axis=1), np.repeat(ulim[:, None], 3 * N, axis=1))
+    eng.solve()
+    assert eng.axis_solver_ran()
+    cstrs_of = lambda k: [dict(wl["cstrs"][0], f=[vlim[k]] * 3), dict(kind="control_bound", lower=[-ulim[k]] * 3, upper=[ulim[k]] * 3)]
+    _assert_matches(eng.results(), _oracle_grouped(oracle, wl, ws, group, cstrs_of=cstrs_of))
+
+
+@pytest.mark.parametrize("two_row", [False, True])
+def test_weights_with_a_reference_trajectory_cost(oracle, two_row):
+    """a reference-trajectory cost whose weights repeat along the horizon: the builds without the horizon compiled in"""
+    b = 512
+    wl = W.tracking(b, two_row=two_row)
+    ws, group = W.tracking_weights(wl, b, 31, groups=K)
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.solve()
+    assert eng.axis_solver_ran()
+    _assert_matches(eng.results(), _oracle_grouped(oracle, wl, ws, group))
+
+
+def test_setter_errors_for_a_reference_trajectory_cost():
+    """weights of a reference-trajectory cost that differ from step to step: COPRA_ERR_DOMAIN; device weights (not checked): COPRA_ERR_UNSUPPORTED"""
+    import torch
+    from copra_amd._capi import CopraDomainError, CopraUnsupported
+    b = 8
+    wl = W.tracking(b)
+    ws, _ = W.tracking_weights(wl, b, 31)
+    eng = _engine(wl, b)
+    eng.set_cost_weights(0, ws[0])  # (repeating: accepted)
+    bad = ws[0].copy()
+    bad[3, 6 * 5 + 2] *= 1.5
+    with pytest.raises(CopraDomainError):
+        eng.set_cost_weights(0, bad)
+    with pytest.raises(CopraUnsupported):
+        eng.set_cost_weights(0, torch.tensor(ws[0], dtype=torch.float64, device="cuda"))
+    eng.set_cost_weights(1, torch.tensor(ws[1], dtype=torch.float64, device="cuda"))  # (a per-step cost takes device weights)
+
+
+@pytest.mark.parametrize("name", ["two_rows", "two_rows_N12", "N12", "axis_major"])
+def test_other_weight_builds(oracle, name):
+    """two rows per axis and step, N = 12 and axis-major state order (tests/cost_weights_cases.py: axis_cases) at a few waves"""
+    from copra_amd import workloads
+    b = 700
+    wl = {"two_rows": lambda: W.two_rows(b), "two_rows_N12": lambda: W.two_rows(b, N=12),
+          "N12": lambda: workloads.com_preview(b, N=12, v_max=0.35, u_max=1.8, seed=23),
+          "axis_major": lambda: workloads.axis_major(workloads.com_preview(b, v_max=0.4, u_max=2.0, seed=17))}[name]()
+    eng, _ = _solve_with_weights(oracle, wl, b, seed=43)
+    ran, finished = eng.lane_pass_info()
+    assert eng.axis_solver_ran() and finished > 0
+
+
+@pytest.mark.parametrize("b", [1, 20, 21, 22, 64, 1000])
+def test_ragged_batches_solved_twice(oracle, b):
+    """one instance, a wave short of one, a full wave, an instance on the spare lanes, several waves: every instance's weights a function of its
+    number, every row another factor -- solved twice (the second solve after the engine's look at its workload)"""
+    from copra_amd import workloads
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=7)
+    ws, group = W.indexed_weights(wl, b)
+    if b > 64:  # (the factors grow with the instance's number: kept within the decade of the other tests)
+        ws, group = W.indexed_weights(wl, 64)
+        group = np.arange(b) % 64
+        ws = [w[group] for w in ws]
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    ref = _oracle_grouped(oracle, wl, ws, group)
+    for _ in range(2):
+        eng.solve()
+        assert eng.axis_solver_ran()
+        _assert_matches(eng.results(), ref)
+
+
+def test_second_launch_alone(oracle):
+    """a tight workload at 2048 instances: part of the batch ends in the solver's two launches, the rest in the tier -- on the first solve and
+    after the engine adapted"""
+    from copra_amd import workloads
+    b = 2048
+    wl = workloads.com_preview(b, v_max=0.25, u_max=1.2, seed=3)
+    ws, group = _grouped_weights(wl, b, 47)
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    ref = _oracle_grouped(oracle, wl, ws, group)
+    for _ in range(2):
+        eng.solve()
+        ran, finished = eng.lane_pass_info()
+        assert eng.axis_solver_ran() and 0 < finished < b
+        _assert_matches(eng.results(), ref)
+
+
+def _closed_loop(oracle, eng, wl, ws, group, ticks, w_seq, ref_of_tick=None):
+    """rollout(ticks) against an oracle loop from the device's own states, with the same weights (and the reference window of the tick)"""
+    hist = eng.rollout(ticks, disturbances=w_seq, x_hist=True, u_hist=True, status_hist=True)
+    xh, uh, sh = (hist[k].cpu().numpy() for k in ("x_hist", "u_hist", "status_hist"))
+    assert eng.axis_solver_ran()
+    for t in range(ticks):
+        step = dict(wl, x0=xh[t])
+        costs_of = None if ref_of_tick is None else (lambda k, costs: [dict(costs[0], p=ref_of_tick(t, k)), costs[1]])
+        ro = _oracle_grouped(oracle, step, ws, group, costs_of=costs_of)
+        assert np.array_equal(sh[t], ro["status"]) and (sh[t] == 0).all(), t
+        e = _rel_inst(uh[t], ro["control"][:, :3])
+        print("tick %d: first control against the oracle, norm-wise %.2e" % (t, e))
+        assert e <= RTOL, t
+        xn = np.einsum("bij,bj->bi", wl["A"], xh[t]) + np.einsum("bij,bj->bi", wl["B"], uh[t]) + wl["d"] + w_seq[t]
+        assert np.abs(xh[t + 1] - xn).max() <= 1e-12
+
+
+def test_rollout_with_weights(oracle):
+    from copra_amd import workloads
+    import tracking_cases as tc
+    b, ticks = 256, 5
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=51)
+    ws, group = _grouped_weights(wl, b, 53, groups=8)
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    _closed_loop(oracle, eng, wl, ws, group, ticks, tc.position_noise(ticks, b, 6, 3, seed=21))
+
+
+def test_rollout_on_a_reference_schedule_with_weights(oracle):
+    """the tracking controller of tests/tracking_cases.py, one schedule per instance, weights that repeat along the horizon"""
+    import tracking_cases as tc
+    b, ticks = 256, 5
+    wl, signals = tc.tracking_workload(batch=b)
+    N = wl["N"]
+    sig = tc.group_of(b, True)
+    ws, wgroup = W.tracking_weights(wl, b, 57, groups=2)
+    group = 2 * sig + wgroup  # (instances that share signal and weights)
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.set_reference_schedule(0, np.ascontiguousarray(signals[sig]), tc.NX)
+    _closed_loop(oracle, eng, wl, ws, group, ticks, tc.position_noise(ticks, b, 6, 3, seed=22),
+                 ref_of_tick=lambda t, k: tc.window(signals[sig[k]], t, N + 1))
+
+
+# ---- accuracy against the certified optimum ----
+def _truth_distances(wl, ws, res, ref, picks):
+    import truth
+    dev = ora = 0.0
+    for k in picks:
+        costs = [dict(c, weights=w[k]) for c, w in zip(wl["costs"], ws)]
+        t = truth.solve(wl["A"][k], wl["B"][k], wl["d"][k], wl["x0"][k], wl["N"], costs, wl["cstrs"], ref["control"][k])
+        dev = max(dev, _rel(res["control"][k], t["control"]), _rel(res["trajectory"][k], t["trajectory"]))
+        ora = max(ora, _rel(ref["control"][k], t["control"]), _rel(ref["trajectory"][k], t["trajectory"]))
+    return dev, ora
+
+
+@pytest.mark.parametrize("f0", [1e-4, 1.0, 1e4])
+@pytest.mark.parametrize("f1", [1e-4, 1.0, 1e4])
+def test_scaled_weights_against_the_certified_optimum(oracle, f0, f1):
+    """weights at the creation weights x {1e-4, 1, 1e4} per cost, 64 instances: the device against the extended-precision certified optimum
+    (tests/truth.py), entry by entry, next to the oracle's own distance on the same instances.  Bound: 10 x the oracle's distance or RTOL,
+    whichever is larger -- the factor covers the cancellation in H0 + (w - w0) c c', whose error grows as eps w0 / w."""
+    from copra_amd import workloads
+    b = 64
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=61)
+    ws = [np.tile(f * np.asarray(c["weights"], dtype=np.float64), (b, 1)) for f, c in zip((f0, f1), wl["costs"])]
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.solve()
+    res = eng.results()
+    ref = _oracle_grouped(oracle, wl, ws, np.zeros(b, dtype=int))
+    assert eng.axis_solver_ran()
+    assert np.array_equal(res["status"], ref["status"]) and (ref["status"] == 0).sum() >= b - 1
+    dev, ora = _truth_distances(wl, ws, res, ref, np.nonzero(ref["status"] == 0)[0])
+    print("weights x (%g, %g): distance from the certified optimum (entry-wise, floor 1e-3): device %.2e | oracle %.2e" % (f0, f1, dev, ora))
+    assert dev <= max(10.0 * ora, RTOL), (dev, ora)
+
+
+def test_zero_instance_weight_on_single_rows(oracle):
+    """a zero weight per instance on one row whose creation weight is not zero (w / w0 = 0: the lane takes the row's whole term out of H):
+    the oracle's statuses; results where the oracle itself is within RTOL of the certified optimum"""
+    from copra_amd import workloads
+    b = 64
+    wl = workloads.com_preview(b, v_max=0.5, u_max=2.5, seed=67)
+    ws = [np.tile(np.asarray(c["weights"], dtype=np.float64), (b, 1)) for c in wl["costs"]]
+    for k in range(b):  # (instance k: row k % 6 of the trajectory cost)
+        ws[0][k, k % 6] = 0.0
+    group = np.arange(b) % 6
+    eng = _engine(wl, b)
+    _set_weights(eng, ws)
+    eng.solve()
+    res = eng.results()
+    ref = _oracle_grouped(oracle, wl, ws, group)
+    assert eng.axis_solver_ran()
+    assert np.array_equal(res["status"], ref["status"])
+    compared = 0
+    for k in np.nonzero(ref["status"] == 0)[0]:
+        dev, ora = _truth_distances(wl, ws, res, ref, [k])
+        if ora <= RTOL:
+            compared += 1
+            assert _rel(res["control"][k], ref["control"][k]) <= RTOL and _rel(res["trajectory"][k], ref["trajectory"][k]) <= RTOL, (k, dev, ora)
+    print("zero instance weights: %d of %d instances compared (oracle within RTOL of the certified optimum)" % (compared, b))
+    assert compared >= b // 2

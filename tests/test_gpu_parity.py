@@ -3158,3 +3158,25 @@ def test_first_tier_grid_follows_the_lists_and_the_second_launch_catches_what_ou
     assert (res["status"] == 0).all()
     assert (res["status"][pick] == ref["status"]).all() and (res["iter"][pick] == ref["iter"]).all()
     assert _rel(res["control"][pick], ref["control"]) <= RTOL and _rel(res["trajectory"][pick], ref["trajectory"]) <= RTOL
+
+
+def test_axis_trip_bounds_cases_on_the_device(oracle):
+    """the trips of the (instance, axis)-per-lane solver bounded by the wave's active set (lmpc_axis.hpp), compiled for the device: the five
+    normal-mode cases of tests/golden/gen_axis_trip_bounds.py -- status and both counters equal to the arrays recorded from the emulated body
+    (tests/golden/axis_trip_bounds.npz), U and X within 1e-9 of them (the compiler contracts multiply-adds on the device: not the same bits),
+    and the oracle's results at RTOL"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import gen_axis_trip_bounds as G
+    golden = np.load(G.PATH)
+    for name, (wl, two_slot) in sorted(G.cases().items()):
+        if two_slot:
+            continue
+        b = len(wl["x0"])
+        eng, res, ref = _check(wl, b, oracle)
+        assert eng.axis_solver_ran(), name
+        ok = ref["status"] == 0
+        assert ok.sum() >= b - 1 and (res["iter"][ok] == ref["iter"][ok]).all(), name
+        assert np.array_equal(res["status"], golden[name + "/status"]) and np.array_equal(res["iter"][ok], golden[name + "/iter"][ok]), name
+        eu, ex = _rel(res["control"][ok], golden[name + "/control"][ok]), _rel(res["trajectory"][ok], golden[name + "/trajectory"][ok])
+        print("%s: against the emulated body's recorded arrays U %.2e, X %.2e" % (name, eu, ex))
+        assert eu <= 1e-9 and ex <= 1e-9, (name, eu, ex)
