@@ -1,7 +1,7 @@
 // axis_builds.hpp -- the builds of the one-(instance, axis)-per-lane solver (lmpc_axis.hpp) and the rule that picks a controller's.  One list,
 // read by the translation units that instantiate the builds (copra_hip_axis*.hip: each its own entries), by the library that launches them
 // (copra_hip.hip: select_axis_kernel, select_axis_list_kernel) and by the CPU emulator that runs their bodies (tests/emu/emu_harness.cpp).
-// Host code only.
+// Host code only.  (The builds of the other tiers: tier_builds.hpp; whether the solver runs at all: front_end.hpp, axis_solver_covers.)
 #pragma once
 #include "plan_builder.hpp" // axis_solver_nmax, kAxisQmax, kAxisQmaxBig
 

@@ -8,6 +8,7 @@
 #include "lmpc_large.hpp"
 #include "lmpc_riccati.hpp"
 #include "lmpc_riccati_mfma.hpp"
+#include "front_end.hpp" // axis_builds.hpp, tier_builds.hpp: the builds the library holds, and which of them a controller runs
 #include "lmpc_shared.hpp"
 
 #include <algorithm>
@@ -58,19 +59,12 @@ __global__ __launch_bounds__(64, 2) void copra_lmpc_fused_tri_kernel(const Fused
 #include "ric_kernels.hpp" // copra_lmpc_fused_ric_kernel, copra_lmpc_lane_kernel
 #include "axis_kernels.hpp" // copra_lmpc_axis*_kernel: the builds of axis_builds.hpp, instantiated in copra_hip_axis*.hip
 COPRA_AXIS_BUILDS(COPRA_AXIS_DECL)
-// run-time-horizon builds (NH == 0) for the shapes of ric_aot_shape: instantiated in copra_hip_ric.hip, a translation unit of its own
-#define COPRA_RIC_RT_DECL(NX, NU)                                                                                      \
-    extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, false>(const FusedPlan);      \
-    extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, 0, false>(const FusedPlan);                 \
-    extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, true>(const FusedPlan);       \
-    extern template __global__ void copra_lmpc_fused_ric_kernel<NX, NU, 0, 0, true>(const FusedPlan);
-COPRA_RIC_RT_DECL(6, 3)
-COPRA_RIC_RT_DECL(4, 2)
-COPRA_RIC_RT_DECL(2, 1)
-extern template __global__ void copra_lmpc_lane_kernel<4, 2, false, true>(const FusedPlan);
-extern template __global__ void copra_lmpc_lane_kernel<4, 2, true, true>(const FusedPlan);
-extern template __global__ void copra_lmpc_lane_kernel<4, 2, false, false>(const FusedPlan);
-extern template __global__ void copra_lmpc_lane_kernel<4, 2, true, false>(const FusedPlan);
+// the builds of tier_builds.hpp that copra_hip_ric.hip, a translation unit of its own, instantiates: the Riccati-factor tier at the run-time horizon
+// (NH == 0) for the shapes of ric_aot_shape, and the pass of (4, 2)
+#define COPRA_FIRST_EXTERN(UNIT, KIND, ...) COPRA_UNIT_##UNIT(extern template, COPRA_FIRST_KERNEL_##KIND(__VA_ARGS__))
+#define COPRA_LANE_EXTERN(UNIT, ...) COPRA_UNIT_##UNIT(extern template, COPRA_LANE_KERNEL(__VA_ARGS__))
+COPRA_FIRST_TIER_BUILDS(COPRA_FIRST_EXTERN)
+COPRA_LANE_BUILDS(COPRA_LANE_EXTERN)
 // ... and its shared-model form: the stage records are those of the whole batch (wave-uniform: scalar operands), only the roll-out
 // from each instance's x0 is left
 template <int NX, int NU, bool SPEC = true>
@@ -125,74 +119,37 @@ __global__ __launch_bounds__(64) void copra_lmpc_shared_tier2_kernel(const Fused
     }
 }
 
-
-
-
-static fused_kernel_t select_shared_kernel(const FusedPlan& P, bool tier2)
-{
-    if (P.lds.tri && !tier2) {
-        if (P.nx == 6 && P.nu == 3 && P.N == 20) return copra_lmpc_shared_tri_kernel<6, 3, 20>;
-        return copra_lmpc_shared_tri_kernel<0, 0, 0>;
-    }
-    if (P.nx == 6 && P.nu == 3 && P.N == 20)
-        return tier2 ? copra_lmpc_shared_tier2_kernel<6, 3, 20> : copra_lmpc_shared_kernel<6, 3, 20>;
-    if (P.nx == 2 && P.nu == 1 && P.N == 10)
-        return tier2 ? copra_lmpc_shared_tier2_kernel<2, 1, 10> : copra_lmpc_shared_kernel<2, 1, 10>;
-    if (!tier2 && (size_t)P.lds.total * sizeof(double) * 9 <= 160u * 1024u) return copra_lmpc_shared_kernel_w4;
-    return tier2 ? copra_lmpc_shared_tier2_kernel<0, 0, 0> : copra_lmpc_shared_kernel<0, 0, 0>;
-}
-// the BASELINE.json shapes get their own instantiation
-fused_kernel_t select_fused_kernel(const FusedPlan& P)
-{
-    const int rp = specialised_cost_rows(P.nx, P.nu, P.N, P.rmax, P.rfull);
-    if (P.lds.tri) {
-        if (P.lds.ric && !ric_aot_exact(P.nx, P.nu, P.N)) { // run-time-horizon builds of the shape (copra_hip_ric.hip)
-#define COPRA_RIC_RT_PICK(NX, NU)                                                                                      \
-    if (P.nx == NX && P.nu == NU)                                                                                      \
-        return P.stage_refs ? (P.lds.q1regs ? copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, true> : copra_lmpc_fused_ric_kernel<NX, NU, 0, 0, true>) \
-                            : (P.lds.q1regs ? copra_lmpc_fused_ric_kernel<NX, NU, 0, kFusedQ1Regs, false> : copra_lmpc_fused_ric_kernel<NX, NU, 0, 0, false>);
-            COPRA_RIC_RT_PICK(6, 3)
-            COPRA_RIC_RT_PICK(4, 2)
-            COPRA_RIC_RT_PICK(2, 1)
-#undef COPRA_RIC_RT_PICK
-        }
-        if (P.lds.ric) { // (plan_builder.hpp: only these shapes get the layout; Q1 in registers, or in LDS further down the ladder)
-            if (P.stage_refs) { // (reference trajectories: the builds with the stage-varying affine term)
-                if (P.N == 10) return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 10, kFusedQ1Regs, true> : copra_lmpc_fused_ric_kernel<6, 3, 10, 0, true>;
-                if (P.N == 15) return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 15, kFusedQ1Regs, true> : copra_lmpc_fused_ric_kernel<6, 3, 15, 0, true>;
-                return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 20, kFusedQ1Regs, true> : copra_lmpc_fused_ric_kernel<6, 3, 20, 0, true>;
-            }
-            if (P.N == 10) return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 10, kFusedQ1Regs> : copra_lmpc_fused_ric_kernel<6, 3, 10, 0>;
-            if (P.N == 15) return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 15, kFusedQ1Regs> : copra_lmpc_fused_ric_kernel<6, 3, 15, 0>;
-            return P.lds.q1regs ? copra_lmpc_fused_ric_kernel<6, 3, 20, kFusedQ1Regs> : copra_lmpc_fused_ric_kernel<6, 3, 20, 0>;
-        }
-        if (P.nx == 6 && rp == 6 && P.lds.q1regs == kFusedQ1Regs) return copra_lmpc_fused_tri_kernel<6, 3, 20, 6, kFusedQ1Regs>;
-        if (P.nx == 6 && rp == 6) return copra_lmpc_fused_tri_kernel<6, 3, 20, 6>;
-        if (P.rfull > 0 && P.nx == 6 && P.nu == 3 && P.N == 20) // headline shape, full-size costs
-            return P.lds.q1regs == kFusedQ1Regs ? copra_lmpc_fused_tri_kernel<6, 3, 20, 0, kFusedQ1Regs> : copra_lmpc_fused_tri_kernel<6, 3, 20, 0>;
-        return copra_lmpc_fused_tri_kernel<0, 0, 0, 0>;
-    }
-    if (P.nx == 6 && rp == 6) return copra_lmpc_fused_kernel<6, 3, 20, 6>;
-    if (P.nx == 2 && rp == 2) return copra_lmpc_fused_kernel<2, 1, 10, 2>;
-    if (P.rfull > 0 && P.nx == 6 && P.nu == 3 && P.N == 20) return copra_lmpc_fused_kernel<6, 3, 20, 0>; // headline shape, full-size costs
-    if ((size_t)P.lds.total * sizeof(double) * 9 <= 160u * 1024u) return copra_lmpc_fused_kernel_w4; // > 8 per CU
-    return copra_lmpc_fused_kernel<0, 0, 0, 0>;
-}
-fused_kernel_t select_tier2_kernel(const FusedPlan& P)
-{
-    const int rp = specialised_cost_rows(P.nx, P.nu, P.N, P.rmax, P.rfull);
-    if (P.nx == 6 && rp == 6) return copra_lmpc_fused_tier2_kernel<6, 3, 20, 6>;
-    if (P.nx == 2 && rp == 2) return copra_lmpc_fused_tier2_kernel<2, 1, 10, 2>;
-    if (P.rfull > 0 && P.nx == 6 && P.nu == 3 && P.N == 20) return copra_lmpc_fused_tier2_kernel<6, 3, 20, 0>;
-    return copra_lmpc_fused_tier2_kernel<0, 0, 0, 0>;
-}
-
+// The builds of tier_builds.hpp and their kernels: k<List>Kernels[k] runs k<List>Builds[k]; a selector is the list's pick and that index
+#define COPRA_FIRST_KERNEL_tri(NX, NU, NH, RP, QR, SREFS) copra_lmpc_fused_tri_kernel<NX, NU, NH, RP, QR>
+#define COPRA_FIRST_KERNEL_square(NX, NU, NH, RP, QR, SREFS) copra_lmpc_fused_kernel<NX, NU, NH, RP>
+#define COPRA_FIRST_KERNEL_w4(NX, NU, NH, RP, QR, SREFS) copra_lmpc_fused_kernel_w4
+#define COPRA_SHARED_KERNEL_tri(NX, NU, NH) copra_lmpc_shared_tri_kernel<NX, NU, NH>
+#define COPRA_SHARED_KERNEL_first(NX, NU, NH) copra_lmpc_shared_kernel<NX, NU, NH>
+#define COPRA_SHARED_KERNEL_w4(NX, NU, NH) copra_lmpc_shared_kernel_w4
+#define COPRA_SHARED_KERNEL_tier2(NX, NU, NH) copra_lmpc_shared_tier2_kernel<NX, NU, NH>
+#define COPRA_FIRST_PTR(UNIT, KIND, ...) COPRA_FIRST_KERNEL_##KIND(__VA_ARGS__),
+#define COPRA_SECOND_PTR(UNIT, ...) copra_lmpc_fused_tier2_kernel<__VA_ARGS__>,
+#define COPRA_LANE_PTR(UNIT, ...) COPRA_LANE_KERNEL(__VA_ARGS__),
+#define COPRA_LANE_SHARED_PTR(UNIT, ...) copra_lmpc_lane_shared_kernel<__VA_ARGS__>,
+#define COPRA_SHARED_PTR(UNIT, KIND, ...) COPRA_SHARED_KERNEL_##KIND(__VA_ARGS__),
+static const fused_kernel_t kFirstTierKernels[] = { COPRA_FIRST_TIER_BUILDS(COPRA_FIRST_PTR) };
+static const fused_kernel_t kSecondTierKernels[] = { COPRA_SECOND_TIER_BUILDS(COPRA_SECOND_PTR) };
+static const fused_kernel_t kLaneKernels[] = { COPRA_LANE_BUILDS(COPRA_LANE_PTR) };
+static const fused_kernel_t kLaneSharedKernels[] = { COPRA_LANE_SHARED_BUILDS(COPRA_LANE_SHARED_PTR) };
+static const fused_kernel_t kSharedKernels[] = { COPRA_SHARED_BUILDS(COPRA_SHARED_PTR) };
+template <size_t K>
+static fused_kernel_t kernel_of(const TierBuild (&builds)[K], const fused_kernel_t (&kernels)[K], const TierBuild* b) { return b ? kernels[b - builds] : nullptr; }
+fused_kernel_t select_fused_kernel(const FusedPlan& P) { return kernel_of(kFirstTierBuilds, kFirstTierKernels, pick_first_tier(P)); }
+fused_kernel_t select_tier2_kernel(const FusedPlan& P) { return kernel_of(kSecondTierBuilds, kSecondTierKernels, pick_second_tier(P)); }
+static fused_kernel_t select_shared_kernel(const FusedPlan& P, bool tier2) { return kernel_of(kSharedBuilds, kSharedKernels, pick_shared(P, tier2)); }
+// ... the one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp) and its shared-model form; nullptr: no build for the shape
+static fused_kernel_t select_lane_kernel(const FusedPlan& P) { return kernel_of(kLaneBuilds, kLaneKernels, pick_lane(P)); }
+static fused_kernel_t select_lane_shared_kernel(const FusedPlan& P) { return kernel_of(kLaneSharedBuilds, kLaneSharedKernels, pick_lane_shared(P)); }
 
 __global__ __launch_bounds__(64) void copra_islmpc_fused_kernel(const FusedPlan P)
 {
     islmpc_fused_body(P, P.inst_offset + (int)blockIdx.x);
 }
-
 
 // more than 64 decision variables: one MPC instance per workgroup (lmpc_large.hpp), persistent grid over the batch
 __global__ __launch_bounds__(kLargeMaxN) void copra_lmpc_large_kernel(const FusedPlan P) { lmpc_large_body(P); }
@@ -225,7 +182,6 @@ static riccati_kernel_t select_riccati_kernel(int nx, int nu)
     if (nx == 2 && nu == 1) return copra_lmpc_riccati_kernel<2, 1>;
     return copra_lmpc_riccati_kernel<0, 0>;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -293,8 +249,6 @@ hipError_t lds_opt_in(const void* fn, size_t bytes)
     if (e == hipSuccess) granted[fn] = bytes;
     return e;
 }
-
-
 
 FusedPlan device_plan(const copra_batch* h)
 {
@@ -417,35 +371,7 @@ static hipError_t launch(K kernel, unsigned grid, unsigned threads, size_t lds, 
     return launch_timed(false, nullptr, nullptr, kernel, grid, threads, lds, s, args...);
 }
 
-// ---- the one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp) ----
-static fused_kernel_t select_lane_kernel(const FusedPlan& P)
-{
-    // <NX, NU, reference trajectories, takes the first steps of the iteration itself (FusedPlan::lane_spec)>
-#define COPRA_LANE_PICK(NX, NU)                                                                                                                   \
-    if (P.nx == NX && P.nu == NU)                                                                                                                  \
-        return P.lane_spec ? (P.stage_refs ? copra_lmpc_lane_kernel<NX, NU, true, true> : copra_lmpc_lane_kernel<NX, NU, false, true>)            \
-                           : (P.stage_refs ? copra_lmpc_lane_kernel<NX, NU, true, false> : copra_lmpc_lane_kernel<NX, NU, false, false>);
-    COPRA_LANE_PICK(6, 3) // (the CoM system)
-    COPRA_LANE_PICK(2, 1) // (the reference's falling-mass system: BASELINE configs[1])
-    COPRA_LANE_PICK(4, 2) // (a planar point mass; copra_hip_ric.hip)
-#undef COPRA_LANE_PICK
-    return nullptr;
-}
-static fused_kernel_t select_lane_shared_kernel(const FusedPlan& P)
-{
-    if (P.nx == 6 && P.nu == 3) return P.lane_spec ? copra_lmpc_lane_shared_kernel<6, 3, true> : copra_lmpc_lane_shared_kernel<6, 3, false>;
-    if (P.nx == 4 && P.nu == 2) return P.lane_spec ? copra_lmpc_lane_shared_kernel<4, 2, true> : copra_lmpc_lane_shared_kernel<4, 2, false>; // (the other shapes of the tier's run-time-horizon builds)
-    if (P.nx == 2 && P.nu == 1) return P.lane_spec ? copra_lmpc_lane_shared_kernel<2, 1, true> : copra_lmpc_lane_shared_kernel<2, 1, false>;
-    return nullptr;
-}
 // ---- the one-(instance, axis)-per-lane solver (lmpc_axis.hpp): the whole solve of a controller whose axes are decoupled ----
-// per-instance cost weights in the launch's plan (copra_batch_set_cost_weights): only the builds that read them may run
-static bool plan_has_weights(const FusedPlan& P)
-{
-    for (int t = 0; t < kMaxCosts; ++t)
-        if (P.cost_w[t]) return true;
-    return false;
-}
 // The build the controller gets (axis_builds.hpp: pick_axis_build) and its kernel: kAxisKernels[k] runs kAxisBuilds[k]
 #define COPRA_AXIS_PTR(UNIT, FAMILY, ...) COPRA_AXIS_KERNEL_##FAMILY(__VA_ARGS__),
 static const fused_kernel_t kAxisKernels[] = { COPRA_AXIS_BUILDS(COPRA_AXIS_PTR) };
@@ -468,35 +394,13 @@ static size_t axis_lds_bytes(const FusedPlan& P)
     int oB = 0, oR = 0, rcs = 0;
     return (size_t)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs) * sizeof(double);
 }
+// does the next solve run it?  What the plan and its inputs decide: front_end.hpp, axis_solver_covers; here what is state of the handle
 static bool axis_solver_wanted(const copra_batch* h, const FusedPlan& P)
 {
     const copra_options_t& opt = h->hp.opt;
-    if (own_weights(h)) { // per-instance weights: only where BOTH the solver and its second chance run builds that read them (lmpc_axis.hpp, WTS) --
-        // a lane rebuilds its tables from the coefficients of FusedPlan::axis_cref divided by the creation weight, which must be non-zero, and
-        // the cost's weights must repeat along the horizon (a reference-trajectory cost: the kernels read the first step's)
-        if (P.axis_cref < 0 || !select_axis_kernel(P) || !select_axis_list_kernel(P)) return false;
-        for (int t = 0; t < P.ncost; ++t) {
-            if (!h->cost_w[t]) continue;
-            const CostTerm& ct = P.cost[t];
-            if (ct.full) return false;
-            for (int r = 0; r < ct.rows; ++r)
-                if (h->hp.params[(size_t)ct.offW + r] == 0.0) return false;
-        }
-    }
-    if (h->ad.axis_off || opt.no_axis_solver || opt.no_lane_pass || P.axis_tab < 0 || P.prof_fine) return false;
+    if (h->ad.axis_off || P.prof_fine || h->packed || h->shared) return false;
     if (opt.lane_min_batch > 0 && P.batch < opt.lane_min_batch) return false;
-    if (h->packed || h->shared || h->hp.large || P.initial_state) return false;
-    // (per-instance limits: the builds that keep bounds and right-hand sides in registers take this lane's own -- where they are the same
-    //  along the horizon, else the instance goes to the tier: lmpc_axis.hpp)
-    if ((P.row_f_inst || P.lb_inst || P.ub_inst) && (!P.axis_const || (P.lb_inst == nullptr) != (P.ub_inst == nullptr))) return false;
-    for (int t = 0; t < kMaxCosts; ++t) // (per-instance references: a lane rebuilds the affine terms of its axis from them -- FusedPlan::axis_cref)
-        if (h->cost_p[t] && (P.axis_cref < 0 || t >= P.ncost)) return false;
-    if (P.stage_refs) { // reference trajectories: the stages' h wait in the lane's sparse array for the sweep (lmpc_axis.hpp)
-        int oB = 0, oR = 0, rcs = 0;
-        (void)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs);
-        if (P.axis_cref < 0 || P.N * (P.nx / P.nu + 1) > rcs) return false;
-    }
-    return select_axis_kernel(P) != nullptr;
+    return axis_solver_covers(h->hp, P);
 }
 static size_t lane_lds_bytes(const FusedPlan& P)
 {
@@ -520,15 +424,9 @@ static bool lane_batch_ok(const copra_options_t& opt, int batch, bool ric_tier, 
 }
 static bool lane_pass_wanted(const copra_batch* h, const FusedPlan& P, bool jit_launch)
 {
-    const copra_options_t& opt = h->hp.opt;
-    if (own_weights(h)) return false; // (its tables hold the creation weights)
-    if (h->ad.lane_off || opt.no_lane_pass || !lane_batch_ok(opt, P.batch, P.lds.ric != 0)) return false;
+    if (h->ad.lane_off || !lane_batch_ok(h->hp.opt, P.batch, P.lds.ric != 0)) return false;
     if (P.prof_fine) return false; // (the fine-grained stamps of the profiling build follow ONE kernel through a whole solve)
-    // (in front of the Riccati-factor tier, which takes the factor over, or of any other one-wave first tier, where it only filters)
-    if (P.lane_tab < 0 || (jit_launch && !h->jit_ric) || h->packed || h->shared || h->hp.large || P.initial_state) return false;
-    for (int t = 0; t < kMaxCosts; ++t)
-        if (h->cost_p[t] && P.lane_cref < 0) return false; // (per-instance references: the pass rebuilds its affine terms per lane)
-    if (P.stage_refs && P.lane_cref < 0) return false; // (reference trajectories: ... per lane and stage)
+    if ((jit_launch && !h->jit_ric) || h->packed || h->shared || !lane_pass_covers(h->hp, P)) return false; // (front_end.hpp: what the plan and its inputs decide)
     return (jit_launch ? h->jit_lane != nullptr : select_lane_kernel(P) != nullptr);
 }
 static copra_status_t ensure_lane_buffers(copra_batch* h, bool need_ws)
@@ -1036,15 +934,10 @@ extern "C" {
 
 int copra_abi_version(void) { return 8; } // 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
-
-
-
-
 const char* copra_last_error(void) { return g_copra_err.c_str(); }
 
 // (copra_source_hash: copra_hip_hash.hip -- a translation unit of its own that is compiled again whenever ANY source of the library changes;
 //  compiled into this one it went stale whenever make rebuilt only another unit, and bench.py's roofline.traffic_stale said so)
-
 
 static copra_status_t create_common(copra_batch_t** out, const copra_dims_t* dims, int n_costs,
     const copra_cost_desc_t* costs, int n_cstrs, const copra_cstr_desc_t* cstrs, const copra_initial_state_desc_t* is,
@@ -1228,10 +1121,6 @@ void copra_batch_destroy(copra_batch_t* h)
     if (h->ev_plant) (void)hipEventDestroy(h->ev_plant);
     delete h;
 }
-
-
-
-
 
 copra_status_t copra_plan_check(const copra_dims_t* dims, int n_costs, const copra_cost_desc_t* costs, int n_cstrs,
     const copra_cstr_desc_t* cstrs, const copra_initial_state_desc_t* is)
@@ -1520,18 +1409,6 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
     return COPRA_OK;
 }
 
-
-
-
-
-
-
-
-
-
-
-
-
 // ---- copra_batch_solve: ONE function per launch path (round-4 verdict: it was one 335-line function with eight paths and four adaptive
 //      controllers inline).  What the engine has learnt about the controller lives in AdaptState (engine.hpp); the controllers run in
 //      learn_from_the_last_solve, before anything of the next solve is chosen. ----
@@ -1728,22 +1605,21 @@ static copra_status_t solve_initial_state(copra_batch* h, FusedPlan& P, hipStrea
     return end_of_solve(h, s);
 }
 
-// Per-instance weights (own_weights): the Riccati-factor tier reads its stage costs from tables the plan builder weighted with the creation
-// weights, so a controller that has them runs the layout that tier's ladder ends on (adapt_layout: the compact or the full layout of the
-// generic one-wave kernels, which evaluate the costs per instance) -- and gets the layout it had back once the weights are restored, so that a
-// restored controller runs the same kernels as before.
+// Per-instance weights (own_weights): a controller on the Riccati-factor tier runs the layout of front_end.hpp's weights_layout while it has them --
+// and gets the layout it had back once the weights are restored, so that a restored controller runs the same kernels as before.
 static void weights_route(copra_batch* h)
 {
     const bool own = own_weights(h);
-    if (own && !h->wt_saved && h->hp.plan.lds.ric && !h->hp.large && !h->hp.plan.initial_state) {
+    WeightsLayout w {};
+    if (own && !h->wt_saved && weights_layout(h->hp, w)) {
         h->wt_saved = true;
         h->wt_lds = h->hp.plan.lds;
         h->wt_two_tier = h->hp.two_tier;
         h->wt_dense = h->hp.dense;
         h->wt_packed = h->packed;
-        h->hp.two_tier = h->hp.dense && h->hp.safe_two_tier && !h->hp.lds_safe.ric;
-        h->hp.dense = false;
-        set_layout(h, h->hp.two_tier ? h->hp.lds_safe : h->hp.lds_full, true);
+        h->hp.two_tier = w.two_tier;
+        h->hp.dense = w.dense;
+        set_layout(h, w.lds, true);
     } else if (!own && h->wt_saved) {
         h->wt_saved = false;
         set_layout(h, h->wt_lds, false); // (its size in bytes is the layout's total everywhere a layout is set)

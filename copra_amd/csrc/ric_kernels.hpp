@@ -1,10 +1,11 @@
 // ric_kernels.hpp -- the __global__ templates of the Riccati-factor tier and of the one-instance-per-lane pass, shared by the translation
 // units that instantiate them: copra_hip.hip (compile-time horizons of the BASELINE shapes) and copra_hip_ric.hip (run-time horizon,
-// NH == 0, for the shapes of plan_builder.hpp::ric_aot_shape).
+// NH == 0, for the shapes of plan_builder.hpp::ric_aot_shape) -- each the entries of tier_builds.hpp with its UNIT.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "lmpc_fused_ric.hpp"
+#include "tier_builds.hpp"
 #include "lmpc_lane.hpp"
 
 using namespace copra_hip;
@@ -28,3 +29,9 @@ __global__ __launch_bounds__(64, 1) void copra_lmpc_lane_kernel(const FusedPlan 
 {
     lmpc_lane_body<NX, NU, SREFS, SPEC>(P, (int)blockIdx.x);
 }
+// the kernel of an entry of COPRA_FIRST_TIER_BUILDS (KIND ric) and of COPRA_LANE_BUILDS, and -- SPEC: template, or extern template -- what a
+// translation unit says of the entries whose UNIT is ric: copra_hip_ric.hip instantiates them, copra_hip.hip declares them
+#define COPRA_FIRST_KERNEL_ric(NX, NU, NH, RP, QR, SREFS) copra_lmpc_fused_ric_kernel<NX, NU, NH, QR, SREFS>
+#define COPRA_LANE_KERNEL(NX, NU, SREFS, SPEC) copra_lmpc_lane_kernel<NX, NU, SREFS, SPEC>
+#define COPRA_UNIT_core(SPEC, ...)
+#define COPRA_UNIT_ric(SPEC, ...) SPEC __global__ void __VA_ARGS__(const FusedPlan);

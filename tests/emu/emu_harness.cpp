@@ -1,8 +1,11 @@
 // tests/emu/emu_harness.cpp -- runs the HIP kernel BODIES on the CPU, one fiber per lane (TEST INFRASTRUCTURE ONLY).
 // See wave_prims.hpp in this directory.  Exposes a tiny C interface for ctypes.
+// WHICH body runs, and on which route, is the library's own decision: the builds and their picks come from axis_builds.hpp and tier_builds.hpp, the
+// front ends' conditions and the weights' layout from front_end.hpp -- the headers copra_hip.hip launches from.  The emulator's own: the stand-ins
+// for what copra_batch_specialise compiles (COPRA_EMU_SPECIALISED_*), use_specialised = 0, and the switches named where they are read.
 #include "wave_prims.hpp" // must come first: shadows copra_amd/csrc/wave_prims.hpp (same include guard name)
 
-#include "../../copra_amd/csrc/axis_builds.hpp"
+#include "../../copra_amd/csrc/front_end.hpp" // axis_builds.hpp, tier_builds.hpp
 #include "../../copra_amd/csrc/islmpc_fused.hpp"
 #include "../../copra_amd/csrc/lmpc_fused.hpp"
 #include "../../copra_amd/csrc/lmpc_fused_ric.hpp"
@@ -163,12 +166,7 @@ using namespace copra_hip;
 
 static const double* g_cost_p[copra_hip::kMaxCosts]; // per-instance cost references for the next emu_lmpc_solve
 static const double* g_cost_w[copra_hip::kMaxCosts]; // per-instance cost weights, by the USER's cost index (emu_set_cost_weights)
-static bool emu_weights_set()
-{
-    for (int k = 0; k < copra_hip::kMaxCosts; ++k)
-        if (g_cost_w[k]) return true;
-    return false;
-}
+static bool any_set(const double* const* p) { return std::any_of(p, p + copra_hip::kMaxCosts, [](const double* q) { return q != nullptr; }); }
 
 // The body of a build of the (instance, axis)-per-lane solver (axis_builds.hpp) for wave g -- in the tests' two-slot mode (small_q) the first
 // launch's build with room for two active constraints and without the horizon compiled in.  The families first_w and list_w are the same bodies
@@ -192,6 +190,54 @@ static bool emu_axis_body(const AxisBuild* b, bool small_q, const FusedPlan& P, 
     return false;
 }
 
+// The emulator's own builds, in the entry form of tier_builds.hpp: the stand-ins for what copra_batch_specialise compiles for a shape the library holds no
+// build of (or, under COPRA_EMU_WANT_RIC, instead of the run-time-horizon build it holds) -- the Riccati-factor tier with the horizon compiled in, the pass of (5, 3)
+#define COPRA_EMU_SPECIALISED_FIRST(X)                                                                                                      \
+    COPRA_RIC_BUILDS_OF(X, emu, 6, 3, 12) COPRA_RIC_BUILDS_OF(X, emu, 4, 2, 16) COPRA_RIC_BUILDS_OF(X, emu, 5, 3, 12) COPRA_RIC_BUILDS_OF(X, emu, 2, 1, 10) COPRA_RIC_BUILDS_OF(X, emu, 2, 1, 40)
+#define COPRA_EMU_SPECIALISED_LANE(X) COPRA_LANE_BUILDS_OF(X, emu, 5, 3)
+static constexpr TierBuild kEmuSpecialisedFirst[] = { COPRA_EMU_SPECIALISED_FIRST(COPRA_FIRST_ENTRY) };
+static constexpr TierBuild kEmuSpecialisedLane[] = { COPRA_EMU_SPECIALISED_LANE(COPRA_LANE_ENTRY) };
+// The body of an entry of a list of tier_builds.hpp, or of a stand-in, for instance -- the pass: wave -- i; false: b is no entry
+static bool emu_tier_body(const TierBuild* b, const FusedPlan& P, int i, bool lane_failed = false)
+{
+#define COPRA_EMU_first_ric(NX, NU, NH, RP, QR, SREFS) lmpc_fused_ric_body<NX, NU, NH, 6, QR, SREFS>(P, i, lane_failed)
+#define COPRA_EMU_first_tri(NX, NU, NH, RP, QR, SREFS) lmpc_fused_body<NX, NU, NH, RP, true, QR>(P, i)
+#define COPRA_EMU_first_square(NX, NU, NH, RP, QR, SREFS) lmpc_fused_body<NX, NU, NH, RP>(P, i)
+#define COPRA_EMU_first_w4(NX, NU, NH, RP, QR, SREFS) lmpc_fused_body<0, 0, 0, 0>(P, i)
+#define COPRA_EMU_shared_tri(NX, NU, NH) lmpc_shared_body<NX, NU, NH, true>(P, i)
+#define COPRA_EMU_shared_first(NX, NU, NH) lmpc_shared_body<NX, NU, NH>(P, i)
+#define COPRA_EMU_shared_w4(NX, NU, NH) lmpc_shared_body<0, 0, 0>(P, i)
+#define COPRA_EMU_shared_tier2(NX, NU, NH) lmpc_shared_body<NX, NU, NH>(P, i)
+#define COPRA_EMU_RUN_FIRST(UNIT, KIND, ...) if (b == e++) return COPRA_EMU_first_##KIND(__VA_ARGS__), true;
+#define COPRA_EMU_RUN_SHARED(UNIT, KIND, ...) if (b == e++) return COPRA_EMU_shared_##KIND(__VA_ARGS__), true;
+#define COPRA_EMU_RUN_SECOND(UNIT, ...) if (b == e++) return lmpc_fused_body<__VA_ARGS__>(P, i), true;
+#define COPRA_EMU_RUN_LANE(UNIT, ...) if (b == e++) return lmpc_lane_body<__VA_ARGS__>(P, i), true;
+#define COPRA_EMU_RUN_LANE_SHARED(UNIT, ...) if (b == e++) return lmpc_lane_shared_body<__VA_ARGS__>(P, i), true;
+    const TierBuild* e = kFirstTierBuilds; COPRA_FIRST_TIER_BUILDS(COPRA_EMU_RUN_FIRST)
+    e = kEmuSpecialisedFirst; COPRA_EMU_SPECIALISED_FIRST(COPRA_EMU_RUN_FIRST)
+    e = kSecondTierBuilds; COPRA_SECOND_TIER_BUILDS(COPRA_EMU_RUN_SECOND)
+    e = kLaneBuilds; COPRA_LANE_BUILDS(COPRA_EMU_RUN_LANE)
+    e = kEmuSpecialisedLane; COPRA_EMU_SPECIALISED_LANE(COPRA_EMU_RUN_LANE)
+    e = kLaneSharedBuilds; COPRA_LANE_SHARED_BUILDS(COPRA_EMU_RUN_LANE_SHARED)
+    e = kSharedBuilds; COPRA_SHARED_BUILDS(COPRA_EMU_RUN_SHARED)
+    return false;
+}
+// The emulator's picks: the library's (tier_builds.hpp), or a stand-in's where the library's list has no entry for the shape -- the Riccati-factor tier's
+// under COPRA_EMU_WANT_RIC too; nullptr: neither.  use_specialised = 0: the run-time-shape body for a shape that has a build of its own.
+static const TierBuild* emu_pick_first_tier(const FusedPlan& P, bool use_specialised)
+{
+    const TierBuild* b = pick_first_tier(P, use_specialised);
+    if (!(P.lds.tri && P.lds.ric)) return b;
+    if (!ric_aot_shape(P.nx, P.nu)) b = nullptr; // (the library answers such a shape with a build nobody launches)
+    const TierBuild* s = find_build(kEmuSpecialisedFirst, { TierKind::ric, P.nx, P.nu, P.N, 6, P.lds.q1regs ? kFusedQ1Regs : 0, P.stage_refs != 0, false });
+    return s && (!b || std::getenv("COPRA_EMU_WANT_RIC")) ? s : b;
+}
+static const TierBuild* emu_pick_lane(const FusedPlan& P)
+{
+    const TierBuild* b = pick_lane(P);
+    return b ? b : find_build(kEmuSpecialisedLane, { TierKind::lane, P.nx, P.nu, 0, 0, 0, P.stage_refs != 0, P.lane_spec != 0 });
+}
+
 extern "C" {
 
 static int g_lane_hist[copra_hip::kLaneHistBins]; // violated-row histogram of the last lane pass (FusedPlan::lane_hist)
@@ -199,14 +245,46 @@ static int g_lane_hist[copra_hip::kLaneHistBins]; // violated-row histogram of t
 // first launch listed for the second, and the instances the second listed for the tier
 static int g_axis_last[4] = { -1, -1, 0, 0 };
 void emu_last_axis_run(int* out) { std::copy(g_axis_last, g_axis_last + 4, out); }
-// entry k of kAxisBuilds as emu_axis_build reports a pick; 0: no such entry
-int emu_axis_build_entry(int k, int* out)
+// a build of kAxisBuilds as (family, NXA, NU, NMAX, QMAX, EXACT, CT, RPA); 0: b is none
+static int emu_axis_fields(const AxisBuild* b, int* out)
 {
-    if (k < 0 || k >= (int)(sizeof(kAxisBuilds) / sizeof(kAxisBuilds[0]))) return 0;
-    const AxisBuild* b = kAxisBuilds + k;
+    if (!b) return 0;
     const int v[8] = { (int)b->family, b->nxa, b->nu, b->nmax, b->qmax, b->exact, b->ct, b->rpa };
     std::copy(v, v + 8, out);
     return 1;
+}
+int emu_axis_build_entry(int k, int* out) { return emu_axis_fields(k >= 0 && (size_t)k < std::size(kAxisBuilds) ? kAxisBuilds + k : nullptr, out); } // entry k; 0: no such entry
+// ... and the tiers and the pass of the last emu_lmpc_solve or emu_lmpc_solve_shared (nullptr: did not run):
+// [first tier | second tier | pass | shared-model pass | shared-model first | second tier]
+static const TierBuild* g_tier_last[6];
+// an entry as (kind, nx, nu, nh, rp, qr, srefs, spec); 0: b is none
+static int emu_entry_fields(const TierBuild* b, int* out)
+{
+    if (!b) return 0;
+    const int v[8] = { (int)b->kind, b->nx, b->nu, b->nh, b->rp, b->qr, b->srefs, b->spec };
+    std::copy(v, v + 8, out);
+    return 1;
+}
+void emu_last_tier_run(int* out) // out[9 * i]: launch i ran, out[9 * i + 1 ...]: its entry
+{ for (int i = 0; i < 6; ++i) out[9 * i] = emu_entry_fields(g_tier_last[i], out + 9 * i + 1); }
+// entry k of list `list`: the lists of tier_builds.hpp (0 first tier, 1 second tier, 2 pass, 3 shared-model pass, 4 shared-model kernels) and the emulator's
+// stand-ins (5 first tier, 6 pass); 0: no such entry
+int emu_tier_build_entry(int list, int k, int* out)
+{
+    auto at = [&](auto& builds) { return k >= 0 && (size_t)k < std::size(builds) ? builds + k : nullptr; };
+    return emu_entry_fields(list == 0 ? at(kFirstTierBuilds) : list == 1 ? at(kSecondTierBuilds) : list == 2 ? at(kLaneBuilds) : list == 3 ? at(kLaneSharedBuilds)
+            : list == 4 ? at(kSharedBuilds) : list == 5 ? at(kEmuSpecialisedFirst) : at(kEmuSpecialisedLane), out);
+}
+// the LIBRARY's pick from list `list` (0 .. 4) for a plan with the fields f = (nx, nu, N, rmax, rfull, lds.tri, lds.ric, lds.q1regs, lds.total, stage_refs,
+// lane_spec, second tier of the shared-model kernels); 0: none
+int emu_tier_build(int list, const int* f, int use_specialised, int* out)
+{
+    FusedPlan P {};
+    P.nx = f[0], P.nu = f[1], P.N = f[2], P.rmax = f[3], P.rfull = f[4];
+    P.lds.tri = f[5], P.lds.ric = f[6], P.lds.q1regs = f[7], P.lds.total = f[8];
+    P.stage_refs = f[9], P.lane_spec = f[10];
+    return emu_entry_fields(list == 0 ? pick_first_tier(P, use_specialised != 0) : list == 1 ? pick_second_tier(P, use_specialised != 0) : list == 2 ? pick_lane(P)
+            : list == 3 ? pick_lane_shared(P) : pick_shared(P, f[11] != 0), out);
 }
 void emu_last_lane_hist(int* out) { std::copy(g_lane_hist, g_lane_hist + copra_hip::kLaneHistBins, out); }
 void emu_set_cost_reference(int cost_index, const double* p) { g_cost_p[cost_index] = p; }
@@ -229,19 +307,51 @@ void emu_set_options(const copra_options_t* opts)
 static const double *g_row_f_inst, *g_lb_inst, *g_ub_inst;
 void emu_set_instance_rows(const double* row_f, const double* lb, const double* ub)
 {
-    g_row_f_inst = row_f;
-    g_lb_inst = lb;
-    g_ub_inst = ub;
+    g_row_f_inst = row_f, g_lb_inst = lb, g_ub_inst = ub;
 }
-// the build of the (instance, axis)-per-lane solver a controller gets (axis_builds.hpp: pick_axis_build): 1 and out = (family, NXA, NU, NMAX,
-// QMAX, EXACT, CT, RPA), or 0: none
+// the build of the (instance, axis)-per-lane solver a controller gets (axis_builds.hpp: pick_axis_build); 0: none
 int emu_axis_build(int nx, int nu, int N, int axis_const, int axis_rpa, int stage_refs, int weights, int list, int* out)
 {
-    const AxisBuild* b = pick_axis_build(nx, nu, N, axis_const, axis_rpa, stage_refs, weights, list);
-    if (!b) return 0;
-    const int v[8] = { (int)b->family, b->nxa, b->nu, b->nmax, b->qmax, b->exact, b->ct, b->rpa };
-    std::copy(v, v + 8, out);
-    return 1;
+    return emu_axis_fields(pick_axis_build(nx, nu, N, axis_const, axis_rpa, stage_refs, weights, list), out);
+}
+
+// The per-solve inputs of a plan as device_plan (copra_hip.hip) places them: the per-instance references, weights -- the user's cost k is the
+// kernel-evaluated term cost_slot[k]; a dense (host-evaluated) cost has no weights the kernels read --, right-hand sides and bounds, and the tables of the
+// order the systems' states are in (from the first system: copra_hip.hip, see_axis_order)
+static int emu_plan_inputs(HostPlan& hp, const double* A, const double* B, int batch)
+{
+    FusedPlan& P = hp.plan;
+    for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = g_cost_p[k];
+    for (int k = 0; k < kMaxCosts; ++k) {
+        if (!g_cost_w[k]) continue;
+        if (k >= (int)hp.cost_slot.size()) return (int)COPRA_ERR_ARG;
+        const int t = hp.cost_slot[(size_t)k];
+        if (t < 0) return (int)COPRA_ERR_UNSUPPORTED;
+        P.cost_w[t] = g_cost_w[k];
+    }
+    P.row_f_inst = g_row_f_inst, P.lb_inst = g_lb_inst, P.ub_inst = g_ub_inst;
+    if (batch > 0 && A && B && !hp.large && !P.initial_state && axis_order_of(A, B, P.nx, P.nu) == 1 && hp.axis1_tab >= 0) {
+        P.axis_order = 1, P.axis_tab = hp.axis1_tab, P.axis_cref = hp.axis1_cref, P.axis_rpa = hp.axis1_rpa, P.axis_const = hp.axis1_const;
+    }
+    return 0;
+}
+// front_end.hpp on the plan of a controller with the inputs set for the next solve: out = (axis_solver_covers, lane_pass_covers, weights_layout's answer for
+// a controller that has weights, its two_tier, dense, lds.total, lds.tri, lds.ric, lds.rcap; the HostPlan's dense, safe_two_tier, lds_safe and lds_full)
+int emu_front_end(const copra_dims_t* dims, int n_costs, const copra_cost_desc_t* costs, int n_cstrs, const copra_cstr_desc_t* cstrs,
+    const copra_initial_state_desc_t* is, const double* A, const double* B, int* out)
+{
+    HostPlan hp;
+    const copra_status_t rc = build_plan(hp, *dims, n_costs, costs, n_cstrs, cstrs, is);
+    if (rc != COPRA_OK) return (int)rc;
+    point_plan_to_host(hp);
+    if (const int e = emu_plan_inputs(hp, A, B, dims->batch)) return e;
+    WeightsLayout w {};
+    const bool routed = weights_layout(hp, w);
+    const LdsLayout &ls = hp.lds_safe, &lf = hp.lds_full; // (the HostPlan's fields weights_layout reads, for a test to hold its answer against)
+    const int v[19] = { axis_solver_covers(hp, hp.plan), lane_pass_covers(hp, hp.plan), routed, w.two_tier, w.dense, w.lds.total, w.lds.tri, w.lds.ric, w.lds.rcap,
+        hp.dense, hp.safe_two_tier, ls.total, ls.tri, ls.ric, ls.rcap, lf.total, lf.tri, lf.ric, lf.rcap };
+    std::copy(v, v + 19, out);
+    return 0;
 }
 
 // Build the plan exactly as copra_batch_create does and run the fused kernel body for every instance.
@@ -257,8 +367,8 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         fprintf(stderr, "emu: %s\n", hp.error.c_str());
         return (int)rc;
     }
-    g_axis_last[0] = g_axis_last[1] = -1;
-    g_axis_last[2] = g_axis_last[3] = 0;
+    g_axis_last[0] = g_axis_last[1] = -1, g_axis_last[2] = g_axis_last[3] = 0;
+    std::fill(g_tier_last, g_tier_last + 6, nullptr);
     if (std::getenv("COPRA_EMU_WANT_RIC")) (void)take_ric_layout(hp); // (what copra_batch_specialise does once the shape's kernel is compiled)
     if (const char* steps = std::getenv("COPRA_EMU_LADDER_STEPS")) { // (what adapt_layout does after solves that overflowed: steps down the tier's ladder)
         for (int q = 0; q < std::atoi(steps); ++q) {
@@ -270,46 +380,19 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
     }
     point_plan_to_host(hp);
     FusedPlan& P = hp.plan;
-    P.A = A;
-    P.B = B;
-    P.d = d;
-    P.x0 = x0;
-    P.control = control;
-    P.trajectory = trajectory;
-    P.status = status;
-    P.iter = iter;
-    P.dump_instance = dump_instance;
-    P.dumpQ = dumpQ;
-    P.dumpc = dumpc;
-    P.dumpA = dumpA;
-    P.dumpb = dumpb;
-    P.x0lb = x0lb;
-    P.x0ub = x0ub;
-    P.x0_opt = x0_opt;
-    for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = g_cost_p[k];
-    // per-instance weights, as copra_batch_set_cost_weights places them: the user's cost k is the kernel-evaluated term cost_slot[k]; a dense
-    // (host-evaluated) cost has no weights the kernels read
-    bool weights = false;
-    for (int k = 0; k < kMaxCosts; ++k) {
-        if (!g_cost_w[k]) continue;
-        if (k >= (int)hp.cost_slot.size()) return (int)COPRA_ERR_ARG;
-        const int t = hp.cost_slot[(size_t)k];
-        if (t < 0) return (int)COPRA_ERR_UNSUPPORTED;
-        P.cost_w[t] = g_cost_w[k];
-        weights = true;
-    }
-    // (copra_hip.hip, weights_route: the Riccati-factor tier's tables hold the creation weights -- a controller with per-instance weights runs
-    //  the generic one-wave kernels on the layout that tier's ladder ends on)
-    LdsLayout lds_own = P.lds; // (the controller's own first tier, before the weights route it away: what the front ends' conditions look at)
-    if (weights && P.lds.ric && !hp.large && !P.initial_state) {
-        hp.two_tier = hp.dense && hp.safe_two_tier && !hp.lds_safe.ric;
-        hp.dense = false;
-        P.lds = hp.two_tier ? hp.lds_safe : hp.lds_full;
+    P.A = A, P.B = B, P.d = d, P.x0 = x0;
+    P.control = control, P.trajectory = trajectory, P.status = status, P.iter = iter;
+    P.dump_instance = dump_instance, P.dumpQ = dumpQ, P.dumpc = dumpc, P.dumpA = dumpA, P.dumpb = dumpb;
+    P.x0lb = x0lb, P.x0ub = x0ub, P.x0_opt = x0_opt;
+    if (const int e = emu_plan_inputs(hp, A, B, dims->batch)) return e;
+    LdsLayout lds_own = P.lds; // (the controller's own first tier, before the weights route it away: what the emulator's own conditions below look at)
+    WeightsLayout wl {};
+    if (plan_has_weights(P) && weights_layout(hp, wl)) { // (copra_hip.hip, weights_route)
+        hp.two_tier = wl.two_tier;
+        hp.dense = wl.dense;
+        P.lds = wl.lds;
         hp.lds_bytes = (size_t)P.lds.total * sizeof(double);
     }
-    P.row_f_inst = g_row_f_inst;
-    P.lb_inst = g_lb_inst;
-    P.ub_inst = g_ub_inst;
     if (sizes) {
         sizes[0] = P.initial_state ? P.nx + P.n : P.n;
         sizes[1] = P.meq;
@@ -340,15 +423,10 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
     }
     if (P.initial_state) {
         for (int b = 0; b < dims->batch; ++b) {
-            int r = emu::run_wave([&]() { islmpc_fused_body(P, b); }, hp.lds_bytes, b, dims->batch);
-            if (r != 0) return -100;
+            if (emu::run_wave([&]() { islmpc_fused_body(P, b); }, hp.lds_bytes, b, dims->batch) != 0) return -100;
         }
         return 0;
     }
-    // same dispatch as the HIP launcher (select_fused_kernel): compile-time shapes for the BASELINE configs
-    const int rp = specialised_cost_rows(P.nx, P.nu, P.N, P.rmax, P.rfull);
-    const bool s6 = use_specialised && P.nx == 6 && rp == 6;
-    const bool s2 = use_specialised && P.nx == 2 && rp == 2;
     // two-tier execution exactly as copra_batch_solve does it: compact layout first, overflow queue, full layout
     int ovf_count = 0;
     std::vector<int> ovf_list((size_t)(dims->batch > 0 ? dims->batch : 1));
@@ -356,112 +434,39 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
     P.ovf_list = ovf_list.data();
     P.from_list = 0;
     if (dump_instance >= 0) P.lds = hp.lds_full;
-    const bool sfull = use_specialised && P.rfull > 0 && P.nx == 6 && P.nu == 3 && P.N == 20; // (headline shape, full-size costs)
-    if (!s6 && !sfull && !(use_specialised && P.lds.ric) && P.lds.q1regs > 0) { // the run-time-shape body keeps Q1 in LDS (it never meets a register-Q1 layout in the library)
+    // a body without register columns of Q1 keeps Q1 in LDS (it never meets a register-Q1 layout in the library; use_specialised = 0: nor does the tier's)
+    for (LdsLayout* l : { &P.lds, &lds_own }) {
+        FusedPlan T = P;
+        T.lds = *l;
+        const TierBuild* b = emu_pick_first_tier(T, use_specialised);
         LdsLayout lq {};
-        if (tri_layout_with_lds_q1(P, P.lds, lq)) P.lds = lq;
-    }
-    if (!s6 && !sfull && !(use_specialised && lds_own.ric) && lds_own.q1regs > 0) { // (the same step on the layout the weights routed away)
-        LdsLayout lq {};
-        if (tri_layout_with_lds_q1(P, lds_own, lq)) lds_own = lq;
+        if (l->q1regs > 0 && ((b && b->qr == 0) || (!use_specialised && l->ric)) && tri_layout_with_lds_q1(P, *l, lq)) *l = lq;
     }
     const bool ric_layout = lds_own.ric != 0;
     bool lane_failed = false; // (the instance comes from the one-instance-per-lane pass with a failed factorisation)
-    auto body = [&](const FusedPlan& PP, int b) {
-        // the library's builds with a RUN-TIME horizon (copra_hip_ric.hip; select_fused_kernel) for the shapes of ric_aot_shape -- unless the
-        // test asks for what copra_batch_specialise compiles (COPRA_EMU_WANT_RIC: the compile-time instantiations below)
-        const bool rt = PP.lds.tri && PP.lds.ric && ric_aot_shape(PP.nx, PP.nu) && !ric_aot_exact(PP.nx, PP.nu, PP.N) && !std::getenv("COPRA_EMU_WANT_RIC");
-#define EMU_RIC_RT(NX, NU)                                                                                             \
-    (PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<NX, NU, 0, 6, kFusedQ1Regs, true>(PP, b, lane_failed)        \
-                                    : lmpc_fused_ric_body<NX, NU, 0, 6, kFusedQ1Regs>(PP, b, lane_failed))             \
-                   : (PP.stage_refs ? lmpc_fused_ric_body<NX, NU, 0, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<NX, NU, 0, 6, 0>(PP, b, lane_failed)))
-        if (rt && PP.nx == 6)
-            EMU_RIC_RT(6, 3);
-        else if (rt && PP.nx == 4)
-            EMU_RIC_RT(4, 2);
-        else if (rt)
-            EMU_RIC_RT(2, 1);
-#undef EMU_RIC_RT
-        // (shapes beyond the library's instantiations: what copra_batch_specialise compiles at run time)
-        else if (PP.lds.tri && PP.lds.ric && PP.nx == 6 && PP.nu == 3 && PP.N == 12)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 12, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 12, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 12, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 12, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.nx == 4 && PP.nu == 2 && PP.N == 16)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<4, 2, 16, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<4, 2, 16, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<4, 2, 16, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<4, 2, 16, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.nx == 5 && PP.nu == 3 && PP.N == 12)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<5, 3, 12, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<5, 3, 12, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<5, 3, 12, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<5, 3, 12, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.nx == 2 && PP.nu == 1 && PP.N == 10)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<2, 1, 10, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<2, 1, 10, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<2, 1, 10, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<2, 1, 10, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.nx == 2 && PP.nu == 1 && PP.N == 40)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<2, 1, 40, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<2, 1, 40, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<2, 1, 40, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<2, 1, 40, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.N == 10) // (select_fused_kernel: the factor in Riccati form)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 10, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 10, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 10, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 10, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.N == 15)
-            PP.lds.q1regs ? (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 15, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 15, 6, kFusedQ1Regs>(PP, b, lane_failed)) : (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 15, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 15, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric && PP.lds.q1regs)
-            (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 20, 6, kFusedQ1Regs, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 20, 6, kFusedQ1Regs>(PP, b, lane_failed));
-        else if (PP.lds.tri && PP.lds.ric)
-            (PP.stage_refs ? lmpc_fused_ric_body<6, 3, 20, 6, 0, true>(PP, b, lane_failed) : lmpc_fused_ric_body<6, 3, 20, 6, 0>(PP, b, lane_failed));
-        else if (PP.lds.tri && s6 && PP.lds.q1regs == kFusedQ1Regs) // (select_fused_kernel: the factor-only first tier, Q1 in registers)
-            lmpc_fused_body<6, 3, 20, 6, true, kFusedQ1Regs>(PP, b);
-        else if (PP.lds.tri && s6)
-            lmpc_fused_body<6, 3, 20, 6, true>(PP, b);
-        else if (PP.lds.tri && sfull && PP.lds.q1regs == kFusedQ1Regs)
-            lmpc_fused_body<6, 3, 20, 0, true, kFusedQ1Regs>(PP, b);
-        else if (PP.lds.tri && sfull)
-            lmpc_fused_body<6, 3, 20, 0, true>(PP, b);
-        else if (PP.lds.tri)
-            lmpc_fused_body<0, 0, 0, 0, true>(PP, b);
-        else if (s6)
-            lmpc_fused_body<6, 3, 20, 6>(PP, b);
-        else if (s2)
-            lmpc_fused_body<2, 1, 10, 2>(PP, b);
-        else if (use_specialised && PP.rfull > 0 && PP.nx == 6 && PP.nu == 3 && PP.N == 20) // headline shape, full-size costs
-            lmpc_fused_body<6, 3, 20, 0>(PP, b);
-        else
-            lmpc_fused_body<0, 0, 0, 0>(PP, b);
-    };
+    // the first tier's build (tier_builds.hpp: the pick of select_fused_kernel; the stand-ins of copra_batch_specialise), and the second tier's
+    bool no_body = false;
+    auto body = [&](const FusedPlan& PP, int b) { no_body = !emu_tier_body(g_tier_last[0] = emu_pick_first_tier(PP, use_specialised), PP, b, lane_failed) || no_body; };
     const size_t bytes1 = (size_t)P.lds.total * sizeof(double);
-    // the one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp), as copra_batch_solve runs it
-    // (copra_hip.hip: lane_pass_wanted): the instances it does not finish go through the first tier
-    bool lane_pass = P.lane_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && (ric_layout || std::getenv("COPRA_EMU_LANE_FILTER")) && !default_options().no_lane_pass
-        && ((P.nx == 6 && P.nu == 3) || (P.nx == 4 && P.nu == 2) || (P.nx == 5 && P.nu == 3) || (P.nx == 2 && P.nu == 1));
-    for (int k = 0; k < kMaxCosts; ++k) lane_pass = lane_pass && (!P.cost_p[k] || P.lane_cref >= 0);
-    const bool lane_shape = lane_pass; // (what the axis solver's condition below asks of the pass: its shape, not whether it runs)
-    lane_pass = lane_pass && !weights; // (lane_pass_wanted: its tables hold the creation weights)
+    // The emulator's own conditions on a front end, besides front_end.hpp's: never for a dump; the library's batch threshold (lane_batch_ok) has no meaning
+    // here -- the pass runs in front of the Riccati-factor tier, in front of another tier under COPRA_EMU_LANE_FILTER only --; and chains of TWO states
+    // per control go to the (instance, axis)-per-lane solver only where the pass could run, weights aside (the library has no such term: the tests
+    // that compare the tiers behind plain options -- no_ric, no_tri, a ladder step -- on decoupled (6, 3) controllers rely on it)
+    const bool pass_here = dump_instance < 0 && (ric_layout || std::getenv("COPRA_EMU_LANE_FILTER"));
+    bool two_state_chains_here = pass_here && P.lane_tab >= 0;
+    for (int k = 0; k < kMaxCosts; ++k) two_state_chains_here = two_state_chains_here && (!P.cost_p[k] || P.lane_cref >= 0);
+    // the one-(instance, axis)-per-lane solver (lmpc_axis.hpp) where the controller's axes are decoupled, else the one-instance-per-lane pass (lmpc_lane.hpp)
+    // where a build of it exists: the instances a front end does not finish go through the first tier
+    const bool axis_pass = dump_instance < 0 && axis_solver_covers(hp, P) && (P.nx != 2 * P.nu || two_state_chains_here);
+    const bool lane_pass = pass_here && lane_pass_covers(hp, P) && emu_pick_lane(P) != nullptr;
     std::vector<int> lane_list((size_t)dims->batch + 64, -1);
     std::vector<double> lane_ws, lane_ws2;
     int lane_cnt[4] = { 0, 0, 0, 0 }; // (as the device's: [left over | the next solve's] [+ 2: ended by the pass's own steps])
     int &lane_count = lane_cnt[0], &lane_other = lane_cnt[1];
-    // ... or, where the controller's axes are decoupled, the one-(instance, axis)-per-lane solver (lmpc_axis.hpp; copra_hip.hip: axis_solver_wanted)
-    // (the order of the systems' states, from the first one: copra_hip.hip, see_axis_order)
-    if (dims->batch > 0 && P.A && P.B && !hp.large && !P.initial_state && axis_order_of(P.A, P.B, P.nx, P.nu) == 1 && hp.axis1_tab >= 0) {
-        P.axis_order = 1;
-        P.axis_tab = hp.axis1_tab;
-        P.axis_cref = hp.axis1_cref;
-        P.axis_rpa = hp.axis1_rpa;
-        P.axis_const = hp.axis1_const;
-    }
-    // (independent of the pass: chains of three states per control have no build of it)
-    bool axis_pass = P.axis_tab >= 0 && !hp.large && !P.initial_state && dump_instance < 0 && !default_options().no_lane_pass && (lane_shape || P.nx == 3 * P.nu || P.nx == P.nu)
-        && !default_options().no_axis_solver && axis_solver_nmax(P.nx, P.nu, P.N) > 0
-        && (!(P.row_f_inst || P.lb_inst || P.ub_inst) || (P.axis_const && (P.lb_inst == nullptr) == (P.ub_inst == nullptr)));
-    for (int k = 0; k < kMaxCosts; ++k) axis_pass = axis_pass && (!P.cost_p[k] || (P.axis_cref >= 0 && k < P.ncost));
-    if (axis_pass && weights) { // (per-instance weights: copra_hip.hip, axis_solver_wanted -- both launches need a build that reads them, the lane
-        // divides by the creation weight, and a full-size cost has no coefficients in FusedPlan::axis_cref)
-        axis_pass = P.axis_cref >= 0 && pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, true, false)
-            && pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, true, true);
-        for (int t = 0; t < P.ncost && axis_pass; ++t) {
-            if (!P.cost_w[t]) continue;
-            const CostTerm& ct = P.cost[t];
-            if (ct.full) axis_pass = false;
-            for (int r = 0; r < ct.rows; ++r)
-                if (P.params[(size_t)ct.offW + r] == 0.0) axis_pass = false;
-        }
-    }
-    if (axis_pass && P.stage_refs) { // (reference trajectories: copra_hip.hip, axis_solver_wanted)
-        int oB = 0, oR = 0, rcs = 0;
-        (void)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs);
-        axis_pass = P.axis_cref >= 0 && P.N * (P.nx / P.nu + 1) <= rcs;
+    if (axis_pass || lane_pass) { // what either front end fills: the list of the instances it leaves to the tier, and the violated-row histogram
+        P.lane_list = lane_list.data(), P.lane_count = &lane_count, P.lane_zero = &lane_other;
+        std::fill(g_lane_hist, g_lane_hist + kLaneHistBins, 0);
+        P.lane_hist = g_lane_hist; // (what the first solve of a controller asks of the pass: copra_batch_solve picks the tier's layout from it)
     }
     if (axis_pass) {
         int on_spare = 0;
@@ -470,25 +475,19 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         P.axis_waves = groups;
         P.axis_pf = groups > 2 ? 2 : 0; // (the touches of a later wave's systems: exercised, without effect here)
         P.axis_acc = axis_acc.data();
-        P.lane_list = lane_list.data();
-        P.lane_count = &lane_count;
-        P.lane_zero = &lane_other;
-        std::fill(g_lane_hist, g_lane_hist + kLaneHistBins, 0);
-        P.lane_hist = g_lane_hist;
         int oB = 0, oR = 0, rcs = 0;
         const size_t abytes = (size_t)axis_lds_doubles(P.nx, P.nu, P.N, P.axis_rpa, kAxisQmax, oB, oR, rcs) * sizeof(double); // (sized for the library's builds; the two-slot test build needs less)
         const bool small_q = std::getenv("COPRA_EMU_AXIS_QMAX2") != nullptr; // (tests: an active set that outgrows the lane -- the hand-over to the tier)
-        // the library's builds: the same pick as copra_hip.hip's select_axis_kernel and select_axis_list_kernel
-        const AxisBuild* first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, false);
-        const AxisBuild* second = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, true);
+        // the library's builds: the pick of copra_hip.hip's select_axis_kernel and select_axis_list_kernel
+        const AxisBuild* first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, plan_has_weights(P), false);
+        const AxisBuild* second = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, plan_has_weights(P), true);
         if (!first || !second) {
             std::fprintf(stderr, "emu: the axis solver has no build for nx %d, nu %d, N %d, axis_rpa %d\n", P.nx, P.nu, P.N, P.axis_rpa);
             return -100;
         }
         for (int g = 0; g < groups; ++g) {
             bool ran = false;
-            int r = emu::run_wave([&]() { ran = emu_axis_body(first, small_q, P, g); }, abytes, g, groups);
-            if (r != 0 || !ran) return -100;
+            if (emu::run_wave([&]() { ran = emu_axis_body(first, small_q, P, g); }, abytes, g, groups) != 0 || !ran) return -100;
         }
         P.lane_hist = nullptr;
         g_axis_last[0] = (int)(first - kAxisBuilds);
@@ -510,8 +509,7 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
             const int ipw = 64 / P.nu;
             for (int g = 0; g * ipw < lane_count; ++g) {
                 bool ran = false;
-                int r = emu::run_wave([&]() { ran = emu_axis_body(second, false, Pl, g); }, lbytes, g, 1);
-                if (r != 0 || !ran) return -100;
+                if (emu::run_wave([&]() { ran = emu_axis_body(second, false, Pl, g); }, lbytes, g, 1) != 0 || !ran) return -100;
             }
             if (std::getenv("COPRA_EMU_AXIS_REPORT")) { // (tools: who is listed, and why)
                 int bad1 = 0, bad2 = 0;
@@ -526,18 +524,8 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
             lane_count = count2;
             g_axis_last[3] = count2;
         }
-        P.lane_from_list = 1;
         P.lane_spec = P.lds.ricC ? 1 : 0; // (nothing is handed over: the tier sweeps for itself)
         P.lane_handover = 0;
-        for (int k = 0; k < lane_count; ++k) {
-            const int raw = lane_list[(size_t)k], b = raw & 0x7fffffff;
-            lane_failed = raw < 0;
-            int r = emu::run_wave([&]() { body(P, b); }, bytes1, b, dims->batch);
-            if (r != 0) return -100;
-        }
-        lane_failed = false;
-        P.lane_from_list = 0;
-        if (sizes) sizes[8] = dims->batch - lane_count;
     } else if (lane_pass) {
         const int groups = (dims->batch + 63) / 64;
         P.lane_bp = (dims->batch + 63) / 64 * 64 + 64;
@@ -545,53 +533,34 @@ int emu_lmpc_solve(const copra_dims_t* dims, int n_costs, const copra_cost_desc_
         P.lane_ws = lane_ws.data();
         lane_ws2.assign((size_t)P.lane_bp * lane_ws2_doubles(P.nx, P.nu, P.N), 0.0);
         P.lane_ws2 = lane_ws2.data();
-        P.lane_list = lane_list.data();
-        P.lane_count = &lane_count;
-        P.lane_zero = &lane_other;
         P.lane_spec = (P.lds.ricC && !default_options().no_lane_spec) ? 1 : 0; // (as copra_batch_solve: the two forms of the pass)
+        const TierBuild* lane_build = g_tier_last[2] = emu_pick_lane(P);
         P.lane_handover = (P.lds.ricC && !default_options().no_lane_handover && !P.lane_spec) ? 1 : 0;
-        std::fill(g_lane_hist, g_lane_hist + kLaneHistBins, 0);
-        P.lane_hist = g_lane_hist; // (what the first solve of a controller asks of the pass: copra_batch_solve picks the tier's layout from it)
         for (int g = 0; g < groups; ++g) {
             int oHl = 0;
             const size_t lbytes = (size_t)(lane_lds_doubles(P.nx, P.nu, oHl) + P.lane_tlds) * sizeof(double);
-            int r = emu::run_wave([&]() {
-#define COPRA_EMU_LANE(NX, NU)                                                                                                    \
-    (P.lane_spec ? (P.stage_refs ? lmpc_lane_body<NX, NU, true, true>(P, g) : lmpc_lane_body<NX, NU, false, true>(P, g))            \
-                 : (P.stage_refs ? lmpc_lane_body<NX, NU, true, false>(P, g) : lmpc_lane_body<NX, NU, false, false>(P, g)))
-                if (P.nx == 6) COPRA_EMU_LANE(6, 3);
-                else if (P.nx == 4) COPRA_EMU_LANE(4, 2);
-                else if (P.nx == 5) COPRA_EMU_LANE(5, 3);
-                else COPRA_EMU_LANE(2, 1);
-#undef COPRA_EMU_LANE
-            }, lbytes, g, groups);
-            if (r != 0) return -100;
+            if (emu::run_wave([&]() { (void)emu_tier_body(lane_build, P, g); }, lbytes, g, groups) != 0) return -100;
         }
         P.lane_hist = nullptr;
-        P.lane_from_list = 1;
-        for (int k = 0; k < lane_count; ++k) {
-            const int raw = lane_list[(size_t)k], b = raw & 0x7fffffff;
-            lane_failed = raw < 0;
-            int r = emu::run_wave([&]() { body(P, b); }, bytes1, b, dims->batch);
-            if (r != 0) return -100;
-        }
-        lane_failed = false;
-        P.lane_from_list = 0;
-        if (sizes) sizes[8] = dims->batch - lane_count;
-    } else {
-    for (int b = 0; b < dims->batch; ++b) {
-        int r = emu::run_wave([&]() { body(P, b); }, bytes1, b, dims->batch);
-        if (r != 0) return -100;
     }
+    // the first tier: what the front end listed (a negative entry: with a failed factorisation), or every instance
+    P.lane_from_list = (axis_pass || lane_pass) ? 1 : 0;
+    for (int k = 0; k < (P.lane_from_list ? lane_count : dims->batch); ++k) {
+        const int raw = P.lane_from_list ? lane_list[(size_t)k] : k, b = raw & 0x7fffffff;
+        lane_failed = raw < 0;
+        if (emu::run_wave([&]() { body(P, b); }, bytes1, b, dims->batch) != 0 || no_body) return -100; // (no_body: neither the library nor the stand-ins hold a build for the layout)
     }
+    lane_failed = false;
+    if (sizes && P.lane_from_list) sizes[8] = dims->batch - lane_count;
+    P.lane_from_list = 0;
     if (sizes) sizes[4] = ovf_count;
     if (ovf_count > 0) {
         FusedPlan P2 = P;
         P2.lds = hp.lds_full;
+        g_tier_last[1] = pick_second_tier(P2, use_specialised); // (select_tier2_kernel)
         for (int k = 0; k < ovf_count; ++k) {
             const int b = ovf_list[(size_t)k];
-            int r = emu::run_wave([&]() { body(P2, b); }, hp.lds_full_bytes, b, dims->batch);
-            if (r != 0) return -100;
+            if (emu::run_wave([&]() { (void)emu_tier_body(g_tier_last[1], P2, b); }, hp.lds_full_bytes, b, dims->batch) != 0) return -100;
         }
     }
     return 0;
@@ -612,7 +581,7 @@ int emu_lmpc_solve_riccati(const copra_dims_t* dims, int n_costs, const copra_co
     }
     point_plan_to_host(hp);
     FusedPlan& P = hp.plan;
-    if (emu_weights_set()) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_solve: the stage plan holds the creation weights)
+    if (any_set(g_cost_w)) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_solve: the stage plan holds the creation weights)
     HostStagePlan hs;
     build_stage_plan(hp, hs, g_lb_inst != nullptr);
     if (!hs.eligible) {
@@ -624,9 +593,7 @@ int emu_lmpc_solve_riccati(const copra_dims_t* dims, int n_costs, const copra_co
     P.control = control, P.trajectory = trajectory, P.status = status, P.iter = iter;
     P.x0lb = x0lb, P.x0ub = x0ub, P.x0_opt = x0_opt;
     for (int k = 0; k < kMaxCosts; ++k) P.cost_p[k] = g_cost_p[k];
-    P.row_f_inst = g_row_f_inst;
-    P.lb_inst = g_lb_inst;
-    P.ub_inst = g_ub_inst;
+    P.row_f_inst = g_row_f_inst, P.lb_inst = g_lb_inst, P.ub_inst = g_ub_inst;
     int ovf_count = 0;
     std::vector<int> ovf_list((size_t)(dims->batch > 0 ? dims->batch : 1));
     P.ovf_count = &ovf_count;
@@ -640,9 +607,7 @@ int emu_lmpc_solve_riccati(const copra_dims_t* dims, int n_costs, const copra_co
     const StagePlan& S = hs.sp;
     // same dispatch as the HIP launcher: the LDS-resident kernel (lmpc_riccati_mfma.hpp) where the plan fits it ...
     if (not_converged) not_converged[1] = 0;
-    bool refs = false;
-    for (int k = 0; k < kMaxCosts; ++k) refs = refs || g_cost_p[k] != nullptr;
-    if (S.fast_ok && !refs && !default_options().no_ric_fast) {
+    if (S.fast_ok && !any_set(g_cost_p) && !default_options().no_ric_fast) {
         int rf = emu::run_wave([&]() { lmpc_riccati_mfma_body(P, S); }, (size_t)S.fast_lds_doubles * sizeof(double), 0, 1);
         if (not_converged) not_converged[0] = ovf_count, not_converged[1] = 1;
         return rf != 0 ? -100 : 0;
@@ -678,7 +643,8 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
         return (int)rc;
     }
     if (hp.large) return (int)COPRA_ERR_UNSUPPORTED;
-    if (emu_weights_set()) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_set_cost_weights: the shared model holds the creation weights)
+    if (any_set(g_cost_w)) return (int)COPRA_ERR_UNSUPPORTED; // (copra_batch_set_cost_weights: the shared model holds the creation weights)
+    std::fill(g_tier_last, g_tier_last + 6, nullptr);
     point_plan_to_host(hp);
     FusedPlan P = hp.plan;
     const int nx = P.nx, nu = P.nu, N = P.N, n = P.n, X = P.X, np1 = nx + 1;
@@ -705,15 +671,7 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
     Q.A = Ap.data(), Q.B = Bp.data(), Q.d = dp.data(), Q.x0 = xp.data();
     Q.batch = np1;
     Q.lds = hp.lds_full;
-    auto fused = [&](const FusedPlan& PP, int b) {
-        const int rp = specialised_cost_rows(PP.nx, PP.nu, PP.N, PP.rmax, PP.rfull);
-        if (PP.nx == 6 && rp == 6)
-            lmpc_fused_body<6, 3, 20, 6>(PP, b);
-        else if (PP.nx == 2 && rp == 2)
-            lmpc_fused_body<2, 1, 10, 2>(PP, b);
-        else
-            lmpc_fused_body<0, 0, 0, 0>(PP, b);
-    };
+    auto fused = [&](const FusedPlan& PP, int b) { (void)emu_tier_body(pick_first_tier(PP), PP, b); }; // (select_fused_kernel, as prepare_shared_model)
     for (int a = 0; a < np1; ++a) {
         Q.dump_instance = a;
         Q.dump_only = 1;
@@ -748,8 +706,7 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
     P.warm_set = warm_set;
     // per-instance cost references (emu_set_cost_reference): only the records form with the pass in front takes them here (the delta sweep of
     // lmpc_lane_shared_body); the emulated lmpc_shared.hpp path has no reference columns in its model -> refused below
-    bool sh_refs = false;
-    for (int k = 0; k < kMaxCosts; ++k) sh_refs = sh_refs || g_cost_p[k] != nullptr;
+    const bool sh_refs = any_set(g_cost_p);
     // Riccati-factor tier in shared-model mode (as copra_batch_solve: cold starts, controller-wide references or the pass's delta sweep): one prepare
     // run of the body leaves the stage records, bkd, G and the row norms; the first tier copies them instead of sweeping
     std::vector<double> ric_model;
@@ -757,22 +714,7 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
     //  builds of the integrator shapes)
     const bool ric_shared = P.lds.ric && (ric_aot_exact(P.nx, P.nu, P.N) || ric_aot_shape(P.nx, P.nu)) && P.lds.q1regs == kFusedQ1Regs && !warm_set
         && !default_options().no_ric_shared;
-    auto ric_tier = [&](const FusedPlan& PP, int b) {
-#define EMU_RIC_SH(NX, NU, NH) (PP.stage_refs ? lmpc_fused_ric_body<NX, NU, NH, 6, kFusedQ1Regs, true>(PP, b) : lmpc_fused_ric_body<NX, NU, NH, 6, kFusedQ1Regs>(PP, b))
-        if (PP.nx == 6 && PP.N == 20)
-            EMU_RIC_SH(6, 3, 20);
-        else if (PP.nx == 6 && PP.N == 15)
-            EMU_RIC_SH(6, 3, 15);
-        else if (PP.nx == 6 && PP.N == 10)
-            EMU_RIC_SH(6, 3, 10);
-        else if (PP.nx == 6)
-            EMU_RIC_SH(6, 3, 0);
-        else if (PP.nx == 4)
-            EMU_RIC_SH(4, 2, 0);
-        else
-            EMU_RIC_SH(2, 1, 0);
-#undef EMU_RIC_SH
-    };
+    auto ric_tier = [&](const FusedPlan& PP, int b) { (void)emu_tier_body(g_tier_last[0] = pick_first_tier(PP), PP, b); }; // (select_fused_kernel)
     if (ric_shared) {
         int oBk, oG, oNb;
         ric_model.assign((size_t)ric_model_offsets(nx, nu, N, P.mgen, oBk, oG, oNb), 0.0);
@@ -790,32 +732,22 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
             hp.lds_bytes = (size_t)lq.total * sizeof(double);
         }
     }
-    auto shared = [&](const FusedPlan& PP, int b) {
-        if (PP.lds.ric && PP.ric_model)
-            ric_tier(PP, b);
-        else if (PP.lds.tri && PP.nx == 6 && PP.nu == 3 && PP.N == 20) // (select_shared_kernel: factor-only first tier)
-            lmpc_shared_body<6, 3, 20, true>(PP, b);
-        else if (PP.lds.tri)
-            lmpc_shared_body<0, 0, 0, true>(PP, b);
-        else if (PP.nx == 6 && PP.nu == 3 && PP.N == 20)
-            lmpc_shared_body<6, 3, 20>(PP, b);
-        else if (PP.nx == 2 && PP.nu == 1 && PP.N == 10)
-            lmpc_shared_body<2, 1, 10>(PP, b);
-        else
-            lmpc_shared_body<0, 0, 0>(PP, b);
+    auto shared = [&](const FusedPlan& PP, int b, bool tier2) { // (solve_shared_model: the records tier, else select_shared_kernel)
+        if (PP.lds.ric && PP.ric_model) return ric_tier(PP, b);
+        (void)emu_tier_body(g_tier_last[tier2 ? 5 : 4] = pick_shared(PP, tier2), PP, b);
     };
     // in front of the Riccati-factor tier in shared-model mode: the one-instance-per-lane pass in its shared-model form (as copra_batch_solve)
     std::vector<int> lane_list((size_t)dims->batch + 64, -1);
     int lane_cnt[4] = { 0, 0, 0, 0 };
     int &lane_count = lane_cnt[0], &lane_other = lane_cnt[1];
     int lane_finished = -1;
-    const bool lane_sh = ric_shared && P.lane_tab >= 0 && P.lds.ricC && !P.row_f_inst && !default_options().no_lane_pass;
+    const bool lane_sh = ric_shared && P.lane_tab >= 0 && P.lds.ricC && !P.row_f_inst && !default_options().no_lane_pass && pick_lane_shared(P); // (select_lane_shared_kernel: every shape of the tier)
     if (sh_refs && !(lane_sh && P.lane_cref >= 0)) {
         fprintf(stderr, "emu: shared-model references need the records form with the pass: ric_shared %d lane_tab %d ricC %d lane_cref %d\n", (int)ric_shared, P.lane_tab, (int)P.lds.ricC, P.lane_cref);
         return (int)COPRA_ERR_UNSUPPORTED;
     }
     std::vector<double> lane_ws_sh;
-    if (lane_sh) { // (select_lane_shared_kernel: every shape of the tier)
+    if (lane_sh) {
         const int groups = (dims->batch + 63) / 64;
         P.lane_bp = groups * 64;
         if (sh_refs) {
@@ -827,32 +759,24 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
         P.lane_count = &lane_count;
         P.lane_zero = &lane_other;
         P.lane_spec = default_options().no_lane_spec ? 0 : 1; // (copra_batch_solve, solve_shared_model)
+        g_tier_last[3] = pick_lane_shared(P);
         int oHl = 0;
         const size_t lbytes = (size_t)(lane_lds_doubles(P.nx, P.nu, oHl) + P.lane_tlds) * sizeof(double);
         for (int g = 0; g < groups; ++g)
-            if (emu::run_wave([&]() {
-                    if (P.nx == 6)
-                        P.lane_spec ? lmpc_lane_shared_body<6, 3, true>(P, g) : lmpc_lane_shared_body<6, 3, false>(P, g);
-                    else if (P.nx == 4)
-                        P.lane_spec ? lmpc_lane_shared_body<4, 2, true>(P, g) : lmpc_lane_shared_body<4, 2, false>(P, g);
-                    else
-                        P.lane_spec ? lmpc_lane_shared_body<2, 1, true>(P, g) : lmpc_lane_shared_body<2, 1, false>(P, g);
-                }, lbytes, g, groups) != 0) return -100;
+            if (emu::run_wave([&]() { (void)emu_tier_body(g_tier_last[3], P, g); }, lbytes, g, groups) != 0) return -100;
         P.lane_from_list = 1;
         P.lane_handover = 1;
         for (int k = 0; k < lane_count; ++k) {
             const int b = lane_list[(size_t)k];
-            if (emu::run_wave([&]() { shared(P, b); }, hp.lds_bytes, b, dims->batch) != 0) return -100;
+            if (emu::run_wave([&]() { shared(P, b, false); }, hp.lds_bytes, b, dims->batch) != 0) return -100;
         }
         P.lane_from_list = 0;
         lane_finished = dims->batch - lane_count;
     } else {
     for (int b = 0; b < dims->batch; ++b)
-        if (emu::run_wave([&]() { shared(P, b); }, hp.lds_bytes, b, dims->batch) != 0) return -100;
+        if (emu::run_wave([&]() { shared(P, b, false); }, hp.lds_bytes, b, dims->batch) != 0) return -100;
     }
-    if (sizes) sizes[0] = ovf_count;
-    if (sizes) sizes[1] = ric_shared ? 1 : 0;
-    if (sizes) sizes[2] = lane_finished;
+    if (sizes) sizes[0] = ovf_count, sizes[1] = ric_shared ? 1 : 0, sizes[2] = lane_finished;
     if (ovf_count > 0 && sh_refs) return (int)COPRA_ERR_UNSUPPORTED; // (the emulated second tier has no reference columns in its model)
     if (ovf_count > 0) {
         FusedPlan P2 = P;
@@ -860,7 +784,7 @@ int emu_lmpc_solve_shared(const copra_dims_t* dims, int n_costs, const copra_cos
         P2.ric_model = nullptr;
         for (int k = 0; k < ovf_count; ++k) {
             const int b = ovf_list[(size_t)k];
-            if (emu::run_wave([&]() { shared(P2, b); }, hp.lds_full_bytes, b, dims->batch) != 0) return -100;
+            if (emu::run_wave([&]() { shared(P2, b, true); }, hp.lds_full_bytes, b, dims->batch) != 0) return -100;
         }
     }
     return 0;

@@ -60,6 +60,77 @@ def last_axis_run():
     return dict(first=picks[0], second=picks[1], listed_first=v[2], listed_second=v[3])
 
 
+TIER_LISTS = ("first", "second", "lane", "lane_shared", "shared")  # (tier_builds.hpp: the lists, as emu_tier_build numbers them)
+TIER_STANDINS = ("first_standins", "lane_standins")  # (the emulator's own: what copra_batch_specialise compiles)
+TIER_KINDS = ("ric", "tri", "square", "w4", "second", "lane", "lane_shared", "shared_tri", "shared_first", "shared_w4", "shared_tier2")  # (TierKind)
+
+
+def _tier_entry(v):
+    return (TIER_KINDS[v[0]], v[1], v[2], v[3], v[4], v[5], bool(v[6]), bool(v[7]))
+
+
+def tier_build_entry(list_, k):
+    """entry k of a list of tier_builds.hpp, or of the emulator's stand-ins (TIER_STANDINS): (kind, nx, nu, nh, rp, qr, srefs, spec) -- the fields a list
+    does not have are zero --, or None"""
+    out = (C.c_int * 8)()
+    return _tier_entry(out) if lib().emu_tier_build_entry((TIER_LISTS + TIER_STANDINS).index(list_), k, out) else None
+
+
+def tier_build(list_, nx, nu, N, rmax=0, rfull=0, tri=0, ric=0, q1regs=0, lds_total=0, stage_refs=0, lane_spec=0, tier2=0, specialised=True):
+    """the library's pick from a list of tier_builds.hpp (pick_first_tier, pick_second_tier, pick_lane, pick_lane_shared, pick_shared) for a plan with
+    these fields, as tier_build_entry reports an entry, or None"""
+    f = (C.c_int * 12)(nx, nu, N, rmax, rfull, tri, ric, q1regs, lds_total, stage_refs, lane_spec, tier2)
+    out = (C.c_int * 8)()
+    return _tier_entry(out) if lib().emu_tier_build(TIER_LISTS.index(list_), f, int(specialised), out) else None
+
+
+def last_tier_run():
+    """what the last lmpc_solve / lmpc_solve_shared ran: dict(first, second, lane, lane_shared, shared, shared_second) of entries as tier_build_entry
+    reports them; None: that launch did not run"""
+    v = (C.c_int * 54)()
+    lib().emu_last_tier_run(v)
+    return {name: (_tier_entry(v[9 * i + 1:9 * i + 9]) if v[9 * i] else None)
+            for i, name in enumerate(("first", "second", "lane", "lane_shared", "shared", "shared_second"))}
+
+
+def front_end(A, B, N, costs, cstrs, batch=1, initial_state=None, cost_refs=None, row_rhs=None, bounds=None, cost_weights=None):
+    """front_end.hpp on the plan of a controller with these per-solve inputs (arguments as lmpc_solve; A, B: the systems, or None): dict(axis, lane: what
+    axis_solver_covers and lane_pass_covers answer, reroute: None, or the (two_tier, dense, lds_total, tri, ric, rcap) of weights_layout, host_plan: the
+    fields of the HostPlan weights_layout reads -- dense, safe_two_tier, and (total, tri, ric, rcap) of lds_safe and lds_full)"""
+    _sync_options()
+    keep = [np.ascontiguousarray(v, dtype=np.float64) if v is not None else None for v in (row_rhs, *(bounds or (None, None)))]
+    lib().emu_set_instance_rows(*[_capi.dptr(v) if v is not None else C.c_void_p() for v in keep])
+    refs = {int(k): np.ascontiguousarray(v, dtype=np.float64) for k, v in (cost_refs or {}).items()}
+    for k in range(8):
+        lib().emu_set_cost_reference(k, _capi.dptr(refs[k]) if k in refs else C.c_void_p())
+    ws = _set_weights(cost_weights)
+    try:
+        Ab = Bb = None
+        if A is not None:
+            Ab, Bb, _, _ = _batchify(A, B, np.zeros(np.asarray(A).shape[-1]), np.zeros(np.asarray(A).shape[-1]))
+        nx, nu = (Bb.shape[2], Bb.shape[1]) if A is not None else (None, None)
+        cc = _capi.pack_costs(costs, keep)
+        kk = _capi.pack_cstrs(cstrs, keep)
+        dims = _capi.Dims(nx, nu, N, batch)
+        isd = C.c_void_p()
+        if initial_state is not None:
+            Rm, rv = _capi.fcol(initial_state["R"]), _capi.fcol(initial_state["r"])
+            keep.extend([Rm, rv])
+            isd = C.byref(_capi.InitialStateDesc(_capi.dptr(Rm), _capi.dptr(rv)))
+        out = (C.c_int * 19)()
+        rc = lib().emu_front_end(C.byref(dims), len(costs), cc, len(cstrs), kk, isd, _capi.dptr(Ab), _capi.dptr(Bb), out)
+        if rc != 0:
+            raise RuntimeError("emu_front_end rc=%d" % rc)
+        return dict(axis=bool(out[0]), lane=bool(out[1]), reroute=tuple(out[3:9]) if out[2] else None,
+                    host_plan=dict(dense=bool(out[9]), safe_two_tier=bool(out[10]), lds_safe=tuple(out[11:15]), lds_full=tuple(out[15:19])))
+    finally:
+        del ws
+        _clear_weights()
+        lib().emu_set_instance_rows(C.c_void_p(), C.c_void_p(), C.c_void_p())
+        for k in range(8):
+            lib().emu_set_cost_reference(k, C.c_void_p())
+
+
 def _sync_options():
     """hand _capi.OPTIONS (what BatchLMPC would pass to copra_batch_create_with_options) to the harness"""
     o = _capi.make_options()

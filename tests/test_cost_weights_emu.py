@@ -1,7 +1,7 @@
 """Per-instance cost weights (copra_batch_set_cost_weights) on the kernel BODIES, run lane by lane on the CPU (tests/emu) against the oracle run
 with each instance's own weights (tests/cost_weights_cases.py): the builds of the (instance, axis)-per-lane solver that rebuild their tables from
 the instance's weights (lmpc_axis.hpp, WTS: the families first_w and list_w of axis_builds.hpp), the routing that keeps every kernel with the
-creation weights in its tables away (copra_hip.hip: axis_solver_wanted, lane_pass_wanted, weights_route -- restated in tests/emu/emu_harness.cpp),
+creation weights in its tables away (copra_amd/csrc/front_end.hpp: axis_solver_covers, lane_pass_covers, weights_layout -- the library's and the emulator's),
 and cost_weights(P, t, inst) of the generic bodies (lmpc_fused.hpp, islmpc_fused.hpp, lmpc_large.hpp).
 
 Measures: RTOL = 1e-6 with the suite's floor of 1e-3.  Scattered weights (log-uniform over two decades per row) are compared norm-wise per instance

@@ -1405,12 +1405,12 @@ def test_riccati_factor_tier_with_a_run_time_horizon(emu, oracle, shape):
     (plan_builder.hpp::ric_aot_shape): the plan takes the tier by itself, statuses and BOTH iteration counters equal the oracle's,
     controls to 1e-9 -- incl. the lane pass's hand-over, a tight workload that steps down to the LDS-Q1 layout, and the tier alone."""
     from copra_amd import workloads
-    import test_gpu_parity as G
+    import controller_cases
     b = 24 if shape.startswith("planar") else 70  # (the planar cases walk long active-set paths: 20 - 40 iterations per instance)
     wl = {"com_12": lambda: workloads.com_preview(b, N=12, seed=5), "com_5": lambda: workloads.com_preview(b, N=5, seed=6),
           "com_21": lambda: workloads.com_preview(b, N=21, seed=7),
           "com_18_tight": lambda: workloads.com_preview(b, N=18, seed=8, v_max=0.3, u_max=1.5),
-          "planar_16": lambda: G._planar_integrator(b, 16), "planar_30": lambda: G._planar_integrator(b, 30, seed=3),
+          "planar_16": lambda: controller_cases.planar_integrator(b, 16), "planar_30": lambda: controller_cases.planar_integrator(b, 30, seed=3),
           "fallingmass_48": lambda: workloads.double_integrator(b, N=48), "fallingmass_64": lambda: workloads.double_integrator(b, N=64)}[shape]()
     args = (wl["A"], wl["B"], wl["d"], wl["x0"], wl["N"], wl["costs"], wl["cstrs"])
     ro = oracle.lmpc_solve_batch(*args, nthreads=8)
