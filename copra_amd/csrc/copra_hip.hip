@@ -433,45 +433,40 @@ static copra_status_t ensure_lane_buffers(copra_batch* h, bool need_ws)
 {
     const FusedPlan& P = h->hp.plan;
     const size_t bp = ((size_t)P.batch + kWave - 1) / kWave * kWave + kWave; // (+ 64 spare columns: what lanes without an instance write)
-    // every buffer is tested on its own, and a failed attempt leaves NONE behind (round-3 advisor finding: with the counters allocated
-    // and the list not, the next call returned COPRA_OK with a null list)
+    // the missing buffers are built in locals and moved in together: a failed attempt leaves the handle as it was (the type guarantees it)
+    Dev<int> count, list, hist;
+    Dev<double> ws, ws2;
     hipError_t e = hipSuccess;
-    if (!h->d_lane_count || !h->d_lane_list || !h->d_lane_hist) {
-        (void)hipFree(h->d_lane_count);
-        (void)hipFree(h->d_lane_list);
-        (void)hipFree(h->d_lane_hist);
-        h->d_lane_count = h->d_lane_list = h->d_lane_hist = nullptr;
-        e = hipMalloc((void**)&h->d_lane_count, 4 * sizeof(int)); // [cur | other]: instances left to the tier; [2 + cur | 2 + other]: instances ended by the pass's own steps
-        if (e == hipSuccess) e = hipMemset(h->d_lane_count, 0, 4 * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_lane_list, bp * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_lane_hist, kLaneHistBins * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(h->d_lane_hist, 0, kLaneHistBins * sizeof(int));
-        h->lane_cur = 1;
+    const bool need_list = !h->d_lane_count || !h->d_lane_list || !h->d_lane_hist;
+    if (need_list) {
+        e = (hipError_t)count.alloc(4); // [cur | other]: instances left to the tier; [2 + cur | 2 + other]: instances ended by the pass's own steps
+        if (e == hipSuccess) e = hipMemset(count, 0, 4 * sizeof(int));
+        if (e == hipSuccess) e = (hipError_t)list.alloc(bp);
+        if (e == hipSuccess) e = (hipError_t)hist.alloc(kLaneHistBins);
+        if (e == hipSuccess) e = hipMemset(hist, 0, kLaneHistBins * sizeof(int));
     }
     if (e == hipSuccess && need_ws && !h->d_lane_ws) // (the shared-model form of the pass has no sweep: no workspace)
-        e = hipMalloc((void**)&h->d_lane_ws, (size_t)P.N * lane_ws_rows(P.nx, P.nu) * bp * sizeof(double));
+        e = (hipError_t)ws.alloc((size_t)P.N * lane_ws_rows(P.nx, P.nu) * bp);
     const bool hand_over = P.lds.ricC && !h->hp.opt.no_lane_handover && (h->hp.opt.no_lane_spec || h->ad.lane_form_handover); // (launch_lane_pass: the form of the pass that hands blocks over)
     if (e == hipSuccess && need_ws && hand_over && !h->d_lane_ws2) { // (the hand-over blocks: what only the first tier reads, instance-major)
         // (round-5 advisor: 126 MB at 65 536 instances -- without room for them the pass keeps its speculating form, which needs none, instead of
-        //  being switched off for good with everything else freed)
-        if (hipMalloc((void**)&h->d_lane_ws2, bp * (size_t)lane_ws2_doubles(P.nx, P.nu, P.N) * sizeof(double)) != hipSuccess) {
+        //  being switched off for good)
+        if (ws2.alloc(bp * (size_t)lane_ws2_doubles(P.nx, P.nu, P.N)) != 0) {
             (void)hipGetLastError();
-            h->d_lane_ws2 = nullptr;
             if (h->hp.opt.no_lane_spec) e = hipErrorOutOfMemory; // (no other form allowed: the tier alone)
             else h->ad.lane_form_handover = false, h->ad.lane_ws2_failed = true;
         }
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(h->d_lane_count);
-        (void)hipFree(h->d_lane_list);
-        (void)hipFree(h->d_lane_hist);
-        (void)hipFree(h->d_lane_ws);
-        (void)hipFree(h->d_lane_ws2);
-        h->d_lane_count = h->d_lane_list = h->d_lane_hist = nullptr;
-        h->d_lane_ws = h->d_lane_ws2 = nullptr;
         return fail(COPRA_ERR_HIP, std::string("one-instance-per-lane pass: ") + hipGetErrorString(e));
     }
+    if (need_list) {
+        h->d_lane_count = std::move(count), h->d_lane_list = std::move(list), h->d_lane_hist = std::move(hist);
+        h->lane_cur = 1;
+    }
+    if (ws) h->d_lane_ws = std::move(ws);
+    if (ws2) h->d_lane_ws2 = std::move(ws2);
     return COPRA_OK;
 }
 // ... and what the (instance, axis)-per-lane solver needs on top of the pass's list, under the same contract.  false: no room on the device -- the
@@ -479,34 +474,30 @@ static copra_status_t ensure_lane_buffers(copra_batch* h, bool need_ws)
 static bool ensure_axis_buffers(copra_batch* h, const FusedPlan& P)
 {
     bool ok = ensure_lane_buffers(h, false) == COPRA_OK;
+    Dev<int> list2, count2, acc;
     hipError_t e = hipSuccess;
-    if (ok && (!h->d_axis_list2 || !h->d_axis_count2)) { // the second chance's own list (the first tier's, then) and its length
-        (void)hipFree(h->d_axis_list2);
-        (void)hipFree(h->d_axis_count2);
-        h->d_axis_list2 = h->d_axis_count2 = nullptr;
-        e = hipMalloc((void**)&h->d_axis_list2, ((size_t)P.batch + 64) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_axis_count2, 4 * sizeof(int)); // ([0]: entries; [2]: instances its own steps ended, as d_lane_count)
-        if (e == hipSuccess) e = hipMemset(h->d_axis_count2, 0, 4 * sizeof(int));
+    const bool need_list2 = !h->d_axis_list2 || !h->d_axis_count2;
+    if (ok && need_list2) { // the second chance's own list (the first tier's, then) and its length
+        e = (hipError_t)list2.alloc((size_t)P.batch + 64);
+        if (e == hipSuccess) e = (hipError_t)count2.alloc(4); // ([0]: entries; [2]: instances its own steps ended, as d_lane_count)
+        if (e == hipSuccess) e = hipMemset(count2, 0, 4 * sizeof(int));
     }
     if (ok && e == hipSuccess && !h->d_axis_acc) { // (one word per instance on spare lanes, at most one per nu waves: sized for the batch once)
         int spare = 0;
         const size_t words = (size_t)axis_grid(P.nu, P.batch, spare) / (size_t)P.nu + 2;
-        e = hipMalloc((void**)&h->d_axis_acc, words * sizeof(int));
-        if (e == hipSuccess) e = hipMemset(h->d_axis_acc, 0, words * sizeof(int));
+        e = (hipError_t)acc.alloc(words);
+        if (e == hipSuccess) e = hipMemset(acc, 0, words * sizeof(int));
     }
     if (!ok || e != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(h->d_axis_list2);
-        (void)hipFree(h->d_axis_count2);
-        (void)hipFree(h->d_axis_acc);
-        h->d_axis_list2 = h->d_axis_count2 = h->d_axis_acc = nullptr;
         h->ad.axis_off = true;
         return false;
     }
+    if (need_list2) h->d_axis_list2 = std::move(list2), h->d_axis_count2 = std::move(count2);
+    if (acc) h->d_axis_acc = std::move(acc);
     if (!h->h_lane_seen) {
-        if (hipHostMalloc((void**)&h->h_lane_seen, 4 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        if (h->h_lane_seen.alloc(4) != 0) {
             (void)hipGetLastError();
-            h->h_lane_seen = nullptr;
         } else {
             h->h_lane_seen[0] = h->h_lane_seen[1] = h->h_lane_seen[2] = h->h_lane_seen[3] = 0;
             if (hipHostGetDevicePointer((void**)&h->d_lane_seen, h->h_lane_seen, 0) != hipSuccess) {
@@ -819,10 +810,8 @@ copra_status_t prepare_riccati(copra_batch* h)
     const bool refs = own_references(h); // per-instance cost references: q_k differs per instance, which only the streaming kernel evaluates
     if (h->ric_built && h->ric_all_bounds == all_bounds && h->ric_refs == refs) return COPRA_OK;
     h->ric_refs = refs;
-    for (void* q : h->ric_dev) (void)hipFree(q);
-    h->ric_dev.clear();
-    (void)hipFree(h->d_ric_ws);
-    h->d_ric_ws = nullptr;
+    h->ric_dev.reset(); // (the tables of the plan that build_stage_plan replaces: freed here, before it, as the free is the wait for a solve that reads them)
+    h->d_ric_ws.reset();
     build_stage_plan(h->hp, h->hs, all_bounds);
     h->ric_built = false; // (set once every table and the workspace are on the device: a failed attempt must not look prepared)
     h->ric_all_bounds = all_bounds;
@@ -831,21 +820,11 @@ copra_status_t prepare_riccati(copra_batch* h)
         return COPRA_OK;
     }
     HostStagePlan& hs = h->hs;
-    hipError_t e = hipSuccess;
-    auto upi = [&](const std::vector<int>& v) -> const int* {
-        int* dptr = nullptr;
-        hipError_t r = upload(&dptr, v);
-        if (r != hipSuccess && e == hipSuccess) e = r;
-        h->ric_dev.push_back(dptr);
-        return dptr;
-    };
-    auto upd = [&](const std::vector<double>& v) -> const double* {
-        double* dptr = nullptr;
-        hipError_t r = upload(&dptr, v);
-        if (r != hipSuccess && e == hipSuccess) e = r;
-        h->ric_dev.push_back(dptr);
-        return dptr;
-    };
+    // the tables and the workspace are built in locals and moved in together: a failed attempt leaves none behind (the type guarantees it)
+    Bag tables;
+    Dev<double> ws;
+    auto upi = [&](const std::vector<int>& v) -> const int* { return tables.add(v.size(), &v); };
+    auto upd = [&](const std::vector<double>& v) -> const double* { return tables.add(v.size(), &v); };
     StagePlan& sp = hs.sp;
     sp.cls_of_stage = upi(hs.cls_of_stage);
     sp.stage_row0 = upi(hs.stage_row0);
@@ -881,6 +860,7 @@ copra_status_t prepare_riccati(copra_batch* h)
     const size_t lds_bytes = (size_t)(h->ric_fast ? sp.fast_lds_doubles : sp.lds_doubles) * sizeof(double);
     const void* ric_fn = h->ric_fast ? reinterpret_cast<const void*>(copra_lmpc_riccati_mfma_kernel)
                                      : reinterpret_cast<const void*>(select_riccati_kernel(sp.nx, sp.nu));
+    hipError_t e = (hipError_t)tables.error();
     if (e == hipSuccess) e = lds_opt_in(ric_fn, lds_bytes);
     int dev = 0, cus = 256, per_cu = 0;
     hipDeviceProp_t prop;
@@ -896,25 +876,22 @@ copra_status_t prepare_riccati(copra_batch* h)
     const int batch = h->hp.plan.batch > 0 ? h->hp.plan.batch : 1;
     h->ric_grid = (int)(g < batch ? g : batch);
     if (e == hipSuccess) // the streaming kernel's workspace | the LDS-resident kernel's stage records (all but a ring of four wait there: N x 107 doubles per wave)
-        e = hipMalloc((void**)&h->d_ric_ws, (size_t)h->ric_grid * (h->ric_fast ? (size_t)sp.N * kRfKStride : (size_t)sp.ws_total) * sizeof(double));
-    sp.ws = h->ric_fast ? nullptr : h->d_ric_ws;
-    sp.rec_ws = h->ric_fast ? h->d_ric_ws : nullptr;
-    if (e == hipSuccess && !h->d_ric_next) e = hipMalloc((void**)&h->d_ric_next, sizeof(int));
+        e = (hipError_t)ws.alloc((size_t)h->ric_grid * (h->ric_fast ? (size_t)sp.N * kRfKStride : (size_t)sp.ws_total));
+    sp.ws = h->ric_fast ? nullptr : ws.get();
+    sp.rec_ws = h->ric_fast ? ws.get() : nullptr;
+    if (e == hipSuccess && !h->d_ric_next) e = (hipError_t)h->d_ric_next.alloc(1);
     sp.next_instance = h->d_ric_next;
     if (h->hp.opt.debug)
         fprintf(stderr, "[copra] riccati path (%s): %d classes, %d rows, grid %d (%d per CU), %zu B LDS, %lld B workspace per wave\n",
             h->ric_fast ? "LDS-resident, MFMA" : hs.fast_why.c_str(), sp.ncls, sp.m, h->ric_grid, per_cu, lds_bytes,
             h->ric_fast ? 0LL : sp.ws_total * 8LL);
     if (e != hipSuccess) {
-        for (void* q : h->ric_dev) (void)hipFree(q);
-        h->ric_dev.clear();
-        (void)hipFree(h->d_ric_ws);
-        h->d_ric_ws = nullptr;
         h->hs.eligible = false;
         h->hs.why = "device tables of the stage plan could not be allocated";
         (void)hipGetLastError();
         return fail(COPRA_ERR_HIP, std::string("riccati path: ") + hipGetErrorString(e));
     }
+    h->ric_dev = std::move(tables), h->d_ric_ws = std::move(ws);
     h->ric_built = true;
     return COPRA_OK;
 }
@@ -997,16 +974,16 @@ static copra_status_t create_common(copra_batch_t** out, const copra_dims_t* dim
     auto chk = [&](hipError_t r) {
         if (e == hipSuccess) e = r;
     };
-    chk(upload(&h->d_row_step, h->hp.row_step));
-    chk(upload(&h->d_row_ekind, h->hp.row_ekind));
-    chk(upload(&h->d_row_eoff, h->hp.row_eoff));
-    chk(upload(&h->d_row_gkind, h->hp.row_gkind));
-    chk(upload(&h->d_row_goff, h->hp.row_goff));
-    chk(upload(&h->d_row_f, h->hp.row_f));
-    chk(upload(&h->d_row_prev, h->hp.row_prev));
-    chk(upload(&h->d_params, h->hp.params));
-    chk(upload(&h->d_lb, h->hp.lb));
-    chk(upload(&h->d_ub, h->hp.ub));
+    chk(upload(h->d_row_step, h->hp.row_step));
+    chk(upload(h->d_row_ekind, h->hp.row_ekind));
+    chk(upload(h->d_row_eoff, h->hp.row_eoff));
+    chk(upload(h->d_row_gkind, h->hp.row_gkind));
+    chk(upload(h->d_row_goff, h->hp.row_goff));
+    chk(upload(h->d_row_f, h->hp.row_f));
+    chk(upload(h->d_row_prev, h->hp.row_prev));
+    chk(upload(h->d_params, h->hp.params));
+    chk(upload(h->d_lb, h->hp.lb));
+    chk(upload(h->d_ub, h->hp.ub));
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
     { // result slab [U | X | status | iter], every part 256-byte aligned.  (The slab a multi-GPU caller hands in through
       //  copra_batch_set_outputs is laid out [U | status | iter | X] instead -- copra_amd/sharding.py: there the small parts come first so
@@ -1016,19 +993,19 @@ static copra_status_t create_common(copra_batch_t** out, const copra_dims_t* dim
         h->off_status = h->off_traj + up(b * P.X * sizeof(double));
         h->off_iter = h->off_status + up(b * sizeof(int));
         h->results_bytes = h->off_iter + up(b * 2 * sizeof(int));
-        chk(hipMalloc((void**)&h->d_results, h->results_bytes));
+        chk((hipError_t)h->d_results.alloc(h->results_bytes));
         if (h->d_results) {
-            h->d_control = reinterpret_cast<double*>(h->d_results);
+            h->d_control = reinterpret_cast<double*>(h->d_results.get());
             h->d_traj = reinterpret_cast<double*>(h->d_results + h->off_traj);
             h->d_status = reinterpret_cast<int*>(h->d_results + h->off_status);
             h->d_iter = reinterpret_cast<int*>(h->d_results + h->off_iter);
         }
-        if (h->results_bytes <= kSmallSlab) chk(hipHostMalloc((void**)&h->h_results, h->results_bytes, hipHostMallocDefault));
+        if (h->results_bytes <= kSmallSlab) chk((hipError_t)h->h_results.alloc(h->results_bytes));
     }
     if (is) {
-        chk(upload(&h->d_isR, h->hp.isR));
-        chk(upload(&h->d_isr, h->hp.isr));
-        chk(hipMalloc((void**)&h->d_x0opt, b * P.nx * sizeof(double)));
+        chk(upload(h->d_isR, h->hp.isR));
+        chk(upload(h->d_isr, h->hp.isr));
+        chk((hipError_t)h->d_x0opt.alloc(b * P.nx));
     }
     if (h->hp.ric_only) { // only the Riccati interior-point kernels cover this size: the controller must be stage-wise
         const copra_status_t rr = prepare_riccati(h);
@@ -1046,12 +1023,12 @@ static copra_status_t create_common(copra_batch_t** out, const copra_dims_t* dim
                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->hp.lds_bytes));
         h->large_grid = large_grid(h->hp.opt, reinterpret_cast<const void*>(h->large_fn), P.batch > 0 ? P.batch : 1,
             P.large.threads, h->hp.lds_bytes);
-        chk(hipMalloc((void**)&h->d_ws, (size_t)h->large_grid * (size_t)P.large.ws_total * sizeof(double)));
+        chk((hipError_t)h->d_ws.alloc((size_t)h->large_grid * (size_t)P.large.ws_total));
     }
     h->packed = (h->hp.large || h->hp.plan.lds.tri || h->hp.opt.no_packed) ? 0 // (the packed bodies are square-layout)
         : packed_width(is ? P.nx + P.n : P.n, P.nx * (P.nx + P.nu + 1), P.rfull > 0, h->hp.lds_bytes);
-    chk(hipMalloc((void**)&h->d_ovf_count, 2 * sizeof(int)));
-    chk(hipMalloc((void**)&h->d_ovf_list, b * sizeof(int)));
+    chk((hipError_t)h->d_ovf_count.alloc(2));
+    chk((hipError_t)h->d_ovf_list.alloc(b));
     chk(hipEventCreate(&h->ev0));
     chk(hipEventCreate(&h->ev1));
     chk(hipEventCreate(&h->evm));
@@ -1067,59 +1044,14 @@ static copra_status_t create_common(copra_batch_t** out, const copra_dims_t* dim
 void copra_batch_destroy(copra_batch_t* h)
 {
     if (!h) return;
-    (void)hipFree(h->d_row_step);
-    (void)hipFree(h->d_row_ekind);
-    (void)hipFree(h->d_row_eoff);
-    (void)hipFree(h->d_row_gkind);
-    (void)hipFree(h->d_row_goff);
-    (void)hipFree(h->d_row_f);
-    (void)hipFree(h->d_row_prev);
-    (void)hipFree(h->d_warm);
-    (void)hipFree(h->d_params);
-    (void)hipFree(h->d_lb);
-    (void)hipFree(h->d_ub);
-    (void)hipFree(h->own_A);
-    (void)hipFree(h->own_B);
-    (void)hipFree(h->own_d);
-    (void)hipFree(h->own_x0);
-    (void)hipFree(h->d_results);
-    if (h->h_results) (void)hipHostFree(h->h_results);
-    (void)hipFree(h->d_prof);
-    (void)hipFree(h->d_isR);
-    (void)hipFree(h->d_isr);
-    (void)hipFree(h->d_x0opt);
-    (void)hipFree(h->own_x0lb);
-    (void)hipFree(h->own_x0ub);
+    // (the first of the frees that stood here waited for the device: nothing of this controller runs once its module and events go)
+    (void)hipDeviceSynchronize();
     if (h->jit_module) (void)hipModuleUnload(h->jit_module);
-    for (int k = 0; k < kMaxCosts; ++k) (void)hipFree(h->d_cost_p[k]), (void)hipFree(h->d_cost_w[k]), (void)hipFree(h->ref_sched[k].own);
-    (void)hipFree(h->d_row_f_inst);
-    (void)hipFree(h->d_lb_inst);
-    (void)hipFree(h->d_ub_inst);
-    (void)hipFree(h->d_ws);
-    for (void* q : h->ric_dev) (void)hipFree(q);
-    (void)hipFree(h->d_ric_ws);
-    (void)hipFree(h->d_ric_next);
-    (void)hipFree(h->d_ric_model);
-    (void)hipFree(h->d_shA);
-    (void)hipFree(h->d_shB);
-    (void)hipFree(h->d_shd);
-    (void)hipFree(h->d_model);
-    (void)hipFree(h->d_ovf_count);
-    (void)hipFree(h->d_ovf_list);
-    (void)hipFree(h->d_lane_count);
-    (void)hipFree(h->d_lane_list);
-    (void)hipFree(h->d_lane_hist);
-    (void)hipFree(h->d_axis_acc);
-    (void)hipFree(h->d_axis_list2);
-    (void)hipFree(h->d_axis_count2);
-    if (h->h_lane_seen) (void)hipHostFree(h->h_lane_seen);
-    (void)hipFree(h->d_lane_ws);
-    (void)hipFree(h->d_lane_ws2);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evm) (void)hipEventDestroy(h->evm);
     if (h->ev_plant) (void)hipEventDestroy(h->ev_plant);
-    delete h;
+    delete h; // (every Dev / PinnedBuf / Bag member frees its own)
 }
 
 copra_status_t copra_plan_check(const copra_dims_t* dims, int n_costs, const copra_cost_desc_t* costs, int n_cstrs,
@@ -1205,9 +1137,9 @@ copra_status_t copra_batch_set_shared_system(copra_batch_t* h, const double* A, 
     if (!h->shared && shared_model_runs_as_batch(h)) { // (a handle that is in shared-model mode stays there: its layouts have moved)
         const size_t b = (size_t)P.batch;
         if (!h->own_A) {
-            HIP_TRY(hipMalloc((void**)&h->own_A, b * nA * sizeof(double)));
-            HIP_TRY(hipMalloc((void**)&h->own_B, b * nB * sizeof(double)));
-            HIP_TRY(hipMalloc((void**)&h->own_d, b * nd * sizeof(double)));
+            OWN_TRY(h->own_A.alloc(b * nA));
+            OWN_TRY(h->own_B.alloc(b * nB));
+            OWN_TRY(h->own_d.alloc(b * nd));
         }
         HIP_TRY(hipMemcpy(h->own_A, h->shA.data(), nA * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->own_B, h->shB.data(), nB * sizeof(double), hipMemcpyHostToDevice));
@@ -1266,12 +1198,7 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
     const int np = 1 + nx + rtot;
     const ModelLayout m = model_layout(nx, nu, N, n, X, h->hp.lds_full.ldj, HP.mgen);
     const size_t need = (size_t)m.C2 + 2 * (size_t)n * (rtot > 0 ? rtot : 1);
-    if (!h->d_model || h->model_doubles < need) {
-        (void)hipFree(h->d_model);
-        h->d_model = nullptr;
-        HIP_TRY(hipMalloc((void**)&h->d_model, need * sizeof(double)));
-        h->model_doubles = need;
-    }
+    OWN_TRY(h->d_model.grow(need));
     const size_t nA = (size_t)nx * nx, nB = (size_t)nx * nu;
     std::vector<double> Ap(nA * np), Bp(nB * np), dp((size_t)nx * np), xp((size_t)nx * np, 0.0);
     for (int a = 0; a < np; ++a) {
@@ -1280,19 +1207,8 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
         std::copy(h->shd.begin(), h->shd.end(), dp.begin() + (size_t)a * nx);
         if (a >= 1 && a <= nx) xp[(size_t)a * nx + (a - 1)] = 1.0;
     }
-    std::vector<void*> owned;
-    hipError_t e = hipSuccess;
-    auto up = [&](const std::vector<double>& src) -> double* {
-        double* dst = nullptr;
-        hipError_t r = hipMalloc((void**)&dst, (src.empty() ? 1 : src.size()) * sizeof(double));
-        if (r == hipSuccess && !src.empty()) r = hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (r != hipSuccess && e == hipSuccess) e = r;
-        owned.push_back(dst);
-        return dst;
-    };
-    auto release = [&]() {
-        for (void* q : owned) (void)hipFree(q);
-    };
+    Bag probes; // (what the probe launches read and write: released below, after them)
+    auto up = [&](const std::vector<double>& src) -> double* { return probes.add(src.size(), &src); };
     FusedPlan P = device_plan(h);
     P.A = up(Ap), P.B = up(Bp), P.d = up(dp), P.x0 = up(xp);
     for (int t = 0; t < HP.ncost; ++t) { // probe references of the costs that have per-instance ones
@@ -1307,8 +1223,8 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
     P.lb_inst = P.ub_inst = nullptr;
     double* dQ = up(std::vector<double>((size_t)n * n));
     double* dC = up(std::vector<double>((size_t)n * np));
+    hipError_t e = (hipError_t)probes.error();
     if (e != hipSuccess) {
-        release();
         return fail(COPRA_ERR_HIP, std::string("shared-model prepare: ") + hipGetErrorString(e));
     }
     P.batch = np;
@@ -1368,24 +1284,17 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
                 hipMemcpyHostToDevice);
         h->model_rtot = rtot;
     }
-    release();
+    probes.reset(); // freed after the launches: the free is the wait when one of them failed before the synchronisation
     if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("shared-model prepare: ") + hipGetErrorString(e));
     if (h->shared_ric) { // the stage records of the shared system: one run of the Riccati-factor body (FusedPlan::ric_model_out)
         int oBk, oG, oNb;
         const size_t count = (size_t)ric_model_offsets(nx, nu, N, HP.mgen, oBk, oG, oNb);
-        if (!h->d_ric_model) HIP_TRY(hipMalloc((void**)&h->d_ric_model, count * sizeof(double)));
-        std::vector<void*> own2;
-        hipError_t e2 = hipSuccess;
-        auto up2 = [&](const std::vector<double>& src) -> double* {
-            double* dst = nullptr;
-            hipError_t r = hipMalloc((void**)&dst, src.size() * sizeof(double));
-            if (r == hipSuccess) r = hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice);
-            if (r != hipSuccess && e2 == hipSuccess) e2 = r;
-            own2.push_back(dst);
-            return dst;
-        };
+        if (!h->d_ric_model) OWN_TRY(h->d_ric_model.alloc(count));
+        Bag sys; // (the system of the one launch below)
+        auto up2 = [&](const std::vector<double>& src) -> double* { return sys.add(src.size(), &src); };
         FusedPlan R = device_plan(h);
         R.A = up2(h->shA), R.B = up2(h->shB), R.d = up2(h->shd), R.x0 = up2(std::vector<double>((size_t)nx, 0.0));
+        hipError_t e2 = (hipError_t)sys.error();
         for (int t = 0; t < kMaxCosts; ++t) R.cost_p[t] = nullptr;
         R.row_f_inst = nullptr;
         R.lb_inst = R.ub_inst = nullptr;
@@ -1402,7 +1311,7 @@ static copra_status_t prepare_shared_model(copra_batch* h, hipStream_t s)
             e2 = hipGetLastError();
         }
         if (e2 == hipSuccess) e2 = hipStreamSynchronize(s);
-        for (void* q : own2) (void)hipFree(q);
+        sys.reset(); // freed after the launch: the free is the wait when the synchronisation was not reached
         if (e2 != hipSuccess) return fail(COPRA_ERR_HIP, std::string("shared-model prepare (Riccati records): ") + hipGetErrorString(e2));
     }
     h->model_dirty = false;
@@ -1856,11 +1765,11 @@ copra_status_t copra_batch_dump_qp(copra_batch_t* h, int instance, double* Q, do
     if (h->hp.ric_only)
         return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_dump_qp: the condensed QP of a controller this size is never formed on the device (stage-wise Riccati path)");
     const int n = HP.initial_state ? HP.nx + HP.n : HP.n, mg = HP.mgen;
-    double *dQ = nullptr, *dc = nullptr, *dA = nullptr, *db = nullptr;
-    HIP_TRY(hipMalloc((void**)&dQ, (size_t)n * n * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&dc, (size_t)n * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&dA, (size_t)(mg ? mg : 1) * n * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&db, (size_t)(mg ? mg : 1) * sizeof(double)));
+    Dev<double> dQ, dc, dA, db; // freed on every way out; on one between the launch and its synchronisation the free is the wait
+    OWN_TRY(dQ.alloc((size_t)n * n));
+    OWN_TRY(dc.alloc((size_t)n));
+    OWN_TRY(dA.alloc((size_t)(mg ? mg : 1) * n));
+    OWN_TRY(db.alloc((size_t)(mg ? mg : 1)));
     FusedPlan P = device_plan(h);
     P.inst_offset = instance;
     P.dump_instance = instance;
@@ -1913,10 +1822,6 @@ copra_status_t copra_batch_dump_qp(copra_batch_t* h, int instance, double* Q, do
             if (ub) ub[i] = (i < off) ? u0[(size_t)i] : h->hp.ub[(size_t)(i - off)];
         }
     }
-    (void)hipFree(dQ);
-    (void)hipFree(dc);
-    (void)hipFree(dA);
-    (void)hipFree(db);
     return COPRA_OK;
 }
 

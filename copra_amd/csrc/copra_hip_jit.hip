@@ -205,16 +205,14 @@ copra_status_t copra_batch_specialise_checked(copra_batch_t* h, const char* cach
             if (er == hipSuccess) er = hipModuleGetFunction(&fl, modr, "copra_jit_lane");
             hipFunction_t flp = nullptr;
             if (er == hipSuccess) er = hipModuleGetFunction(&flp, modr, "copra_jit_lane_plain");
-            double* dparams = nullptr;
-            if (er == hipSuccess) er = upload(&dparams, trial.params); // (the stage-cost tables were appended)
+            Dev<double> dparams;
+            if (er == hipSuccess) er = upload(dparams, trial.params); // (the stage-cost tables were appended)
             if (er != hipSuccess) {
                 (void)hipGetLastError();
                 (void)hipModuleUnload(modr);
-                (void)hipFree(dparams);
                 return fail(COPRA_ERR_HIP, std::string("copra_batch_specialise (Riccati-factor tier): ") + hipGetErrorString(er));
             }
-            (void)hipFree(h->d_params);
-            h->d_params = dparams;
+            h->d_params = std::move(dparams); // (the old table is freed here: the free is the wait for a solve that reads it)
             h->hp = trial;
             h->packed = 0; // (one instance per wavefront on this tier)
             h->lds_attr_set = false;

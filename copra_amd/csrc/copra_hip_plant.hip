@@ -43,9 +43,9 @@ copra_status_t shared_model_on_device(copra_batch* h)
     if (h->d_shA && !h->sh_dev_stale) return COPRA_OK;
     const size_t nA = h->shA.size(), nB = h->shB.size(), nd = h->shd.size();
     if (!h->d_shA) {
-        HIP_TRY(hipMalloc((void**)&h->d_shA, nA * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->d_shB, nB * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->d_shd, nd * sizeof(double)));
+        OWN_TRY(h->d_shA.alloc(nA));
+        OWN_TRY(h->d_shB.alloc(nB));
+        OWN_TRY(h->d_shd.alloc(nd));
     }
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // (an advance that still reads the old model: once per model)
     HIP_TRY(hipMemcpy(h->d_shA, h->shA.data(), nA * sizeof(double), hipMemcpyHostToDevice));
@@ -109,7 +109,7 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
         P.A = h->A, P.B = h->B, P.d = h->d;
     }
     const size_t nd = (size_t)HP.batch * HP.nx;
-    if (!h->own_x0) HIP_TRY(hipMalloc((void**)&h->own_x0, nd * sizeof(double)));
+    if (!h->own_x0) OWN_TRY(h->own_x0.alloc(nd));
     P.x0 = h->x0; // (a caller's device buffer is read this once more, never written)
     P.x0_next = h->own_x0;
     P.w = w;
@@ -210,15 +210,13 @@ copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_ind
     if (ct.pstride && r != ct.pstride)
         return fail(COPRA_ERR_DOMAIN, std::string(who) + ": the controller evaluates this full-size cost step by step: r must be the rows of one step");
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
-    if (!h->d_cost_p[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_p[t], b * ct.prows * sizeof(double)));
+    if (!h->d_cost_p[t]) OWN_TRY(h->d_cost_p[t].alloc(b * ct.prows));
     if (!on_device) { // the library's copy: a window launch that still reads the old one first
         const size_t count = (per_instance ? b : 1) * (size_t)steps * r;
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        if (rs.own_doubles < count) {
-            (void)hipFree(rs.own);
-            rs.own = nullptr, rs.own_doubles = 0, rs.sched = nullptr;
-            HIP_TRY(hipMalloc((void**)&rs.own, count * sizeof(double)));
-            rs.own_doubles = count;
+        if (rs.own.count() < count) {
+            rs.sched = nullptr; // (it may be the copy that goes)
+            OWN_TRY(rs.own.alloc(count));
         }
         HIP_TRY(hipMemcpy(rs.own, sched, count * sizeof(double), hipMemcpyHostToDevice));
         sched = rs.own;

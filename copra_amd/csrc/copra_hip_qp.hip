@@ -58,18 +58,14 @@ copra_status_t copra_qp_solve_dense_batch(int batch, int n, int neq, int nineq, 
                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     }
     const size_t b = (size_t)batch;
-    std::vector<void*> owned;
-    auto release = [&]() {
-        for (void* p : owned) (void)hipFree(p);
-    };
+    Bag owned; // (a host caller's inputs and results, the workspace: released below, after the launch)
     hipError_t e = hipSuccess;
     auto to_dev = [&](const double* src, size_t count) -> const double* {
         if (on_device) return src;
-        double* dptr = nullptr;
-        hipError_t r = hipMalloc((void**)&dptr, (count ? count : 1) * sizeof(double));
+        double* dptr = owned.add<double>(count);
+        hipError_t r = (hipError_t)owned.error();
         if (r == hipSuccess && count) r = hipMemcpyAsync(dptr, src, count * sizeof(double), hipMemcpyHostToDevice, s);
         if (r != hipSuccess && e == hipSuccess) e = r;
-        owned.push_back(dptr);
         return dptr;
     };
     P.Q = to_dev(Q, b * n * n);
@@ -83,20 +79,12 @@ copra_status_t copra_qp_solve_dense_batch(int batch, int n, int neq, int nineq, 
     double* dx = x;
     int *dfail = failv, *diter = iter;
     if (!on_device) {
-        hipError_t r = hipMalloc((void**)&dx, b * n * sizeof(double));
-        if (r == hipSuccess) r = hipMalloc((void**)&dfail, b * sizeof(int));
-        if (r == hipSuccess) r = hipMalloc((void**)&diter, b * 2 * sizeof(int));
-        if (r != hipSuccess && e == hipSuccess) e = r;
-        owned.push_back(dx);
-        owned.push_back(dfail);
-        owned.push_back(diter);
+        dx = owned.add<double>(b * n), dfail = owned.add<int>(b), diter = owned.add<int>(b * 2);
     } else if (!diter) {
-        hipError_t r = hipMalloc((void**)&diter, b * 2 * sizeof(int));
-        if (r != hipSuccess && e == hipSuccess) e = r;
-        owned.push_back(diter);
+        diter = owned.add<int>(b * 2);
     }
-    if (e != hipSuccess) {
-        release();
+    if (e == hipSuccess) e = (hipError_t)owned.error();
+    if (e != hipSuccess) { // (copies may be in flight on s: the bag's free, at the return, is the wait)
         return fail(COPRA_ERR_HIP, std::string("copra_qp_solve_dense_batch: ") + hipGetErrorString(e));
     }
     P.x = dx;
@@ -108,14 +96,9 @@ copra_status_t copra_qp_solve_dense_batch(int batch, int n, int neq, int nineq, 
             reinterpret_cast<const void*>(copra_qp_dense_large_kernel_w4), threads, lds_bytes);
         auto dense_kernel = w4 ? copra_qp_dense_large_kernel_w4 : copra_qp_dense_large_kernel;
         const int grid = large_grid(default_options(), reinterpret_cast<const void*>(dense_kernel), batch, threads, lds_bytes);
-        double* ws = nullptr;
-        e = hipMalloc((void**)&ws, (size_t)grid * 2 * n * large_ld(n) * sizeof(double));
-        if (e != hipSuccess) {
-            release();
-            return fail(COPRA_ERR_HIP, std::string("copra_qp_solve_dense_batch: ") + hipGetErrorString(e));
-        }
-        owned.push_back(ws);
-        P.ws = ws;
+        P.ws = owned.add<double>((size_t)grid * 2 * n * large_ld(n));
+        e = (hipError_t)owned.error();
+        if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("copra_qp_solve_dense_batch: ") + hipGetErrorString(e));
         hipLaunchKernelGGL(dense_kernel, dim3((unsigned)grid), dim3((unsigned)threads), lds_bytes, s, P);
     } else {
         const int pw = default_options().no_packed ? 0 : packed_width(n, 0, false, lds_bytes);
@@ -138,8 +121,8 @@ copra_status_t copra_qp_solve_dense_batch(int batch, int n, int neq, int nineq, 
         if (e == hipSuccess) e = hipMemcpyAsync(failv, dfail, b * sizeof(int), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && iter) e = hipMemcpyAsync(iter, diter, b * 2 * sizeof(int), hipMemcpyDeviceToHost, s);
     }
-    if (e == hipSuccess && !owned.empty()) e = hipStreamSynchronize(s);
-    release();
+    if (e == hipSuccess && owned.size()) e = hipStreamSynchronize(s);
+    owned.reset(); // freed after the launch: the free is the wait when the synchronisation was not reached
     if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("copra_qp_solve_dense_batch: ") + hipGetErrorString(e));
     return COPRA_OK;
 }

@@ -78,14 +78,14 @@ copra_status_t copra_preview_update(int nx, int nu, int N, const double* A, cons
     if (nx <= 0 || nu <= 0 || N <= 0) return fail(COPRA_ERR_DOMAIN, "copra_preview_update: dimensions and number of steps must be positive");
     if (!A || !B || !d || !Phi || !Psi || !xi) return fail(COPRA_ERR_ARG, "copra_preview_update: null argument");
     const size_t X = (size_t)nx * (N + 1), U = (size_t)nu * N;
-    double *dA = nullptr, *dB = nullptr, *dd = nullptr, *dPhi = nullptr, *dPsi = nullptr, *dxi = nullptr, *dG = nullptr;
-    hipError_t e = hipMalloc((void**)&dA, (size_t)nx * nx * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dB, (size_t)nx * nu * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dd, (size_t)nx * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dPhi, X * nx * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dPsi, X * U * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dxi, X * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&dG, (size_t)N * nx * nu * sizeof(double));
+    Dev<double> dA, dB, dd, dPhi, dPsi, dxi, dG; // freed at the return: when a launch or a copy failed, after the launch -- the free is the wait
+    hipError_t e = (hipError_t)dA.alloc((size_t)nx * nx);
+    if (e == hipSuccess) e = (hipError_t)dB.alloc((size_t)nx * nu);
+    if (e == hipSuccess) e = (hipError_t)dd.alloc((size_t)nx);
+    if (e == hipSuccess) e = (hipError_t)dPhi.alloc(X * nx);
+    if (e == hipSuccess) e = (hipError_t)dPsi.alloc(X * U);
+    if (e == hipSuccess) e = (hipError_t)dxi.alloc(X);
+    if (e == hipSuccess) e = (hipError_t)dG.alloc((size_t)N * nx * nu);
     if (e == hipSuccess) e = hipMemcpy(dA, A, (size_t)nx * nx * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dB, B, (size_t)nx * nu * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dd, d, (size_t)nx * sizeof(double), hipMemcpyHostToDevice);
@@ -101,7 +101,6 @@ copra_status_t copra_preview_update(int nx, int nu, int N, const double* A, cons
     if (e == hipSuccess) e = hipMemcpy(Phi, dPhi, X * nx * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(Psi, dPsi, X * U * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(xi, dxi, X * sizeof(double), hipMemcpyDeviceToHost);
-    for (double* q : { dA, dB, dd, dPhi, dPsi, dxi, dG }) (void)hipFree(q);
     if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("copra_preview_update: ") + hipGetErrorString(e));
     return COPRA_OK;
 }
@@ -112,12 +111,11 @@ copra_status_t copra_batch_set_warm_start(copra_batch_t* h, int enable)
     if (h->hp.plan.initial_state || h->hp.large)
         return fail(COPRA_ERR_UNSUPPORTED, "the warm start belongs to the shared-model path (LMPC, at most 64 decision variables)");
     if (!enable) {
-        (void)hipFree(h->d_warm);
-        h->d_warm = nullptr;
+        h->d_warm.reset();
         return COPRA_OK;
     }
     const size_t count = (size_t)(h->hp.plan.batch > 0 ? h->hp.plan.batch : 1) * kWarmCap;
-    if (!h->d_warm) HIP_TRY(hipMalloc((void**)&h->d_warm, count * sizeof(int)));
+    OWN_TRY(h->d_warm.grow(count));
     HIP_TRY(hipMemset(h->d_warm, 0xff, count * sizeof(int))); // every entry -1: the first solve starts cold
     return COPRA_OK;
 }
@@ -184,11 +182,11 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
     }
     const size_t nA = b * P.nx * P.nx, nB = b * P.nx * P.nu, nd = b * P.nx;
     if (!h->own_A) {
-        HIP_TRY(hipMalloc((void**)&h->own_A, (nA ? nA : 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->own_B, (nB ? nB : 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->own_d, (nd ? nd : 1) * sizeof(double)));
+        OWN_TRY(h->own_A.alloc((nA ? nA : 1)));
+        OWN_TRY(h->own_B.alloc((nB ? nB : 1)));
+        OWN_TRY(h->own_d.alloc((nd ? nd : 1)));
     }
-    if (!h->own_x0) HIP_TRY(hipMalloc((void**)&h->own_x0, (nd ? nd : 1) * sizeof(double)));
+    if (!h->own_x0) OWN_TRY(h->own_x0.alloc((nd ? nd : 1)));
     HIP_TRY(hipMemcpy(h->own_A, A, nA * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->own_B, B, nB * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->own_d, d, nd * sizeof(double), hipMemcpyHostToDevice));
@@ -241,9 +239,9 @@ copra_status_t copra_batch_set_system_rowmajor_async(copra_batch_t* h, const dou
         }
     }
     if (!h->own_A) {
-        HIP_TRY(hipMalloc((void**)&h->own_A, (nA ? nA : 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->own_B, (nB ? nB : 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->own_d, (nd ? nd : 1) * sizeof(double)));
+        OWN_TRY(h->own_A.alloc((nA ? nA : 1)));
+        OWN_TRY(h->own_B.alloc((nB ? nB : 1)));
+        OWN_TRY(h->own_d.alloc((nd ? nd : 1)));
     }
     hipStream_t s = (hipStream_t)hip_stream;
     if (nA) hipLaunchKernelGGL(copra_rowmajor_to_colmajor_kernel, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, s, A, h->own_A, P.nx, P.nx, (long long)nA);
@@ -282,7 +280,7 @@ copra_status_t copra_batch_set_cost_reference(copra_batch_t* h, int cost_index, 
         return COPRA_OK;
     }
     const size_t count = (size_t)(P.batch > 0 ? P.batch : 1) * P.cost[cost_index].prows; // (a reference trajectory: rows x steps per instance)
-    if (!h->d_cost_p[cost_index]) HIP_TRY(hipMalloc((void**)&h->d_cost_p[cost_index], count * sizeof(double)));
+    if (!h->d_cost_p[cost_index]) OWN_TRY(h->d_cost_p[cost_index].alloc(count));
     HIP_TRY(hipMemcpy(h->d_cost_p[cost_index], p, count * sizeof(double), hipMemcpyHostToDevice));
     h->cost_p[cost_index] = h->d_cost_p[cost_index];
     return COPRA_OK;
@@ -316,7 +314,7 @@ copra_status_t copra_batch_set_cost_weights(copra_batch_t* h, int cost_index, co
                     return fail(COPRA_ERR_DOMAIN, "copra_batch_set_cost_weights: the weights of this full-size cost differ from step to step "
                                                   "(the controller evaluates it step by step: create it with copra_options_t::no_stage_refs)");
     }
-    if (!h->d_cost_w[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_w[t], b * rows * sizeof(double)));
+    if (!h->d_cost_w[t]) OWN_TRY(h->d_cost_w[t].alloc(b * rows));
     HIP_TRY(hipMemcpy(h->d_cost_w[t], w, b * rows * sizeof(double), hipMemcpyHostToDevice));
     h->cost_w[t] = h->d_cost_w[t];
     return COPRA_OK;
@@ -333,7 +331,7 @@ copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_ind
     // library's own buffer (a broadcast on the device: 66 MB at the headline's batch for a reference trajectory, ~ 10 us) and that
     // path is taken -- nothing that was derived from the creation-time p (tables of the plan builder, the shared model's c0) can go stale.
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), rows = (size_t)P.cost[t].prows;
-    if (!h->d_cost_p[t]) HIP_TRY(hipMalloc((void**)&h->d_cost_p[t], b * rows * sizeof(double)));
+    if (!h->d_cost_p[t]) OWN_TRY(h->d_cost_p[t].alloc(b * rows));
     double* const out = h->d_cost_p[t];
     if (p == out) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference_all: p aliases the library's buffer");
     h->ref_sched[t].sched = nullptr; // (a reference given by hand ends the cost's schedule)
@@ -367,20 +365,17 @@ copra_status_t copra_batch_set_constraint_rhs(copra_batch_t* h, int cstr_index, 
     const int row0 = h->hp.cstr_row0[(size_t)cstr_index];
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
     if (!h->d_row_f_inst) { // first use: every instance starts from the controller-wide right-hand sides
-        HIP_TRY(hipMalloc((void**)&h->d_row_f_inst, b * (size_t)P.mgen * sizeof(double)));
+        OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
         std::vector<double> rep(b * (size_t)P.mgen);
         for (size_t i = 0; i < b; ++i) std::copy(h->hp.row_f.begin(), h->hp.row_f.begin() + P.mgen, rep.begin() + i * P.mgen);
         HIP_TRY(hipMemcpy(h->d_row_f_inst, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     const double* src = f;
-    double* tmp = nullptr;
+    Dev<double> tmp; // freed at the return, after the launch that reads it: the free is the wait when the synchronisation was not reached
     if (!on_device) {
-        HIP_TRY(hipMalloc((void**)&tmp, b * (size_t)r * sizeof(double)));
+        OWN_TRY(tmp.alloc(b * (size_t)r));
         hipError_t e = hipMemcpy(tmp, f, b * (size_t)r * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            return fail(COPRA_ERR_HIP, std::string("copra_batch_set_constraint_rhs: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("copra_batch_set_constraint_rhs: ") + hipGetErrorString(e));
         src = tmp;
     }
     const long long total = (long long)P.batch * r * steps;
@@ -390,7 +385,6 @@ copra_status_t copra_batch_set_constraint_rhs(copra_batch_t* h, int cstr_index, 
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->last_stream);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) return fail(COPRA_ERR_HIP, std::string("copra_batch_set_constraint_rhs: ") + hipGetErrorString(e));
     return COPRA_OK; // (the shared-model factorisation does not depend on right-hand sides)
 }
@@ -401,8 +395,8 @@ copra_status_t copra_batch_set_control_bounds(copra_batch_t* h, const double* lo
     const FusedPlan& P = h->hp.plan;
     const size_t count = (size_t)(P.batch > 0 ? P.batch : 1) * P.n;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (!h->d_lb_inst) HIP_TRY(hipMalloc((void**)&h->d_lb_inst, count * sizeof(double)));
-    if (!h->d_ub_inst) HIP_TRY(hipMalloc((void**)&h->d_ub_inst, count * sizeof(double)));
+    if (!h->d_lb_inst) OWN_TRY(h->d_lb_inst.alloc(count));
+    if (!h->d_ub_inst) OWN_TRY(h->d_ub_inst.alloc(count));
     HIP_TRY(hipMemcpy(h->d_lb_inst, lower, count * sizeof(double), kind));
     HIP_TRY(hipMemcpy(h->d_ub_inst, upper, count * sizeof(double), kind));
     return COPRA_OK;
@@ -417,7 +411,7 @@ copra_status_t copra_batch_set_x0(copra_batch_t* h, const double* x0, int on_dev
         return COPRA_OK;
     }
     const size_t nd = (size_t)P.batch * P.nx;
-    if (!h->own_x0) HIP_TRY(hipMalloc((void**)&h->own_x0, (nd ? nd : 1) * sizeof(double)));
+    if (!h->own_x0) OWN_TRY(h->own_x0.alloc((nd ? nd : 1)));
     HIP_TRY(hipMemcpy(h->own_x0, x0, nd * sizeof(double), hipMemcpyHostToDevice));
     h->x0 = h->own_x0;
     return COPRA_OK;
@@ -516,8 +510,8 @@ copra_status_t copra_batch_set_initial_state_bounds(copra_batch_t* h, const doub
         return COPRA_OK;
     }
     if (!h->own_x0lb) {
-        HIP_TRY(hipMalloc((void**)&h->own_x0lb, (nd ? nd : 1) * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->own_x0ub, (nd ? nd : 1) * sizeof(double)));
+        OWN_TRY(h->own_x0lb.alloc((nd ? nd : 1)));
+        OWN_TRY(h->own_x0ub.alloc((nd ? nd : 1)));
     }
     HIP_TRY(hipMemcpy(h->own_x0lb, x0lb, nd * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->own_x0ub, x0ub, nd * sizeof(double), hipMemcpyHostToDevice));
@@ -549,7 +543,7 @@ copra_status_t copra_batch_phase_profile(copra_batch_t* h, int enable, long long
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_phase_profile: null handle");
     const size_t b = (size_t)(h->hp.plan.batch > 0 ? h->hp.plan.batch : 1);
     if (enable && !h->d_prof) {
-        HIP_TRY(hipMalloc((void**)&h->d_prof, b * 8 * sizeof(long long)));
+        OWN_TRY(h->d_prof.alloc(b * 8));
         HIP_TRY(hipMemset(h->d_prof, 0, b * 8 * sizeof(long long)));
     }
     if (cycles_out) {
@@ -557,10 +551,7 @@ copra_status_t copra_batch_phase_profile(copra_batch_t* h, int enable, long long
         HIP_TRY(hipStreamSynchronize(h->last_stream));
         HIP_TRY(hipMemcpy(cycles_out, h->d_prof, b * 8 * sizeof(long long), hipMemcpyDeviceToHost));
     }
-    if (!enable && h->d_prof) {
-        (void)hipFree(h->d_prof);
-        h->d_prof = nullptr;
-    }
+    if (!enable) h->d_prof.reset();
     return COPRA_OK;
 }
 
@@ -571,7 +562,7 @@ copra_status_t copra_batch_fine_profile(copra_batch_t* h, long long* out)
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_fine_profile: null handle");
     const size_t b = (size_t)(h->hp.plan.batch > 0 ? h->hp.plan.batch : 1);
     if (!h->d_prof_fine) {
-        HIP_TRY(hipMalloc((void**)&h->d_prof_fine, b * 32 * sizeof(long long)));
+        OWN_TRY(h->d_prof_fine.alloc(b * 32));
         HIP_TRY(hipMemset(h->d_prof_fine, 0xff, b * 32 * sizeof(long long)));
     }
     if (out) {

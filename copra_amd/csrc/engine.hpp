@@ -9,11 +9,14 @@
 //   copra_hip_packed16/32.hip  the one-wave bodies with 16 / 32 lanes per instance
 //   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp); reference
 //                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp)
+// and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
+// place in the library that allocates or frees.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
 #include "../../include/copra_hip.h"
+#include "device_mem.hpp"
 #include "packed_launch.hpp"
 #include "plan_builder.hpp"
 #include "stage_plan.hpp"
@@ -42,14 +45,33 @@ inline copra_status_t fail(copra_status_t code, const std::string& msg)
 hipError_t lds_opt_in(const void* fn, size_t bytes);
 #define LDS_OPT_IN(fn, bytes) HIP_TRY(lds_opt_in(reinterpret_cast<const void*>(fn), (bytes)))
 
+// The allocator policies of device_mem.hpp.  release() of device memory WAITS for the device: a temporary that a just-launched kernel
+// reads is kept alive by the release that follows the launch, so an owner's scope ends where that wait has to stand.
+struct DeviceMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void release(void* p) { (void)hipFree(p); }
+    static int copy_in(void* dst, const void* src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+};
+struct PinnedMem {
+    static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void release(void* p) { (void)hipHostFree(p); }
+};
 template <class T>
-hipError_t upload(T** dst, const std::vector<T>& src)
+using Dev = DevBuf<T, DeviceMem>;
+template <class T>
+using PinnedBuf = DevBuf<T, PinnedMem>;
+using Bag = DevBag<DeviceMem>;
+
+// HIP_TRY for what an owner returns: OWN_TRY(h->d_x.alloc(n)), OWN_TRY(h->d_x.grow(n))
+#define OWN_TRY(expr) HIP_TRY((hipError_t)(expr))
+
+// a plan table on the device (at least one element, so that an empty table still has an address)
+template <class T>
+hipError_t upload(Dev<T>& dst, const std::vector<T>& src)
 {
-    const size_t bytes = (src.empty() ? 1 : src.size()) * sizeof(T);
-    hipError_t e = hipMalloc((void**)dst, bytes);
-    if (e != hipSuccess) return e;
-    if (!src.empty()) e = hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
+    int e = dst.alloc(src.empty() ? 1 : src.size());
+    if (e == 0 && !src.empty()) e = DeviceMem::copy_in(dst, src.data(), src.size() * sizeof(T));
+    return (hipError_t)e;
 }
 
 // persistent grids of the workgroup-per-instance kernels (copra_hip.hip)
@@ -105,22 +127,22 @@ struct AdaptState {
 // A cost whose reference follows a schedule (copra_batch_set_reference_schedule): the tick writes its window into d_cost_p (copra_hip_plant.hip)
 struct RefSchedule {
     const double* sched = nullptr; // device: the caller's, or `own`; null: the cost has no schedule
-    double* own = nullptr; // the library's copy of a host schedule
-    size_t own_doubles = 0;
+    Dev<double> own; // the library's copy of a host schedule
     long long steps = 0;
     int r = 0, S = 0, offset = 0, per_instance = 0;
 };
 
+// Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
+// from the caller or a view into an owned block.  Nothing owned refers to anything else owned, so the order of destruction is free.
 struct copra_batch {
     HostPlan hp;
     AdaptState ad;
     // device copies of the plan tables
-    int *d_row_step = nullptr, *d_row_ekind = nullptr, *d_row_eoff = nullptr, *d_row_gkind = nullptr,
-        *d_row_goff = nullptr;
-    double *d_row_f = nullptr, *d_params = nullptr, *d_lb = nullptr, *d_ub = nullptr;
-    int *d_row_prev = nullptr, *d_warm = nullptr; // warm start of the shared-model path (copra_batch_set_warm_start)
+    Dev<int> d_row_step, d_row_ekind, d_row_eoff, d_row_gkind, d_row_goff;
+    Dev<double> d_row_f, d_params, d_lb, d_ub;
+    Dev<int> d_row_prev, d_warm; // warm start of the shared-model path (copra_batch_set_warm_start)
     // system (owned copies, or borrowed device pointers)
-    double *own_A = nullptr, *own_B = nullptr, *own_d = nullptr, *own_x0 = nullptr;
+    Dev<double> own_A, own_B, own_d, own_x0;
     int axis_order = 0; // the state order of this controller's systems as the (instance, axis)-per-lane solver sees it (FusedPlan::axis_order) ...
     bool axis_order_seen = false; // ... looked at when the first systems were set (see_axis_order, copra_hip.hip)
     bool shared_as_batch = false; // copra_batch_set_shared_system on a controller the (instance, axis)-per-lane solver takes: the model written out per instance (copra_hip.hip)
@@ -128,13 +150,13 @@ struct copra_batch {
     // results
     double *d_control = nullptr, *d_traj = nullptr; // (carved from ONE allocation, d_results: small batches fetch it with one copy)
     int *d_status = nullptr, *d_iter = nullptr;
-    unsigned char* d_results = nullptr;
+    Dev<unsigned char> d_results;
     size_t results_bytes = 0, off_traj = 0, off_status = 0, off_iter = 0;
-    unsigned char* h_results = nullptr; // pinned staging copy of the slab (batches whose slab is at most kSmallSlab bytes)
+    PinnedBuf<unsigned char> h_results; // pinned staging copy of the slab (batches whose slab is at most kSmallSlab bytes)
     // caller-provided device result buffers (copra_batch_set_outputs); override the engine-owned ones
     double *ext_control = nullptr, *ext_traj = nullptr;
     int *ext_status = nullptr, *ext_iter = nullptr;
-    int *d_ovf_count = nullptr, *d_ovf_list = nullptr; // two-tier queue (TWO counters, used in turn: begin_overflow_queue)
+    Dev<int> d_ovf_count, d_ovf_list; // two-tier queue (TWO counters, used in turn: begin_overflow_queue)
     int ovf_cur = 0; // the counter the last solve appended to
     bool ovf_clean[2] = { false, false }; // known to hold zero on the device
     // shared-model fast path: one (A, B, d) for the whole batch, factorised once (copra_batch_set_shared_system)
@@ -144,19 +166,18 @@ struct copra_batch {
     // and the batch-wide records
     bool has_lds_ric = false, shared_ric = false;
     LdsLayout lds_ric {};
-    double* d_ric_model = nullptr;
+    Dev<double> d_ric_model;
     int model_ref_off[kMaxCosts]; // columns of C2 per cost as prepared (-1: none)
-    size_t model_doubles = 0; // allocated size of d_model
     int model_rtot = 0; // columns of C2 / K2 as prepared
-    double *d_shA = nullptr, *d_shB = nullptr, *d_shd = nullptr, *d_model = nullptr;
+    Dev<double> d_shA, d_shB, d_shd, d_model;
     std::vector<double> shA, shB, shd;
     bool sh_dev_stale = true; // d_shA / d_shB / d_shd (the shared model as a plant, copra_hip_plant.hip) are older than shA / shB / shd
-    double *d_row_f_inst = nullptr, *d_lb_inst = nullptr, *d_ub_inst = nullptr; // per-instance rhs / control bounds
-    double* d_cost_p[kMaxCosts] = {}; // per-instance cost references (owned copies) ...
+    Dev<double> d_row_f_inst, d_lb_inst, d_ub_inst; // per-instance rhs / control bounds
+    Dev<double> d_cost_p[kMaxCosts]; // per-instance cost references (owned copies) ...
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
     RefSchedule ref_sched[kMaxCosts]; // ... which the tick rewrites for the costs that follow a schedule,
     long long sched_tick = 0; // at the controller's tick counter tau: the advances so far, or what copra_batch_schedule_seek set
-    double* d_cost_w[kMaxCosts] = {}; // per-instance cost weights (owned copies) ...
+    Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
     // weights): the layout it had is kept here and given back once the weights are restored (weights_route, copra_hip.hip)
@@ -174,21 +195,21 @@ struct copra_batch {
     int jit_lanes = 64; // lanes per instance the code object was compiled for
     int jit_tri = 0; // ... and whether for the factor-only layout
     // one-instance-per-lane pass in front of the Riccati-factor tier (lmpc_lane.hpp)
-    int *d_lane_count = nullptr, *d_lane_list = nullptr; // (two counters, used in turn like the overflow queue's)
-    int* d_lane_hist = nullptr; // histogram of the violated-row counts the pass leaves (kLaneHistBins; read once, before the first tier launch)
-    double* d_lane_ws = nullptr;
-    int* d_lane_seen = nullptr; // ... the same words as the device sees them
-    int* h_lane_seen = nullptr; // pinned: [2] the lengths of the last solves' first-tier lists as they arrive (ensure_axis_buffers; read by adapt_list_window into AdaptState)
-    int *d_axis_list2 = nullptr, *d_axis_count2 = nullptr; // the list the second chance of the (instance, axis)-per-lane solver appends to (the first tier's, then) and its length
-    int* d_axis_acc = nullptr; // lmpc_axis.hpp: the words in which the counters of instances on spare lanes meet (FusedPlan::axis_acc; zero between solves)
-    double* d_lane_ws2 = nullptr; // the instance-major hand-over blocks of the pass (FusedPlan::lane_ws2)
+    Dev<int> d_lane_count, d_lane_list; // (two counters, used in turn like the overflow queue's)
+    Dev<int> d_lane_hist; // histogram of the violated-row counts the pass leaves (kLaneHistBins; read once, before the first tier launch)
+    Dev<double> d_lane_ws;
+    int* d_lane_seen = nullptr; // ... the same words as the device sees them (a view of h_lane_seen)
+    PinnedBuf<int> h_lane_seen; // pinned: [2] the lengths of the last solves' first-tier lists as they arrive (ensure_axis_buffers; read by adapt_list_window into AdaptState)
+    Dev<int> d_axis_list2, d_axis_count2; // the list the second chance of the (instance, axis)-per-lane solver appends to (the first tier's, then) and its length
+    Dev<int> d_axis_acc; // lmpc_axis.hpp: the words in which the counters of instances on spare lanes meet (FusedPlan::axis_acc; zero between solves)
+    Dev<double> d_lane_ws2; // the instance-major hand-over blocks of the pass (FusedPlan::lane_ws2)
     int lane_cur = 0; // the counter the last solve appended to
     int packed = 0; // lanes per instance when several small problems share a wavefront (16 / 32; 0: one wave each)
     void (*large_fn)(const FusedPlan) = nullptr; // workgroup-per-instance kernel variant chosen at creation
-    double* d_ws = nullptr; // workgroup-per-instance kernel: [large_grid][ws_total] doubles (J, factor, Phi, ...)
+    Dev<double> d_ws; // workgroup-per-instance kernel: [large_grid][ws_total] doubles (J, factor, Phi, ...)
     int large_grid = 0;
     // InitialStateLMPC variant
-    double *d_isR = nullptr, *d_isr = nullptr, *d_x0opt = nullptr, *own_x0lb = nullptr, *own_x0ub = nullptr;
+    Dev<double> d_isR, d_isr, d_x0opt, own_x0lb, own_x0ub;
     const double *x0lb = nullptr, *x0ub = nullptr;
     // stage-wise Riccati interior-point path (copra_batch_select_solver; lmpc_riccati.hpp)
     int solver = COPRA_SOLVER_DEFAULT;
@@ -197,12 +218,12 @@ struct copra_batch {
     bool ric_refs = false; // ... decided for this state of the per-instance cost references
     bool ric_built = false; // hs describes this controller (eligible or not) ...
     bool ric_all_bounds = false; // ... with bound rows for every control
-    std::vector<void*> ric_dev; // device copies of its tables
-    double* d_ric_ws = nullptr;
-    int* d_ric_next = nullptr; // work-queue counter of the Riccati kernel
+    Bag ric_dev; // device copies of its tables
+    Dev<double> d_ric_ws;
+    Dev<int> d_ric_next; // work-queue counter of the Riccati kernel
     int ric_grid = 0;
-    long long* d_prof_fine = nullptr; // profiling builds only
-    long long* d_prof = nullptr; // optional per-instance phase cycle counts (copra_batch_enable_phase_profile)
+    Dev<long long> d_prof_fine; // profiling builds only
+    Dev<long long> d_prof; // optional per-instance phase cycle counts (copra_batch_enable_phase_profile)
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr; // start | end of the solve | end of its first launch (packet-borne timing)
     bool tier_timed = false; // evm was written by the last solve
     hipEvent_t ev_plant = nullptr; // orders copra_batch_advance on another stream behind the solve

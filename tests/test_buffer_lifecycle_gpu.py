@@ -1,0 +1,175 @@
+"""The lifetimes of the engine's device buffers (copra_amd/csrc/device_mem.hpp: every owned block is a DevBuf / DevBag member or local): the
+paths that allocate late, re-allocate, use a temporary behind a launch, or free -- walked on a batch of 130 instances (two waves and a ragged
+tail), every solve against the CPU oracle at the bars tests/test_gpu_parity.py and tests/test_reference_schedule_gpu.py hold the same
+controllers to: equal statuses, controls and trajectories entry-wise within 1e-6 with the absolute floor 1e-3.  No case makes an allocation
+fail: the failure paths are tests/cpp/test_device_mem.cpp's."""
+import numpy as np
+import pytest
+
+import tracking_cases as tc
+from controller_cases import planar_integrator
+
+pytestmark = pytest.mark.gpu
+
+B = 130
+RTOL = 1e-6
+ABS_FLOOR = 1e-3
+
+
+def _rel(a, b):
+    return float(np.nanmax(np.abs(a - b) / np.maximum(np.abs(b), ABS_FLOOR)))
+
+
+def _against(res, ref, what):
+    """a whole batch against the oracle's (status, control, trajectory)"""
+    assert np.array_equal(res["status"], ref["status"]), what
+    ok = ref["status"] == 0
+    assert ok.sum() >= len(ok) // 2, what
+    eu, ex = _rel(res["control"][ok], ref["control"][ok]), _rel(res["trajectory"][ok], ref["trajectory"][ok])
+    print("%s: %d of %d solved, against the oracle U %.2e X %.2e" % (what, ok.sum(), len(ok), eu, ex))
+    assert eu <= RTOL and ex <= RTOL, what
+
+
+def _one_by_one(oracle, wl, N, costs_of, cstrs_of, x0=None, shared=False):
+    """the oracle instance by instance (it takes controller-wide costs and constraints), stacked like lmpc_solve_batch's result"""
+    x0 = wl["x0"] if x0 is None else x0
+    rows = []
+    for k in range(x0.shape[0]):
+        s = 0 if shared else k
+        rows.append(oracle.lmpc_solve(wl["A"][s], wl["B"][s], wl["d"][s], x0[k], N, costs_of(k), cstrs_of(k)))
+    return {key: np.stack([np.asarray(r[key]) for r in rows]) for key in ("status", "control", "trajectory")}
+
+
+def _headline_with_limits():
+    """the decoupled (6, 3), N = 20 controller with the velocity limit as a TrajectoryConstraint (a bound has no right-hand side to set)"""
+    from copra_amd import workloads
+    wl = workloads.com_preview(B, seed=61, v_max=0.5, u_max=2.5)
+    Ev = np.hstack([np.zeros((3, 3)), np.eye(3)])
+    wl["cstrs"] = [dict(kind="trajectory", E=Ev, f=[0.5] * 3, ineq=True), wl["cstrs"][1]]
+    return wl
+
+
+def test_axis_and_lane_groups_rhs_temporary_and_the_parity_dump(oracle):
+    """cases 1 and 5: the (instance, axis)-per-lane solver's buffer groups come with the first solve; per-instance right-hand sides (a temporary
+    behind the scatter launch) and bounds (allocated on first use); a second solve on the groups that are there; copra_batch_dump_qp (four
+    temporaries behind one launch) on the first and the last instance"""
+    from copra_amd import BatchLMPC
+    wl = _headline_with_limits()
+    N, cstrs = wl["N"], wl["cstrs"]
+    eng = BatchLMPC(6, 3, N, B, wl["costs"], cstrs)
+    eng.set_system(wl["A"], wl["B"], wl["d"], wl["x0"])
+    eng.solve()
+    assert eng.axis_solver_ran()
+    _against(eng.results(), oracle.lmpc_solve_batch(wl["A"], wl["B"], wl["d"], wl["x0"], N, wl["costs"], cstrs, nthreads=8), "first solve")
+    rng = np.random.default_rng(6)
+    vlim, ulim = 0.5 * rng.uniform(0.6, 1.3, B), 2.5 * rng.uniform(0.6, 1.3, B)
+    lo, hi = -np.repeat(ulim[:, None], 3 * N, axis=1), np.repeat(ulim[:, None], 3 * N, axis=1)
+    hi[::43, 3 * 5 + 1] *= 0.5  # (limits that change along the horizon: instances the solver leaves to the tier)
+    for _ in range(2):  # (twice: the second call finds every buffer in place)
+        eng.set_constraint_rhs(0, np.repeat(vlim[:, None], 3, axis=1))
+        eng.set_control_bounds(lo, hi)
+    eng.solve()
+    assert eng.axis_solver_ran()
+    per = lambda k: [dict(cstrs[0], f=[vlim[k]] * 3), dict(kind="control_bound", lower=lo[k], upper=hi[k])]
+    _against(eng.results(), _one_by_one(oracle, wl, N, lambda k: wl["costs"], per), "per-instance limits")
+    for k in (0, B - 1):
+        got = eng.dump_qp(k)  # (its bounds are the controller-wide ones: LMPC::lb / ub)
+        qp = oracle.lmpc_build(wl["A"][k], wl["B"][k], wl["d"][k], wl["x0"][k], N, wl["costs"], [dict(cstrs[0], f=[vlim[k]] * 3), cstrs[1]])
+        assert np.abs(got["Q"] - qp["Q"]).max() <= 1e-12 * np.abs(qp["Q"]).max()
+        assert np.abs(got["c"] - qp["c"]).max() <= 1e-12 * max(1.0, np.abs(qp["c"]).max())
+        assert np.abs(got["Aineq"] - qp["Aineq"]).max() <= 1e-13 and np.abs(got["bineq"] - qp["bineq"]).max() <= 1e-12
+        assert (got["lb"] == qp["lb"]).all() and (got["ub"] == qp["ub"]).all()
+    eng.solve()  # ... and the dump left the controller as it was
+    _against(eng.results(), _one_by_one(oracle, wl, N, lambda k: wl["costs"], per), "after the dump")
+    eng.close()
+
+
+def test_shared_model_grows_and_the_warm_start_comes_and_goes(oracle):
+    """cases 2 and 3: a shared-model controller on the shared-model kernels; per-instance goals give its prepared model more columns (d_model
+    regrows behind the probe launches' temporaries); the warm-start table is allocated, freed and allocated again -- its size follows the
+    batch, so the second controller, of another batch, is the one with another count"""
+    from copra_amd import BatchLMPC
+    N = 8
+    wl = planar_integrator(B, N)
+    costs, cstrs = wl["costs"], wl["cstrs"]
+    eng = BatchLMPC(4, 2, N, B, costs, cstrs, options=dict(no_axis_solver=1))
+    eng.set_shared_system(wl["A"][0], wl["B"][0], wl["d"][0])
+    eng.set_x0(wl["x0"])
+    eng.solve()
+    same = lambda k: costs
+    _against(eng.results(), _one_by_one(oracle, wl, N, same, lambda k: cstrs, shared=True), "shared model")
+    r1, x = eng.results(), wl["x0"]
+    for on in (True, False, True):  # (on: a fresh table of -1; the tick after it starts from the last active sets)
+        eng.set_warm_start(on)
+        for _ in range(2):
+            ok = r1["status"] == 0
+            x = np.where(ok[:, None], r1["trajectory"][:, 4:8], x)  # every solved instance moves to the state it predicted for step 1
+            eng.set_x0(x)
+            eng.solve()
+            r1 = eng.results()
+            _against(r1, _one_by_one(oracle, wl, N, same, lambda k: cstrs, x0=x, shared=True), "tick, warm start %s" % on)
+    eng.set_warm_start(False)
+    goals = costs[0]["p"][None, :] + 0.1 * np.random.default_rng(2).standard_normal((B, 4))
+    own = lambda k: [dict(costs[0], p=goals[k]), costs[1]]
+    for _ in range(2):  # (the second time the model is large enough)
+        eng.set_cost_reference(0, goals)
+        eng.solve()
+        _against(eng.results(), _one_by_one(oracle, wl, N, own, lambda k: cstrs, x0=x, shared=True), "shared model, per-instance goals")
+        goals = goals[::-1].copy()
+    eng.close()
+    small = planar_integrator(37, N, seed=3)
+    e2 = BatchLMPC(4, 2, N, 37, costs, cstrs, options=dict(no_axis_solver=1))
+    e2.set_shared_system(small["A"][0], small["B"][0], small["d"][0])
+    e2.set_x0(small["x0"])
+    for _ in range(2):
+        e2.set_warm_start(True)
+        e2.solve()
+    _against(e2.results(), _one_by_one(oracle, small, N, same, lambda k: cstrs, shared=True), "another batch, warm start")
+    e2.close()
+
+
+def test_host_schedule_regrows(oracle):
+    """case 4: a reference schedule from the host, then a longer one with a signal per instance (the library's copy regrows); one advance
+    after each, every solve against the oracle from the state and with the window the device held at that tick"""
+    from copra_amd import BatchLMPC
+    wl, signals = tc.tracking_workload(batch=B)
+    S = wl["N"] + 1
+    eng = BatchLMPC(6, 3, wl["N"], B, wl["costs"], wl["cstrs"])
+    eng.set_system(wl["A"], wl["B"], wl["d"], wl["x0"])
+    every = tc.group_of(B, True)
+    steps = ((signals[:1, :5], np.zeros(B, dtype=int), signals[0, :5]),  # (steps, r): five blocks, one signal
+             (signals, every, np.ascontiguousarray(signals[every])))  # (batch, steps, r): 29 blocks, four signals in turn
+    tick = 0
+    for sigs, groups, sched in steps:
+        eng.set_reference_schedule(0, sched, tc.NX)
+        assert eng.schedule_tick() == tick
+        for i in range(2):  # at the tick the schedule was set, and behind the advance
+            x = eng.state()
+            eng.solve()
+            ref = tc.oracle_tick(oracle, wl, x, groups, [tc.window(s, tick, S) for s in sigs])
+            _against(eng.results(), ref, "%d-block schedule, tick %d" % (sched.shape[-2], tick))
+            if i == 0:
+                eng.advance()
+                tick += 1
+    assert eng.schedule_tick() == 2
+    eng.close()
+
+
+def test_destroy_then_create_again(oracle):
+    """case 6: controllers of every kind above destroyed with their late buffers in place; one more is created and solves in the same process"""
+    from copra_amd import BatchLMPC
+    head = _headline_with_limits()
+    a = BatchLMPC(6, 3, head["N"], B, head["costs"], head["cstrs"])
+    a.set_system(head["A"], head["B"], head["d"], head["x0"])
+    a.set_constraint_rhs(0, np.full((B, 3), 0.45))
+    a.solve()
+    a.synchronize()
+    a.close()
+    wl = planar_integrator(B, 12)
+    ref = oracle.lmpc_solve_batch(wl["A"], wl["B"], wl["d"], wl["x0"], 12, wl["costs"], wl["cstrs"], nthreads=8)
+    for _ in range(2):
+        eng = BatchLMPC(4, 2, 12, B, wl["costs"], wl["cstrs"])
+        eng.set_system(wl["A"], wl["B"], wl["d"], wl["x0"])
+        eng.solve()
+        _against(eng.results(), ref, "a controller created after the others were destroyed")
+        eng.close()

@@ -114,3 +114,23 @@ def test_every_engine_option_takes_part_in_the_mode_fuzzer():
     covered = set().union(*[set(o) for o in fuzz_modes.OPTION_SETS])
     assert covered == set(_capi.OPTION_NAMES), (covered ^ set(_capi.OPTION_NAMES))
     assert 240 // 8 >= len(fuzz_modes.OPTION_SETS)  # (the GPU suite's slice reaches every set)
+
+
+def test_only_the_two_allocator_policies_allocate_or_free():
+    """Ownership of device and pinned memory is by type (copra_amd/csrc/device_mem.hpp): hipMalloc / hipFree / hipHostMalloc / hipHostFree
+    are called from the two policies in engine.hpp, DeviceMem and PinnedMem, and from nowhere else under copra_amd/csrc."""
+    csrc = os.path.join(ROOT, "copra_amd", "csrc")
+    calls = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\b")
+    found = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp", ".inc", ".h")):
+            continue
+        for no, line in enumerate(open(os.path.join(csrc, f), errors="replace"), 1):
+            found += [(f, no, m.group(1)) for m in calls.finditer(line)]
+    assert sorted(c for _, _, c in found) == ["hipFree", "hipHostFree", "hipHostMalloc", "hipMalloc"], found
+    assert {f for f, _, _ in found} == {"engine.hpp"}
+    text = open(os.path.join(csrc, "engine.hpp")).read()
+    dev = text[text.index("struct DeviceMem {"):text.index("struct PinnedMem {")]
+    pin = text[text.index("struct PinnedMem {"):]
+    pin = pin[:pin.index("};")]
+    assert set(calls.findall(dev)) == {"hipMalloc", "hipFree"} and set(calls.findall(pin)) == {"hipHostMalloc", "hipHostFree"}
