@@ -367,6 +367,10 @@ def lib():
         L.copra_batch_schedule_seek.argtypes = [vp, C.c_longlong]
         L.copra_batch_schedule_tick.restype = C.c_longlong
         L.copra_batch_schedule_tick.argtypes = [vp]
+        L.copra_batch_set_constraint_schedule.restype = C.c_int
+        L.copra_batch_set_constraint_schedule.argtypes = [vp, C.c_int, vp, C.c_longlong] + [C.c_int] * 5
+        L.copra_batch_set_control_bound_schedule.restype = C.c_int
+        L.copra_batch_set_control_bound_schedule.argtypes = [vp, vp, vp, C.c_longlong] + [C.c_int] * 4
         _lib = L
     return _lib
 

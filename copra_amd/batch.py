@@ -42,6 +42,7 @@ class BatchLMPC:
         self._ref_keep = {}  # torch tensors used in place as per-instance cost references, by cost index
         self._w_keep = {}  # ... and as per-instance cost weights
         self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
+        self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
         self._cost_rows = [None if cc[i].kind == _capi.COST_KINDS["dense"] else int(cc[i].rows) for i in range(len(costs))]
@@ -221,8 +222,62 @@ class BatchLMPC:
         if torch_in:
             self._sched_keep[k] = schedule
 
+    def _limit_schedule(self, schedule, r, what):
+        """(pointer, steps, per_instance, on_device, the tensor to keep alive or None) of a limit schedule (steps, r) or (batch, steps, r)"""
+        torch_in = _is_torch(schedule)
+        if torch_in:
+            if not (schedule.is_cuda and schedule.is_contiguous() and str(schedule.dtype) == "torch.float64"):
+                raise ValueError("%s: a contiguous CUDA float64 tensor is needed" % what)
+            sb, ptr = schedule, schedule.data_ptr()
+        else:
+            sb = np.ascontiguousarray(schedule, dtype=np.float64)
+            ptr = sb.ctypes.data
+        shape = tuple(sb.shape)
+        if len(shape) not in (2, 3) or shape[-1] != r or (len(shape) == 3 and shape[0] != self.batch):
+            raise _capi.CopraDomainError("%s: expected (steps, %d) or (%d, steps, %d), got %s" % (what, r, self.batch, r, shape))
+        return ptr, shape[-2], 1 if len(shape) == 3 else 0, 1 if torch_in else 0, sb
+
+    def set_constraint_schedule(self, cstr_index, schedule, rows_per_step, offset=0, preview=True):
+        """The right-hand side f of the Trajectory / Control / Mixed constraint `cstr_index` follows a signal (copra_batch_set_constraint_schedule):
+        schedule of shape (steps, r) -- one for the batch -- or (batch, steps, r) -- one per instance --, r = rows_per_step (the rows of a per-step
+        constraint; a divisor of the rows of a full-size one); numpy: copied; a torch CUDA float64 tensor: used in place and kept alive, never
+        written.  The solve at tick tau reads, for the S steps of the constraint, the blocks min(tau + offset + s, steps - 1) -- preview=True: the
+        horizon sees the future limits -- or block min(tau + offset, steps - 1) at every step (preview=False).  advance() / rollout() move the
+        window by one step per tick, on the device.  None ends the schedule and keeps the last window; set_constraint_rhs on that constraint
+        ends it too."""
+        k, r = int(cstr_index), int(rows_per_step)
+        if schedule is None:
+            _capi.check(self._lib.copra_batch_set_constraint_schedule(self._h, k, None, 0, 0, 0, 0, 0, 0))
+            self._limit_keep.pop(k, None)
+            return
+        ptr, steps, per, dev, sb = self._limit_schedule(schedule, r, "set_constraint_schedule")
+        _capi.check(self._lib.copra_batch_set_constraint_schedule(self._h, k, ptr, steps, r, int(offset), 1 if preview else 0, per, dev))
+        self._limit_keep.pop(k, None)
+        if dev:
+            self._limit_keep[k] = sb
+
+    def set_control_bound_schedule(self, lower, upper, offset=0, preview=True):
+        """The bounds of the controller's ControlBoundConstraint follow two signals (copra_batch_set_control_bound_schedule): lower and upper of
+        shape (steps, nu) or (batch, steps, nu), both numpy (copied) or both torch CUDA float64 tensors (used in place and kept alive); infinite
+        entries are allowed.  Windows and `preview` as in set_constraint_schedule, with the N steps of the horizon.  None, None ends the
+        schedule and keeps the last window; set_control_bounds ends it too."""
+        if lower is None and upper is None:
+            _capi.check(self._lib.copra_batch_set_control_bound_schedule(self._h, None, None, 0, 0, 0, 0, 0))
+            self._limit_keep.pop("bounds", None)
+            return
+        if lower is None or upper is None:
+            raise ValueError("set_control_bound_schedule: both of lower and upper are needed (None, None ends the schedule)")
+        lp, steps, per, dev, lb = self._limit_schedule(lower, self.nu, "set_control_bound_schedule")
+        up, steps_u, per_u, dev_u, ub = self._limit_schedule(upper, self.nu, "set_control_bound_schedule")
+        if (steps, per, dev) != (steps_u, per_u, dev_u):
+            raise _capi.CopraDomainError("set_control_bound_schedule: lower and upper differ in shape or in where they live")
+        _capi.check(self._lib.copra_batch_set_control_bound_schedule(self._h, lp, up, steps, int(offset), 1 if preview else 0, per, dev))
+        self._limit_keep.pop("bounds", None)
+        if dev:
+            self._limit_keep["bounds"] = (lb, ub)
+
     def schedule_seek(self, tick):
-        """the controller's tick counter <- tick, the windows of all scheduled costs rewritten (copra_batch_schedule_seek; asynchronous)"""
+        """the controller's tick counter <- tick, the windows of all scheduled costs and limits rewritten (copra_batch_schedule_seek; asynchronous)"""
         _capi.check(self._lib.copra_batch_schedule_seek(self._h, int(tick)))
 
     def schedule_tick(self):
@@ -261,12 +316,14 @@ class BatchLMPC:
         fb = np.ascontiguousarray(f, dtype=np.float64)
         assert fb.shape[0] == self.batch
         _capi.check(self._lib.copra_batch_set_constraint_rhs(self._h, int(cstr_index), fb.ctypes.data, 0))
+        self._limit_keep.pop(int(cstr_index), None)  # (the library ends the constraint's schedule)
 
     def set_control_bounds(self, lower, upper):
         """per-instance ControlBoundConstraint: lower / upper broadcastable to (batch, nu * N)"""
         lo = np.ascontiguousarray(np.broadcast_to(lower, (self.batch, self.n)), dtype=np.float64)
         up = np.ascontiguousarray(np.broadcast_to(upper, (self.batch, self.n)), dtype=np.float64)
         _capi.check(self._lib.copra_batch_set_control_bounds(self._h, lo.ctypes.data, up.ctypes.data, 0))
+        self._limit_keep.pop("bounds", None)  # (the library ends the bound schedule)
 
     def set_x0(self, x0):
         if _is_torch(x0):

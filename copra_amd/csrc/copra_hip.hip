@@ -400,6 +400,13 @@ static bool axis_solver_wanted(const copra_batch* h, const FusedPlan& P)
     const copra_options_t& opt = h->hp.opt;
     if (h->ad.axis_off || P.prof_fine || h->packed || h->shared) return false;
     if (opt.lane_min_batch > 0 && P.batch < opt.lane_min_batch) return false;
+    if (h->limit_sched_seen) { // limits written by a schedule (live, or ended with its last window kept): only the builds that read an instance's own
+        // limits (CT: lmpc_axis.hpp) -- the others read the controller's
+        const bool weights = plan_has_weights(P);
+        const AxisBuild* const first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, false);
+        const AxisBuild* const list = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, true);
+        if (!first || !first->ct || !list || !list->ct) return false;
+    }
     return axis_solver_covers(h->hp, P);
 }
 static size_t lane_lds_bytes(const FusedPlan& P)
@@ -909,7 +916,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 8; } // 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 9; } // 9: + copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 const char* copra_last_error(void) { return g_copra_err.c_str(); }
 

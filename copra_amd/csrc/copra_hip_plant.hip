@@ -1,8 +1,10 @@
 // copra_hip_plant.hip -- the receding-horizon tick of the C ABI (include/copra_hip.h): copra_batch_advance applies the first control of the
 // last solve to a plant and makes the result the controller's next initial state (kernel: plant_step.hpp), copra_batch_rollout enqueues
 // `ticks` x (solve, advance) on one stream, copra_batch_x0_device / copra_batch_get_x0 hand the current state out.  A cost whose reference
-// follows a schedule (copra_batch_set_reference_schedule) gets the window of the new tick behind every plant step (kernel: ref_window.hpp).
+// follows a schedule (copra_batch_set_reference_schedule) gets the window of the new tick behind every plant step (kernel: ref_window.hpp),
+// and so does a limit that follows one (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; kernel: limit_window.hpp).
 #include "engine.hpp"
+#include "limit_window.hpp"
 #include "plant_step.hpp"
 #include "ref_window.hpp"
 
@@ -56,7 +58,7 @@ copra_status_t shared_model_on_device(copra_batch* h)
 }
 
 // the windows of every scheduled cost at the controller's tick counter, one launch on `s`: no synchronisation, no allocation
-copra_status_t write_windows(copra_batch* h, hipStream_t s, const char* who)
+copra_status_t write_ref_windows(copra_batch* h, hipStream_t s, const char* who)
 {
     RefWindowArgs W {};
     W.batch = h->hp.plan.batch;
@@ -78,6 +80,54 @@ copra_status_t write_windows(copra_batch* h, hipStream_t s, const char* who)
     const unsigned grid = (unsigned)((W.batch + W.group - 1) / W.group);
     hipLaunchKernelGGL(copra_ref_window_kernel, dim3(grid), dim3(kRefWindowThreads), 0, s, W);
     HIP_TRY(hipGetLastError());
+    return COPRA_OK;
+}
+
+// ... and the windows of every live limit schedule, one launch of its own on `s` -- made only where a limit schedule is live
+copra_status_t write_limit_windows(copra_batch* h, hipStream_t s, const char* who)
+{
+    const FusedPlan& HP = h->hp.plan;
+    if (live_limit_windows(h) == 0 || HP.batch <= 0) return COPRA_OK;
+    LimitWindowArgs W {};
+    W.batch = HP.batch;
+    W.group = kLimitWindowGroup;
+    auto add = [&](const LimitSchedule& ls, double* out, int stride) {
+        if (!ls.sched) return true;
+        if (W.nwin == kLimitWindowMax || !out) return false;
+        LimitWindow& c = W.w[W.nwin++];
+        c.sched = ls.sched;
+        c.out = out;
+        c.steps = ls.steps;
+        c.first = h->sched_tick + ls.offset;
+        c.stride = stride, c.row0 = ls.row0;
+        c.r = ls.r, c.S = ls.S;
+        c.per_instance = ls.per_instance, c.preview = ls.preview;
+        return true;
+    };
+    bool ok = add(h->lb_sched, h->d_lb_inst, HP.n) && add(h->ub_sched, h->d_ub_inst, HP.n);
+    for (const auto& kv : h->cstr_sched) ok = ok && add(kv.second, h->d_row_f_inst, HP.mgen);
+    if (!ok) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": more live limit windows than one launch serves");
+    limit_window_prepare(W, kLimitWindowThreads);
+    const unsigned grid = (unsigned)((W.batch + W.group - 1) / W.group);
+    hipLaunchKernelGGL(copra_limit_window_kernel, dim3(grid), dim3(kLimitWindowThreads), 0, s, W);
+    HIP_TRY(hipGetLastError());
+    return COPRA_OK;
+}
+
+copra_status_t write_windows(copra_batch* h, hipStream_t s, const char* who)
+{
+    const copra_status_t rc = write_ref_windows(h, s, who);
+    return rc != COPRA_OK ? rc : write_limit_windows(h, s, who);
+}
+
+// the library's copy of a host schedule (the caller has waited for the window launch that may still read the old one)
+copra_status_t own_schedule(LimitSchedule& ls, const double* sched, size_t count)
+{
+    if (ls.own.count() < count) {
+        ls.sched = nullptr; // (it may be the copy that goes)
+        OWN_TRY(ls.own.alloc(count));
+    }
+    HIP_TRY(hipMemcpy(ls.own, sched, count * sizeof(double), hipMemcpyHostToDevice));
     return COPRA_OK;
 }
 
@@ -235,6 +285,106 @@ copra_status_t copra_batch_schedule_seek(copra_batch_t* h, long long tick)
     if (tick < 0) return fail(COPRA_ERR_ARG, "copra_batch_schedule_seek: negative tick");
     h->sched_tick = tick;
     return write_windows(h, h->last_stream, "copra_batch_schedule_seek");
+}
+
+copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_index, const double* sched, long long steps, int r, int offset, int preview,
+    int per_instance, int on_device)
+{
+    const char* const who = "copra_batch_set_constraint_schedule";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const FusedPlan& P = h->hp.plan;
+    if (cstr_index < 0 || cstr_index >= (int)h->hp.cstr_kind.size() || h->hp.cstr_kind[(size_t)cstr_index] < 0)
+        return fail(COPRA_ERR_ARG, std::string(who) + ": no such constraint");
+    const int kind = h->hp.cstr_kind[(size_t)cstr_index], row0 = h->hp.cstr_row0[(size_t)cstr_index];
+    if (kind == COPRA_CSTR_TRAJECTORY_BOUND || kind == COPRA_CSTR_CONTROL_BOUND || kind == COPRA_CSTR_DENSE || row0 < 0)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": not a Trajectory / Control / Mixed constraint of this controller "
+                                                                "(control bounds: copra_batch_set_control_bound_schedule)");
+    if (!sched) { // the schedule ends, the window stays in the per-instance right-hand sides
+        auto it = h->cstr_sched.find(cstr_index);
+        if (it != h->cstr_sched.end() && it->second.sched) {
+            // (its last window launch may be in flight: it reads the schedule, which the caller may free now, and a right-hand side set by
+            //  hand next must not be overtaken by it)
+            HIP_TRY(hipStreamSynchronize(h->last_stream));
+            it->second.sched = nullptr;
+        }
+        return COPRA_OK;
+    }
+    if (steps < 1 || offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
+    const int per_step = h->hp.cstr_per_step[(size_t)cstr_index], csteps = h->hp.cstr_steps[(size_t)cstr_index];
+    int S = 0;
+    if (csteps == 1) { // a full-size entry: any block size that divides its rows
+        if (r < 1 || per_step % r != 0) return fail(COPRA_ERR_DOMAIN, std::string(who) + ": r does not divide the rows of this full-size constraint");
+        S = per_step / r;
+    } else {
+        if (r != per_step) return fail(COPRA_ERR_DOMAIN, std::string(who) + ": r must be the rows of one step of this per-step constraint");
+        S = csteps;
+    }
+    if (row0 + S * r > P.mgen) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the constraint's rows do not fit the plan");
+    const bool was_live = h->cstr_sched.count(cstr_index) && h->cstr_sched[cstr_index].sched;
+    if (!was_live && live_limit_windows(h) + 1 > kLimitWindowMax)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": more live limit windows than one launch serves (8; lower and upper bounds count as one each)");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    if (!h->d_row_f_inst) { // first use: every instance starts from the controller-wide right-hand sides
+        OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
+        std::vector<double> rep(b * (size_t)P.mgen);
+        for (size_t i = 0; i < b; ++i) std::copy(h->hp.row_f.begin(), h->hp.row_f.begin() + P.mgen, rep.begin() + i * P.mgen);
+        HIP_TRY(hipMemcpy(h->d_row_f_inst, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    LimitSchedule& ls = h->cstr_sched[cstr_index];
+    if (!on_device) { // the library's copy: a window launch that still reads the old one first
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        const copra_status_t rc = own_schedule(ls, sched, (per_instance ? b : 1) * (size_t)steps * r);
+        if (rc != COPRA_OK) return rc;
+        sched = ls.own;
+    }
+    ls.sched = sched;
+    ls.steps = steps;
+    ls.r = r, ls.S = S, ls.row0 = row0, ls.offset = offset, ls.per_instance = per_instance != 0, ls.preview = preview != 0;
+    h->limit_sched_seen = true;
+    return write_limit_windows(h, h->last_stream, who);
+}
+
+copra_status_t copra_batch_set_control_bound_schedule(copra_batch_t* h, const double* lower, const double* upper, long long steps, int offset, int preview,
+    int per_instance, int on_device)
+{
+    const char* const who = "copra_batch_set_control_bound_schedule";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const FusedPlan& P = h->hp.plan;
+    if ((lower == nullptr) != (upper == nullptr)) return fail(COPRA_ERR_ARG, std::string(who) + ": both of lower and upper are needed (or neither: the schedule ends)");
+    if (!h->hp.has_control_bound || P.initial_state)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": the controller has no ControlBoundConstraint (or is an InitialStateLMPC controller)");
+    if (!lower) { // the schedule ends, the window stays in the per-instance bounds
+        if (h->lb_sched.sched || h->ub_sched.sched) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (as for a constraint's schedule)
+        h->lb_sched.sched = h->ub_sched.sched = nullptr;
+        return COPRA_OK;
+    }
+    if (steps < 1 || offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
+    if (P.n != P.nu * P.N) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the plan's variables are not the controls of the horizon");
+    const bool was_live = h->lb_sched.sched != nullptr;
+    if (!was_live && live_limit_windows(h) + 2 > kLimitWindowMax)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": more live limit windows than one launch serves (8; lower and upper bounds count as one each)");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    // (first use: the window covers all nu N bounds of every instance -- nothing to start from)
+    if (!h->d_lb_inst) OWN_TRY(h->d_lb_inst.alloc(b * (size_t)P.n));
+    if (!h->d_ub_inst) OWN_TRY(h->d_ub_inst.alloc(b * (size_t)P.n));
+    if (!on_device) {
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        const size_t count = (per_instance ? b : 1) * (size_t)steps * P.nu;
+        copra_status_t rc = own_schedule(h->lb_sched, lower, count);
+        if (rc == COPRA_OK) rc = own_schedule(h->ub_sched, upper, count);
+        if (rc != COPRA_OK) {
+            h->lb_sched.sched = h->ub_sched.sched = nullptr;
+            return rc;
+        }
+        lower = h->lb_sched.own, upper = h->ub_sched.own;
+    }
+    for (LimitSchedule* ls : { &h->lb_sched, &h->ub_sched }) {
+        ls->sched = ls == &h->lb_sched ? lower : upper;
+        ls->steps = steps;
+        ls->r = P.nu, ls->S = P.N, ls->row0 = 0, ls->offset = offset, ls->per_instance = per_instance != 0, ls->preview = preview != 0;
+    }
+    h->limit_sched_seen = true;
+    return write_limit_windows(h, h->last_stream, who);
 }
 
 long long copra_batch_schedule_tick(const copra_batch_t* h)

@@ -364,6 +364,13 @@ copra_status_t copra_batch_set_constraint_rhs(copra_batch_t* h, int cstr_index, 
     const int r = h->hp.cstr_per_step[(size_t)cstr_index], steps = h->hp.cstr_steps[(size_t)cstr_index];
     const int row0 = h->hp.cstr_row0[(size_t)cstr_index];
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    { // right-hand sides given by hand end the constraint's limit schedule: a window launch in flight must not land after this copy
+        auto it = h->cstr_sched.find(cstr_index);
+        if (it != h->cstr_sched.end() && it->second.sched) {
+            HIP_TRY(hipStreamSynchronize(h->last_stream));
+            it->second.sched = nullptr;
+        }
+    }
     if (!h->d_row_f_inst) { // first use: every instance starts from the controller-wide right-hand sides
         OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
         std::vector<double> rep(b * (size_t)P.mgen);
@@ -395,6 +402,10 @@ copra_status_t copra_batch_set_control_bounds(copra_batch_t* h, const double* lo
     const FusedPlan& P = h->hp.plan;
     const size_t count = (size_t)(P.batch > 0 ? P.batch : 1) * P.n;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (h->lb_sched.sched || h->ub_sched.sched) { // bounds given by hand end the bound schedule: a window launch in flight must not land after these copies
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        h->lb_sched.sched = h->ub_sched.sched = nullptr;
+    }
     if (!h->d_lb_inst) OWN_TRY(h->d_lb_inst.alloc(count));
     if (!h->d_ub_inst) OWN_TRY(h->d_ub_inst.alloc(count));
     HIP_TRY(hipMemcpy(h->d_lb_inst, lower, count * sizeof(double), kind));

@@ -8,7 +8,8 @@
 //   copra_hip_qp.hip       plug-in point 1: copra_qp_solve_dense_batch and its kernels
 //   copra_hip_packed16/32.hip  the one-wave bodies with 16 / 32 lanes per instance
 //   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp); reference
-//                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp)
+//                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp); limit schedules
+//                          (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule, limit_window.hpp)
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -132,6 +133,16 @@ struct RefSchedule {
     int r = 0, S = 0, offset = 0, per_instance = 0;
 };
 
+// A limit that follows a schedule (copra_batch_set_constraint_schedule: the right-hand sides of one constraint, written into d_row_f_inst at its
+// stacked rows; copra_batch_set_control_bound_schedule: the lower / upper control bounds, into d_lb_inst / d_ub_inst): the tick writes its window
+// behind the reference windows (copra_hip_plant.hip, limit_window.hpp)
+struct LimitSchedule {
+    const double* sched = nullptr; // device: the caller's, or `own`; null: no schedule
+    Dev<double> own; // the library's copy of a host schedule
+    long long steps = 0;
+    int r = 0, S = 0, row0 = 0, offset = 0, per_instance = 0, preview = 0;
+};
+
 // Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
 // from the caller or a view into an owned block.  Nothing owned refers to anything else owned, so the order of destruction is free.
 struct copra_batch {
@@ -177,6 +188,9 @@ struct copra_batch {
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
     RefSchedule ref_sched[kMaxCosts]; // ... which the tick rewrites for the costs that follow a schedule,
     long long sched_tick = 0; // at the controller's tick counter tau: the advances so far, or what copra_batch_schedule_seek set
+    std::map<int, LimitSchedule> cstr_sched; // limit schedules by constraint (position in the user's array) ...
+    LimitSchedule lb_sched, ub_sched; // ... and of the control bounds (both live or neither)
+    bool limit_sched_seen = false; // a limit schedule has written per-instance limits of this controller: its last window stays in force when it ends
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -247,6 +261,14 @@ inline bool own_references(const copra_batch* h)
     for (int t = 0; t < kMaxCosts; ++t)
         if (h->cost_p[t]) return true;
     return false;
+}
+
+// Limit schedules that the tick still moves: how many windows one launch has to write
+inline int live_limit_windows(const copra_batch* h)
+{
+    int n = (h->lb_sched.sched != nullptr) + (h->ub_sched.sched != nullptr);
+    for (const auto& kv : h->cstr_sched) n += kv.second.sched != nullptr;
+    return n;
 }
 
 // ---- copra_hip.hip ----

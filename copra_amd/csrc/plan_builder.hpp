@@ -68,6 +68,8 @@ struct HostPlan {
     // where the rows of constraint k (position in the user's array) sit in the stacked order: row = row0 + s * per_step
     // + i for its steps s and lines i (steps == 1 for a full-size entry); row0 < 0: bound constraint, no rows
     std::vector<int> cstr_row0, cstr_per_step, cstr_steps;
+    std::vector<int> cstr_kind; // ... and its kind (copra_cstr_kind_t), as created
+    bool has_control_bound = false; // a ControlBoundConstraint is among them: lb / ub hold its bounds
     std::vector<int> cost_slot; // position of the user's cost k among the kernel-evaluated cost terms, -1: a dense cost
     // the (instance, axis)-per-lane solver's tables for AXIS-MAJOR state order (state i on axis i / nxa: x = (p_x, v_x, p_y, v_y, ..)); the plan's
     // own fields hold the set for component-major order (state i on axis i % nu: x = (p, v)), what FusedPlan::axis_order = 0 means
@@ -1060,6 +1062,7 @@ inline copra_status_t build_plan(HostPlan& hp, const copra_dims_t& dims, int n_c
                 hp.ub[bound_line + i] = c.upper[src];
             }
             bound_line += U;
+            hp.has_control_bound = true;
             break;
         }
         default:
@@ -1122,6 +1125,8 @@ inline copra_status_t build_plan(HostPlan& hp, const copra_dims_t& dims, int n_c
     hp.cstr_row0.assign((size_t)(n_cstrs > 0 ? n_cstrs : 1), -1);
     hp.cstr_per_step.assign((size_t)(n_cstrs > 0 ? n_cstrs : 1), 0);
     hp.cstr_steps.assign((size_t)(n_cstrs > 0 ? n_cstrs : 1), 0);
+    hp.cstr_kind.assign((size_t)(n_cstrs > 0 ? n_cstrs : 1), -1);
+    for (int k = 0; k < n_cstrs; ++k) hp.cstr_kind[(size_t)k] = (int)cstrs[k].kind;
     for (int pass = 0; pass < 2; ++pass) { // pass 0: equalities, pass 1: inequalities (LMPC.cpp:257-271)
         for (int k = 0; k < n_cstrs; ++k) {
             const copra_cstr_desc_t& c = cstrs[k];

@@ -410,6 +410,42 @@ copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_ind
 copra_status_t copra_batch_schedule_seek(copra_batch_t* h, long long tick);
 long long copra_batch_schedule_tick(const copra_batch_t* h);
 
+/* ---- limit schedules: moving limits inside the tick (ABI 9).  The reference has no setter for a constraint's limits either
+ *      (include/constraints.h:114-308: constructor arguments; ControlBoundConstraint: :272-308): a loop whose actuator derates, whose speed
+ *      limit tightens or whose corridor moves replaces the constraint object between solves, and the next solve evaluates the new one
+ *      (src/LMPC.cpp:233-247).  Here the caller hands the limit SIGNAL over once and the library moves the window the horizon sees by one
+ *      step per tick, on the device, in stream order, with the tick counter tau of the reference schedules (copra_batch_advance: tau += 1;
+ *      copra_batch_schedule_seek: tau <- tick, reference AND limit windows rewritten; copra_batch_schedule_tick unchanged).
+ *      copra_batch_set_constraint_schedule: sched [per_instance ? batch : 1][steps][r] are the right-hand sides f of the Trajectory / Control /
+ *      Mixed constraint `cstr_index` (position in the array given at creation).  A per-step entry (E with xDim / G with uDim columns) has
+ *      r = its rows and S = its steps (N + 1 with a state part, else N); a full-size entry any r that divides its rows, S = rows / r.  With
+ *      first = min(tau + offset, steps - 1) the next solve reads for instance b, for s = 0 .. S-1,
+ *        f[b][s r + i] = sched[b or 0][preview ? min(tau + offset + s, steps - 1) : first][i]
+ *      preview != 0: the horizon sees the future limits (the last block is held beyond the end of the schedule); preview == 0: the limit of
+ *      the present tick at every step -- the case the (instance, axis)-per-lane solver keeps in registers; with preview an instance whose
+ *      window varies along the horizon is solved by the tier behind it.
+ *      copra_batch_set_control_bound_schedule: lower and upper, each [per_instance ? batch : 1][steps][uDim], become the bounds of the
+ *      controller's ControlBoundConstraint by the same formula with r = uDim, S = N; both are needed; infinite entries are allowed as in
+ *      copra_batch_set_control_bounds.
+ *      The windows are written into the per-instance limits copra_batch_set_constraint_rhs / copra_batch_set_control_bounds write (on first
+ *      use every instance starts from the controller-wide right-hand sides; rows of other constraints are never touched) -- every kernel
+ *      reads them unchanged.  Both setters write the window of the current tau at once, on the stream of the last solve / tick; they
+ *      synchronise that stream once when they copy a host schedule, never with on_device != 0 (the schedule is then used in place and must
+ *      stay valid).  sched == NULL (lower == NULL and upper == NULL) ends the schedule and keeps the last window (where one was live it waits
+ *      for that stream first: the schedule may be freed on return);
+ *      copra_batch_set_constraint_rhs on that constraint and copra_batch_set_control_bounds end it too (they wait for the stream first where
+ *      a schedule was live).  The tick writes all live limit windows with ONE launch behind the reference windows: no host synchronisation,
+ *      no allocation.  Reference schedules and limit schedules coexist.
+ *      Once a limit schedule has been set (live, or ended with its last window kept) the (instance, axis)-per-lane solver runs only where
+ *      both of its builds read per-instance limits.
+ *      COPRA_ERR_DOMAIN: r does not fit as above; COPRA_ERR_ARG: steps < 1, offset < 0, no such constraint, a NULL handle, exactly one of
+ *      lower / upper; COPRA_ERR_UNSUPPORTED: a bound constraint or a dense constraint as `cstr_index`, a controller without a
+ *      ControlBoundConstraint, more than 8 live limit windows (lower and upper count as one each). ---- */
+copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_index, const double* sched, long long steps, int r, int offset,
+    int preview, int per_instance, int on_device);
+copra_status_t copra_batch_set_control_bound_schedule(copra_batch_t* h, const double* lower, const double* upper, long long steps, int offset,
+    int preview, int per_instance, int on_device);
+
 /* ---- parity hooks: the dense QP of one instance as LMPC exposes it (include/LMPC.h:112-127: Q c Aineq bineq Aeq
  *      beq lb ub), rebuilt ON THE DEVICE by the same condense code the solver runs.  Any pointer may be NULL.
  *      Q [n x n], c [n], Aeq [neq x n], beq [neq], Aineq [nineq x n], bineq [nineq], lb [n], ub [n]. ---- */
