@@ -59,7 +59,11 @@ class Options(C.Structure):
 class PlantStep(C.Structure):
     """copra_plant_step_t (include/copra_hip.h): what copra_batch_advance / copra_batch_rollout apply the first control to; device pointers"""
     _fields_ = [("struct_size", C.c_int), ("A", C.c_void_p), ("B", C.c_void_p), ("d", C.c_void_p), ("shared", C.c_int),
-                ("w", C.c_void_p), ("fallback_u", C.c_void_p), ("x_out", C.c_void_p), ("u_out", C.c_void_p), ("status_out", C.c_void_p)]
+                ("w", C.c_void_p), ("fallback_u", C.c_void_p), ("x_out", C.c_void_p), ("u_out", C.c_void_p), ("status_out", C.c_void_p),
+                ("age_out", C.c_void_p), ("age_hist", C.c_void_p), ("solve_every", C.c_int)]
+
+
+PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
 OPTION_NAMES = tuple(n for n, _ in Options._fields_ if n != "struct_size")
@@ -357,6 +361,8 @@ def lib():
         L.copra_batch_advance.argtypes = [vp, C.POINTER(PlantStep), vp]
         L.copra_batch_rollout.restype = C.c_int
         L.copra_batch_rollout.argtypes = [vp, C.POINTER(PlantStep), C.c_int, vp, vp, vp, vp, vp]
+        L.copra_batch_set_backup_steps.restype = C.c_int
+        L.copra_batch_set_backup_steps.argtypes = [vp, C.c_int]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -401,7 +401,14 @@ class BatchLMPC:
             raise ValueError("%s: outputs stay on the device -- a torch CUDA tensor (or True: allocated for you)" % what)
         return self._device(a, shape, what, dtype)
 
-    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep):
+    def set_backup_steps(self, steps):
+        """backup plans of the tick (copra_batch_set_backup_steps): with steps = K in 1 .. N - 1 the library keeps the controls of horizon steps
+        1 .. K of every instance's last successful solve, and a tick without a fresh solution for an instance -- its solve failed, or no solve
+        was launched since the last advance() -- applies the next of them before it falls back (fallback_control) or holds the state.
+        0: off.  Every call forgets all plans, also with the K in force; set_x0 / set_system do not: call this again for a new episode."""
+        _capi.check(self._lib.copra_batch_set_backup_steps(self._h, int(steps)))
+
+    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None):
         st = _capi.PlantStep()
         self._lib.copra_plant_step_init(C.byref(st))
         b, nx, nu = self.batch, self.nx, self.nu
@@ -420,44 +427,53 @@ class BatchLMPC:
         st.x_out, xo = self._output(x_out, (b, nx), "x_out")
         st.u_out, uo = self._output(u_out, (b, nu), "u_out")
         st.status_out, so = self._output(status_out, (b,), "status_out", "int32")
-        keep.extend([t1, t2, xo, uo, so])
-        return st, dict(x_out=xo, u_out=uo, status_out=so)
+        st.age_out, ao = self._output(age_out, (b,), "age_out", "int32")
+        keep.extend([t1, t2, xo, uo, so, ao])
+        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao)
 
-    def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None):
+    def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None,
+                age_out=None):
         """The second half of a tick (copra_batch_advance): apply the first control of the last solve to the plant and make the result the next
         initial state -- x+ = A x0 + B u + d (+ disturbance) where the solve succeeded (or fallback_control (batch, nu) is given); an instance
         whose solve failed keeps its state otherwise.  Asynchronous on `stream`, behind the solve.
         plant: (A, B, d) -- numpy in natural indexing ((batch, nx, nx), (batch, nx, nu), (batch, nx); with shared=True ONE system (nx, nx),
         (nx, nu), (nx,)): copied to the device; torch CUDA tensors in ABI layout (as set_system): used in place; None: the controller's model.
         x_out / u_out / status_out: torch CUDA tensors (batch, nx) / (batch, nu) / int32 (batch,) that receive copies, or True (allocated
-        here).  Returns dict(x_out, u_out, status_out) of those tensors (None where not asked for).  The state lives in a buffer of the
-        library afterwards (state(), state_ptr()): a tensor given to set_x0 is not written."""
+        here).  age_out: int32 (batch,), the same way: where each instance's control came from -- 0 this tick's solve, j >= 1 step j of its
+        backup plan (set_backup_steps), _capi.PLAN_FALLBACK (-1) fallback_control, _capi.PLAN_HELD (-2) the state was kept; on a tick without
+        a solve status_out is the last solve's and only age_out tells.  Returns dict(x_out, u_out, status_out, age_out) of those tensors
+        (None where not asked for).  The state lives in a buffer of the library afterwards (state(), state_ptr()): a tensor given to set_x0
+        is not written."""
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep)
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out)
         _capi.check(self._lib.copra_batch_advance(self._h, C.byref(st), C.c_void_p(stream or 0)))
         self._tick_keep = keep
         return outs
 
     def rollout(self, ticks, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None,
-                disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None):
+                disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None, age_out=None, age_hist=None, solve_every=1):
         """`ticks` x (solve(), advance(...)) enqueued on `stream` by ONE call (copra_batch_rollout): the closed loop never returns to the host.
         disturbances: (ticks, batch, nx), tick t's replaces `disturbance`; x_hist (ticks + 1, batch, nx) -- [0] is the state the first solve
         read --, u_hist (ticks, batch, nu), status_hist int32 (ticks, batch): torch CUDA tensors written in place, or True (allocated here).
-        Returns dict(x_hist, u_hist, status_hist, x_out, u_out, status_out)."""
+        age_hist int32 (ticks, batch): tick t's age_out (see advance).  solve_every = k > 1: a solve at the ticks t with t % k == 0 only, the
+        ticks in between play the backup plan -- needs set_backup_steps(K) with K >= k - 1.
+        Returns dict(x_hist, u_hist, status_hist, age_hist, x_out, u_out, status_out, age_out)."""
         ticks = int(ticks)
         if ticks < 0:
             raise ValueError("rollout: ticks < 0")
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep)
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out)
         b, nx, nu = self.batch, self.nx, self.nu
         wp, wt = self._device(disturbances, (ticks, b, nx), "disturbances")
         xp, xt = self._output(x_hist, (ticks + 1, b, nx), "x_hist")
         up, ut = self._output(u_hist, (ticks, b, nu), "u_hist")
         sp, stt = self._output(status_hist, (ticks, b), "status_hist", "int32")
-        keep.extend([wt, xt, ut, stt])
+        st.age_hist, at = self._output(age_hist, (ticks, b), "age_hist", "int32")
+        st.solve_every = int(solve_every)
+        keep.extend([wt, xt, ut, stt, at])
         _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, wp, xp, up, sp, C.c_void_p(stream or 0)))
         self._tick_keep = keep
-        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt)
+        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at)
 
     def state(self):
         """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""

@@ -916,7 +916,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 9; } // 9: + copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 10; } // 10: + copra_batch_set_backup_steps, copra_plant_step_t::age_out / age_hist / solve_every; 9: + copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 const char* copra_last_error(void) { return g_copra_err.c_str(); }
 
@@ -1347,6 +1347,7 @@ static void remember_outputs(copra_batch* h, const FusedPlan& P)
     h->ad.last_iter = P.iter;
     h->ad.last_status = P.status;
     h->ad.last_control = P.control;
+    h->plan_fresh = true; // (backup plans: the next plant step belongs to THIS solve)
 }
 
 // Shared-model tick: WHICH first tier -- the Riccati-factor tier in shared-model mode, or lmpc_shared.hpp.  May move the plan's layout.

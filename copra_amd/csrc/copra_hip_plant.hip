@@ -3,6 +3,7 @@
 // `ticks` x (solve, advance) on one stream, copra_batch_x0_device / copra_batch_get_x0 hand the current state out.  A cost whose reference
 // follows a schedule (copra_batch_set_reference_schedule) gets the window of the new tick behind every plant step (kernel: ref_window.hpp),
 // and so does a limit that follows one (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; kernel: limit_window.hpp).
+// copra_batch_set_backup_steps: an instance without a fresh solution plays the tail of its last plan (the store: d_plan, d_plan_next).
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
@@ -132,8 +133,8 @@ copra_status_t own_schedule(LimitSchedule& ls, const double* sched, size_t count
 }
 
 // one plant step behind the last launched solve; `st` has been through read_step
-copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const double* w, double* x_out, double* u_out, int* status_out, hipStream_t s,
-    const char* who)
+copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const double* w, double* x_out, double* u_out, int* status_out, int* age_out,
+    hipStream_t s, const char* who)
 {
     const FusedPlan& HP = h->hp.plan;
     if (!h->ad.solved_once) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no solve has been launched (copra_batch_solve)");
@@ -169,6 +170,13 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
     P.x_out = x_out;
     P.u_out = u_out;
     P.status_out = status_out;
+    P.age_out = age_out;
+    if (h->backup_steps > 0) {
+        P.backup_steps = h->backup_steps;
+        P.fresh = h->plan_fresh;
+        P.plan = h->d_plan;
+        P.next = h->d_plan_next;
+    }
     // instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes
     const size_t one = (size_t)plant_lds(P.nx, P.nu, 1, 0, 1).total * sizeof(double);
     if (one > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's plant does not fit the LDS (xDim beyond about 130)");
@@ -177,7 +185,7 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
     if (group > 1) group &= ~1;
     P.group = group;
     P.vec2 = plant_vec2_ok(P);
-    const size_t lds_bytes = (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr).total * sizeof(double);
+    const size_t lds_bytes = (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0).total * sizeof(double);
     if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_plant_step_kernel, lds_bytes);
     if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
         if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
@@ -188,6 +196,7 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
     hipLaunchKernelGGL(copra_plant_step_kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
     HIP_TRY(hipGetLastError());
     h->x0 = h->own_x0;
+    h->plan_fresh = false;
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
     h->sched_tick += 1; // time moves on for every instance, a failed one included: the next solve reads the next window
     return write_windows(h, s, who);
@@ -211,7 +220,7 @@ copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* s
     copra_status_t rc = read_step(step, st, "copra_batch_advance");
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_advance");
     if (rc != COPRA_OK) return rc;
-    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, (hipStream_t)hip_stream, "copra_batch_advance");
+    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, st.age_out, (hipStream_t)hip_stream, "copra_batch_advance");
 }
 
 copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* step, int ticks, const double* w_seq, double* x_hist, double* u_hist,
@@ -223,6 +232,10 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
     copra_status_t rc = read_step(step, st, "copra_batch_rollout");
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_rollout");
     if (rc != COPRA_OK) return rc;
+    const int every = st.solve_every;
+    if (every < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative solve_every");
+    if (every > 1 && h->backup_steps < every - 1)
+        return fail(COPRA_ERR_ARG, "copra_batch_rollout: solve_every = k needs backup plans of at least k - 1 steps (copra_batch_set_backup_steps)");
     hipStream_t s = (hipStream_t)hip_stream;
     const FusedPlan& HP = h->hp.plan;
     const size_t nd = (size_t)HP.batch * HP.nx, nc = (size_t)HP.batch * HP.nu, nb = (size_t)HP.batch;
@@ -231,12 +244,39 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
         HIP_TRY(hipMemcpyAsync(x_hist, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     for (int t = 0; t < ticks; ++t) {
-        rc = copra_batch_solve(h, hip_stream);
-        if (rc != COPRA_OK) return rc;
+        if (every <= 1 || t % every == 0) { // (the ticks in between play the plan)
+            rc = copra_batch_solve(h, hip_stream);
+            if (rc != COPRA_OK) return rc;
+        }
         rc = advance(h, st, w_seq ? w_seq + (size_t)t * nd : st.w, x_hist ? x_hist + (size_t)(t + 1) * nd : st.x_out, u_hist ? u_hist + (size_t)t * nc : st.u_out,
-            status_hist ? status_hist + (size_t)t * nb : st.status_out, s, "copra_batch_rollout");
+            status_hist ? status_hist + (size_t)t * nb : st.status_out, st.age_hist ? st.age_hist + (size_t)t * nb : st.age_out, s, "copra_batch_rollout");
         if (rc != COPRA_OK) return rc;
     }
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_backup_steps(copra_batch_t* h, int steps)
+{
+    const char* const who = "copra_batch_set_backup_steps";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    const FusedPlan& P = h->hp.plan;
+    if (steps < 0 || steps > P.N - 1) return fail(COPRA_ERR_ARG, std::string(who) + ": steps outside 0 .. N - 1");
+    if (steps == 0) { // off: the store goes (the release waits for a tick that still uses it)
+        h->backup_steps = 0;
+        h->d_plan.reset();
+        h->d_plan_next.reset();
+        return COPRA_OK;
+    }
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    if (steps != h->backup_steps || !h->d_plan || !h->d_plan_next) {
+        h->backup_steps = 0; // (a failed attempt leaves the feature off, never a store of the wrong size)
+        OWN_TRY(h->d_plan.alloc(b * (size_t)steps * P.nu));
+        if (!h->d_plan_next) OWN_TRY(h->d_plan_next.alloc(b));
+    }
+    HIP_TRY(hipMemsetAsync(h->d_plan_next, 0, b * sizeof(int), h->last_stream)); // every plan is forgotten, behind the last solve / tick
+    h->backup_steps = steps;
     return COPRA_OK;
 }
 

@@ -191,6 +191,11 @@ struct copra_batch {
     std::map<int, LimitSchedule> cstr_sched; // limit schedules by constraint (position in the user's array) ...
     LimitSchedule lb_sched, ub_sched; // ... and of the control bounds (both live or neither)
     bool limit_sched_seen = false; // a limit schedule has written per-instance limits of this controller: its last window stays in force when it ends
+    // backup plans of the tick (copra_batch_set_backup_steps; copra_hip_plant.hip, plant_step.hpp)
+    int backup_steps = 0; // K: 0 is off
+    Dev<double> d_plan; // [batch][K][nu]: controls of steps 1 .. K of every instance's last successful solve
+    Dev<int> d_plan_next; // [batch]: the step of d_plan the next tick without a fresh solution applies (0: no plan, > K: used up)
+    bool plan_fresh = false; // a solve has been launched since the previous plant step (set by copra_batch_solve, cleared by the tick)
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation

@@ -5,6 +5,14 @@
 //   ok = status[b] == COPRA_QP_OK;   u = ok ? control[b][0 .. nu) : fallback_u ? fallback_u[b] : none
 //   x+ = (ok || fallback_u) ? Ap[b] x0[b] + Bp[b] u + dp[b] (+ w[b]) : x0[b]            (no fallback: the state is HELD, bit for bit)
 // A failed instance's control holds NaN: the status is looked at FIRST, the control of a failed instance is never loaded.
+// With backup plans (copra_batch_set_backup_steps, K = backup_steps > 0) an instance without a fresh solution plays the tail of its last plan
+// that did solve before it falls back or is held; per instance the store is plan[b][K][nu] and next[b] (0: no plan, > K: used up):
+//   fresh && status[b] == COPRA_QP_OK : u = control[b][0 .. nu);  plan[b] = control[b][nu .. (K + 1) nu);  next[b] = 1;  age 0
+//   else 1 <= next[b] <= K            : u = plan[b][next[b] - 1];  age = next[b];  next[b] += 1
+//   else                              : fallback_u[b] (age -1) or held (age -2) as above, next[b] unchanged
+// next[b] is READ in phase 1 (by the nu threads that fetch the instance's control) and WRITTEN in phase 2, behind the barrier, by the one
+// thread that owns the instance; the age found in phase 1 goes through the LDS image beside the status.  An instance that reads plan[b] never
+// writes it in the same tick.  backup_steps == 0 takes the bodies below with kBackup = false: the image, the copies and the sums of ABI 9.
 //
 // A streaming kernel (about 600 B read, 50-130 B written per instance at xDim 6, uDim 3).  One workgroup takes `group` consecutive instances:
 // their A, B, d, x0, w blocks are ONE contiguous range per array, copied into LDS with wide coalesced loads (16 B per lane where the
@@ -51,7 +59,14 @@ struct PlantStepArgs {
     double* x0_next; // [batch][nx]; may be x0
     double *x_out, *u_out; // optional copies
     int* status_out;
+    int backup_steps; // K: controls of horizon steps 1 .. K kept per instance; 0: no backup plans (plan, next, fresh are not looked at)
+    int fresh; // a solve has been launched since the previous plant step: status / control are of THIS tick
+    double* plan; // [batch][backup_steps][nu]
+    int* next; // [batch]: the step of plan[b] the next tick without a fresh solution applies; 0: no plan yet, > backup_steps: used up
+    int* age_out; // optional [batch]: 0 fresh solution | j >= 1 step j of the plan | kPlantAgeFallback | kPlantAgeHeld
 };
+
+constexpr int kPlantAgeFallback = -1, kPlantAgeHeld = -2; // (COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD of include/copra_hip.h)
 
 struct alignas(16) PlantPair {
     double a, b;
@@ -66,11 +81,11 @@ inline bool plant_vec2_ok(const PlantStepArgs& P)
 
 COPRA_PLANT_HD int plant_even(int v) { return (v + 1) & ~1; }
 
-// LDS image of one workgroup, in doubles: A | B | d | x0 | w | u | status (ints); every part starts on 16 bytes
+// LDS image of one workgroup, in doubles: A | B | d | x0 | w | u | status (ints) [| age (ints), with backup plans]; every part starts on 16 bytes
 struct PlantLds {
-    int oA, oB, od, ox, ow, ou, ost, total;
+    int oA, oB, od, ox, ow, ou, ost, total, oag;
 };
-COPRA_PLANT_HD PlantLds plant_lds(int nx, int nu, int group, int shared, int has_w)
+COPRA_PLANT_HD PlantLds plant_lds(int nx, int nu, int group, int shared, int has_w, int backup = 0)
 {
     const int gs = shared ? 1 : group;
     PlantLds L;
@@ -82,6 +97,8 @@ COPRA_PLANT_HD PlantLds plant_lds(int nx, int nu, int group, int shared, int has
     L.ou = L.ow + (has_w ? plant_even(group * nx) : 0);
     L.ost = L.ou + plant_even(group * nu);
     L.total = L.ost + plant_even((group + 1) / 2);
+    L.oag = L.total;
+    if (backup) L.total += plant_even((group + 1) / 2);
     return L;
 }
 
@@ -109,13 +126,23 @@ COPRA_DEV double plant_row(int nx, int nu, int r, const double* A, const double*
     return acc;
 }
 
+// where instance b's control of this tick comes from (backup plans): 0, the step of its plan, kPlantAgeFallback or kPlantAgeHeld
+COPRA_DEV int plant_age(const PlantStepArgs& P, size_t b)
+{
+    if (P.fresh && P.status[b] == 0) return 0;
+    const int nxt = P.next[b];
+    if (nxt >= 1 && nxt <= P.backup_steps) return nxt;
+    return P.fallback_u ? kPlantAgeFallback : kPlantAgeHeld;
+}
+
 // phase 1: everything workgroup `wg` reads, into its image `lds`
-COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+template <bool kBackup>
+COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr);
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr, kBackup);
     const size_t s0 = P.shared ? 0 : (size_t)b0;
     const int scnt = P.shared ? 1 : cnt;
     plant_copy(lds + L.oA, P.A + s0 * nx * nx, scnt * nx * nx, tid, T, P.vec2);
@@ -125,28 +152,46 @@ COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, doubl
     if (P.w) plant_copy(lds + L.ow, P.w + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
     int* st = reinterpret_cast<int*>(lds + L.ost);
     for (int i = tid; i < cnt; i += T) st[i] = P.status[b0 + i];
+    if (kBackup) {
+        int* ag = reinterpret_cast<int*>(lds + L.oag);
+        for (int i = tid; i < cnt; i += T) ag[i] = plant_age(P, (size_t)b0 + i);
+    }
     for (int e = tid; e < cnt * nu; e += T) { // the control that is applied: the status decides BEFORE anything of `control` is touched
         const int i = e / nu, c = e - i * nu;
         const size_t b = (size_t)b0 + i;
         double u = NAN;
-        if (P.status[b] == 0) u = P.control[b * P.ctrl_stride + c];
-        else if (P.fallback_u) u = P.fallback_u[b * nu + c];
+        if (kBackup) { // (next[b] is only read here: its new value is written behind the barrier)
+            const int age = plant_age(P, b);
+            if (age == 0) u = P.control[b * P.ctrl_stride + c];
+            else if (age > 0) u = P.plan[(b * P.backup_steps + (age - 1)) * nu + c];
+            else if (age == kPlantAgeFallback) u = P.fallback_u[b * nu + c];
+        } else {
+            if (P.status[b] == 0) u = P.control[b * P.ctrl_stride + c];
+            else if (P.fallback_u) u = P.fallback_u[b * nu + c];
+        }
         lds[L.ou + e] = u;
     }
 }
+COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+{
+    if (P.backup_steps > 0) plant_stage_body<true>(P, wg, tid, T, lds);
+    else plant_stage_body<false>(P, wg, tid, T, lds);
+}
 
-// phase 2 (behind a barrier): the new states and the optional copies
-COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
+// phase 2 (behind a barrier): the new states and the optional copies; with backup plans the tails of the fresh plans and every next[b]
+template <bool kBackup>
+COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr);
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr, kBackup);
     const int* st = reinterpret_cast<const int*>(lds + L.ost);
+    const int* ag = reinterpret_cast<const int*>(lds + L.oag); // (read with backup plans only)
     for (int e = tid; e < cnt * nx; e += T) {
         const int i = e / nx, r = e - i * nx, is = P.shared ? 0 : i;
         double xn = lds[L.ox + e]; // held
-        if (st[i] == 0 || P.fallback_u)
+        if (kBackup ? ag[i] != kPlantAgeHeld : (st[i] == 0 || P.fallback_u))
             xn = plant_row(nx, nu, r, lds + L.oA + is * nx * nx, lds + L.oB + is * nx * nu, lds + L.od + is * nx, P.w ? lds + L.ow + i * nx : nullptr,
                 lds + L.ox + i * nx, lds + L.ou + i * nu);
         const size_t o = (size_t)b0 * nx + e;
@@ -157,6 +202,39 @@ COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const
         for (int e = tid; e < cnt * nu; e += T) P.u_out[(size_t)b0 * nu + e] = lds[L.ou + e];
     if (P.status_out)
         for (int i = tid; i < cnt; i += T) P.status_out[b0 + i] = st[i];
+    if (!kBackup) {
+        if (P.age_out)
+            for (int i = tid; i < cnt; i += T) P.age_out[b0 + i] = st[i] == 0 ? 0 : P.fallback_u ? kPlantAgeFallback : kPlantAgeHeld;
+        return;
+    }
+    // the tail of every fresh plan: controls of steps 1 .. K, K nu doubles per instance out of `control` (stride nu N; K <= N - 1: nothing
+    // beyond control[b][(K + 1) nu) is read) into the group's contiguous range of `plan`; only instances with a fresh solution are read
+    const int kn = P.backup_steps * nu;
+    const bool pairs = (nu & 1) == 0 && ((reinterpret_cast<uintptr_t>(P.plan) | reinterpret_cast<uintptr_t>(P.control)) & 15u) == 0;
+    if (pairs) { // (nu even: nu N, nu and K nu are even, every instance's tail starts on 16 bytes in both arrays)
+        const int kn2 = kn >> 1;
+        for (int e = tid; e < cnt * kn2; e += T) {
+            const int i = e / kn2, j = e - i * kn2;
+            const size_t b = (size_t)b0 + i;
+            if (ag[i] == 0) reinterpret_cast<PlantPair*>(P.plan + b * kn)[j] = reinterpret_cast<const PlantPair*>(P.control + b * P.ctrl_stride + nu)[j];
+        }
+    } else {
+        for (int e = tid; e < cnt * kn; e += T) {
+            const int i = e / kn, j = e - i * kn;
+            const size_t b = (size_t)b0 + i;
+            if (ag[i] == 0) P.plan[b * kn + j] = P.control[b * P.ctrl_stride + nu + j];
+        }
+    }
+    for (int i = tid; i < cnt; i += T) { // one thread per instance: the only writer of next[b], behind the barrier
+        const int age = ag[i];
+        if (age >= 0) P.next[b0 + i] = age + 1;
+        if (P.age_out) P.age_out[b0 + i] = age;
+    }
+}
+COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
+{
+    if (P.backup_steps > 0) plant_apply_body<true>(P, wg, tid, T, lds);
+    else plant_apply_body<false>(P, wg, tid, T, lds);
 }
 
 #if defined(__HIPCC__)

@@ -374,6 +374,9 @@ typedef struct {
     double* x_out; /* optional copies for the caller: [batch][nx], [batch][nu], [batch] */
     double* u_out;
     int* status_out;
+    int* age_out; /* optional [batch], device: where the applied control came from (backup plans below) */
+    int* age_hist; /* copra_batch_rollout only: [ticks][batch], device; tick t's age_out */
+    int solve_every; /* copra_batch_rollout only: 0 or 1: a solve at every tick; k > 1: a solve at the ticks t with t % k == 0 */
 } copra_plant_step_t;
 void copra_plant_step_init(copra_plant_step_t* step);
 copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* step, void* hip_stream);
@@ -381,6 +384,38 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
     double* u_hist, int* status_hist, void* hip_stream);
 const double* copra_batch_x0_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_x0(copra_batch_t* h, double* x0);
+
+/* ---- backup plans: what the tick does without a fresh solution (ABI 10).  A receding-horizon loop whose solve fails for a few ticks -- limits
+ *      that tighten (limit schedules below) make that an ordinary event -- keeps applying the tail u_1, u_2, ... of the last plan that did
+ *      solve until a solve succeeds again or the tail runs out; the reference's loop (include/LMPC.h:108) leaves that to its caller.
+ *      copra_batch_set_backup_steps(h, K): K = 0 (the state of a new handle): off, the store is released, the tick is the one above.
+ *      1 <= K <= N - 1: the library keeps per instance plan[b][K][nu], the controls of horizon steps 1 .. K of the instance's last successful
+ *      solve, and an int next[b], the step of that plan the next tick without a fresh solution applies (0: no plan yet, > K: used up).
+ *      A tick is FRESH when a copra_batch_solve has been launched since the previous copra_batch_advance (a flag of the handle: set by the
+ *      solve, cleared by the advance).  With K > 0 the tick's rule for instance b is
+ *        fresh && status[b] == COPRA_QP_OK :  u = control[b][0 .. nu);  plan[b][j-1] = control[b][j nu .. (j+1) nu), j = 1 .. K;
+ *                                             next[b] = 1;  age = 0
+ *        else if 1 <= next[b] <= K         :  u = plan[b][next[b] - 1];  age = next[b];  next[b] += 1
+ *        else if fallback_u                :  u = fallback_u[b];  age = COPRA_PLAN_FALLBACK  (next[b] unchanged)
+ *        else                              :  the state is kept bit for bit, u_out[b] = NaN;  age = COPRA_PLAN_HELD
+ *      and x+ = A[b] x0[b] + B[b] u + d[b] (+ w[b]) in the first three cases, exactly as above: the plan is applied to the PLANT, nothing is
+ *      taken from the model's trajectory.  The control of an instance whose solve failed holds NaN and is still never loaded, neither its
+ *      first nu entries nor its tail.  age_out[b] (optional) receives `age`.  status_out stays the content of the status buffer: on a tick
+ *      without a solve that is the LAST solve's status, so it is stale -- age_out is what says where a control came from.
+ *      With K = 0 age_out receives 0 / COPRA_PLAN_FALLBACK / COPRA_PLAN_HELD by the three cases of the tick above, and `fresh` is not looked
+ *      at: a second copra_batch_advance without a solve applies u_0 again.
+ *      EVERY call forgets all plans (next <- 0, asynchronously on the stream of the last solve / tick), also one that repeats the K in force.
+ *      copra_batch_set_x0 and copra_batch_set_system do NOT touch the plans: a caller that starts a new episode calls
+ *      copra_batch_set_backup_steps again.
+ *      Multi-rate loops: copra_batch_rollout with copra_plant_step_t::solve_every = k > 1 launches a solve at the ticks t with t % k == 0
+ *      only; the ticks in between play the plan (ages 1 .. k - 1), the plant and the tick counter of the schedules move at every tick, so the
+ *      next solve reads the right window.  It needs K >= k - 1.  age_hist[t] is tick t's age_out.  copra_batch_advance ignores solve_every and
+ *      age_hist.
+ *      COPRA_ERR_ARG: K outside 0 .. N - 1, a NULL handle, solve_every < 0, solve_every = k > 1 with K < k - 1; COPRA_ERR_UNSUPPORTED: an
+ *      InitialStateLMPC controller (as for the tick itself). ---- */
+#define COPRA_PLAN_FALLBACK (-1) /* age_out: fallback_u was applied */
+#define COPRA_PLAN_HELD (-2) /* age_out: the state was kept */
+copra_status_t copra_batch_set_backup_steps(copra_batch_t* h, int steps);
 
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
