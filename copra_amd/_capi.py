@@ -63,6 +63,12 @@ class PlantStep(C.Structure):
                 ("age_out", C.c_void_p), ("age_hist", C.c_void_p), ("solve_every", C.c_int)]
 
 
+class PlantStepEx(C.Structure):
+    """copra_plant_step_ex_t: copra_plant_step_t grown at its end by the disturbance estimator's outputs -- the same bytes as a struct whose
+    first member is a PlantStep (its size is a multiple of 8), written flat so that st.A, st.w, ... read as on a PlantStep"""
+    _fields_ = PlantStep._fields_ + [("d_out", C.c_void_p), ("d_hist", C.c_void_p)]
+
+
 PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
@@ -358,11 +364,21 @@ def lib():
         L.copra_plant_step_init.restype = None
         L.copra_plant_step_init.argtypes = [C.POINTER(PlantStep)]
         L.copra_batch_advance.restype = C.c_int
-        L.copra_batch_advance.argtypes = [vp, C.POINTER(PlantStep), vp]
+        L.copra_plant_step_ex_init.restype = None
+        L.copra_plant_step_ex_init.argtypes = [C.POINTER(PlantStepEx)]
+        L.copra_batch_advance.argtypes = [vp, vp, vp]  # (a PlantStep or a PlantStepEx by reference: struct_size says which)
         L.copra_batch_rollout.restype = C.c_int
-        L.copra_batch_rollout.argtypes = [vp, C.POINTER(PlantStep), C.c_int, vp, vp, vp, vp, vp]
+        L.copra_batch_rollout.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.copra_batch_set_backup_steps.restype = C.c_int
         L.copra_batch_set_backup_steps.argtypes = [vp, C.c_int]
+        L.copra_batch_set_bias_estimator.restype = C.c_int
+        L.copra_batch_set_bias_estimator.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+        L.copra_batch_set_bias.restype = C.c_int
+        L.copra_batch_set_bias.argtypes = [vp, vp, C.c_int]
+        L.copra_batch_bias_device.restype = vp
+        L.copra_batch_bias_device.argtypes = [vp]
+        L.copra_batch_get_bias.restype = C.c_int
+        L.copra_batch_get_bias.argtypes = [vp, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -42,6 +42,7 @@ class BatchLMPC:
         self._ref_keep = {}  # torch tensors used in place as per-instance cost references, by cost index
         self._w_keep = {}  # ... and as per-instance cost weights
         self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
+        self._bias_keep = None  # ... and as the disturbance estimator's gain (set_bias_estimator)
         self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
@@ -408,9 +409,72 @@ class BatchLMPC:
         0: off.  Every call forgets all plans, also with the K in force; set_x0 / set_system do not: call this again for a new episode."""
         _capi.check(self._lib.copra_batch_set_backup_steps(self._h, int(steps)))
 
-    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None):
-        st = _capi.PlantStep()
-        self._lib.copra_plant_step_init(C.byref(st))
+    def set_bias_estimator(self, gain):
+        """The disturbance estimator of the tick (copra_batch_set_bias_estimator): after every advance() the d of each instance's model moves
+        by gain @ (x+ - prediction of the model for the applied control), so a constant load or a mismatched plant no longer leaves an
+        offset.  gain of shape (nx,): one diagonal gain for the batch; (batch, nx): one per instance; (nx, nx): one dense gain L in natural
+        indexing (transposed here to the ABI's column-major); (batch, nx, nx): one per instance -- with batch == nx a 2-d gain is read as
+        (nx, nx).  numpy: copied; a torch CUDA float64 tensor: in ABI layout already, used in place and kept alive.  The estimates live in a
+        buffer of the library that becomes the controller's d (bias(), bias_ptr()); a tensor given to set_system is not written.  None
+        ends the estimator and keeps the last estimates as d.  set_system while on restarts the estimates from the new d;
+        set_shared_system ends the estimator."""
+        if gain is None:
+            _capi.check(self._lib.copra_batch_set_bias_estimator(self._h, None, 0, 0, 0))
+            self._bias_keep = None
+            return
+        b, nx = self.batch, self.nx
+        torch_in = _is_torch(gain)
+        if torch_in:
+            if not (gain.is_cuda and gain.is_contiguous() and str(gain.dtype) == "torch.float64"):
+                raise ValueError("set_bias_estimator: a contiguous CUDA float64 tensor is needed")
+            g = gain
+        else:
+            g = np.asarray(gain, dtype=np.float64)
+        shape = tuple(g.shape)
+        if shape == (nx,):
+            dense, per = 0, 0
+        elif shape == (nx, nx):
+            dense, per = 1, 0
+        elif shape == (b, nx):
+            dense, per = 0, 1
+        elif shape == (b, nx, nx):
+            dense, per = 1, 1
+        else:
+            raise _capi.CopraDomainError("set_bias_estimator: expected (%d,), (%d, %d), (%d, %d) or (%d, %d, %d), got %s" % (nx, b, nx, nx, nx, b, nx, nx, shape))
+        if torch_in:
+            ptr = g.data_ptr()
+        else:
+            g = np.ascontiguousarray(np.swapaxes(g, -1, -2) if dense else g)
+            ptr = g.ctypes.data
+        _capi.check(self._lib.copra_batch_set_bias_estimator(self._h, ptr, dense, per, 1 if torch_in else 0))
+        self._bias_keep = gain if torch_in else None
+
+    def set_bias(self, d):
+        """restart the estimates (copra_batch_set_bias): d of shape (batch, nx), numpy (copied) or a torch CUDA float64 tensor (copied on the
+        stream of the last tick)"""
+        if _is_torch(d):
+            ptr, _ = self._device(d, (self.batch, self.nx), "set_bias")
+            _capi.check(self._lib.copra_batch_set_bias(self._h, ptr, 1))
+        else:
+            db = np.ascontiguousarray(d, dtype=np.float64)
+            if db.shape != (self.batch, self.nx):
+                raise _capi.CopraDomainError("set_bias: expected %s, got %s" % ((self.batch, self.nx), db.shape))
+            _capi.check(self._lib.copra_batch_set_bias(self._h, db.ctypes.data, 0))
+
+    def bias(self):
+        """the d the next solve reads, (batch, nx), as a numpy copy (copra_batch_get_bias: waits for the last tick): the estimates while the
+        estimator is or was on"""
+        out = np.empty((self.batch, self.nx))
+        _capi.check(self._lib.copra_batch_get_bias(self._h, out.ctypes.data))
+        return out
+
+    def bias_ptr(self):
+        """device pointer of the d the next solve reads (copra_batch_bias_device)"""
+        return int(self._lib.copra_batch_bias_device(self._h) or 0)
+
+    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None):
+        st = _capi.PlantStepEx()
+        self._lib.copra_plant_step_ex_init(C.byref(st))
         b, nx, nu = self.batch, self.nx, self.nu
         if plant is not None:
             A, B, d = plant
@@ -428,11 +492,12 @@ class BatchLMPC:
         st.u_out, uo = self._output(u_out, (b, nu), "u_out")
         st.status_out, so = self._output(status_out, (b,), "status_out", "int32")
         st.age_out, ao = self._output(age_out, (b,), "age_out", "int32")
-        keep.extend([t1, t2, xo, uo, so, ao])
-        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao)
+        st.d_out, do = self._output(d_out, (b, nx), "d_out")
+        keep.extend([t1, t2, xo, uo, so, ao, do])
+        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao, d_out=do)
 
     def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None,
-                age_out=None):
+                age_out=None, d_out=None):
         """The second half of a tick (copra_batch_advance): apply the first control of the last solve to the plant and make the result the next
         initial state -- x+ = A x0 + B u + d (+ disturbance) where the solve succeeded (or fallback_control (batch, nu) is given); an instance
         whose solve failed keeps its state otherwise.  Asynchronous on `stream`, behind the solve.
@@ -442,27 +507,30 @@ class BatchLMPC:
         here).  age_out: int32 (batch,), the same way: where each instance's control came from -- 0 this tick's solve, j >= 1 step j of its
         backup plan (set_backup_steps), _capi.PLAN_FALLBACK (-1) fallback_control, _capi.PLAN_HELD (-2) the state was kept; on a tick without
         a solve status_out is the last solve's and only age_out tells.  Returns dict(x_out, u_out, status_out, age_out) of those tensors
-        (None where not asked for).  The state lives in a buffer of the library afterwards (state(), state_ptr()): a tensor given to set_x0
+        (None where not asked for).  d_out: (batch, nx), the same way: the disturbance estimates after the tick (set_bias_estimator; not written
+        while the estimator is off), returned under "d_out".  The state lives in a buffer of the library afterwards (state(), state_ptr()): a tensor given to set_x0
         is not written."""
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out)
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out)
         _capi.check(self._lib.copra_batch_advance(self._h, C.byref(st), C.c_void_p(stream or 0)))
         self._tick_keep = keep
         return outs
 
     def rollout(self, ticks, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None,
-                disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None, age_out=None, age_hist=None, solve_every=1):
+                disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None, age_out=None, age_hist=None, solve_every=1,
+                d_out=None, d_hist=None):
         """`ticks` x (solve(), advance(...)) enqueued on `stream` by ONE call (copra_batch_rollout): the closed loop never returns to the host.
         disturbances: (ticks, batch, nx), tick t's replaces `disturbance`; x_hist (ticks + 1, batch, nx) -- [0] is the state the first solve
         read --, u_hist (ticks, batch, nu), status_hist int32 (ticks, batch): torch CUDA tensors written in place, or True (allocated here).
         age_hist int32 (ticks, batch): tick t's age_out (see advance).  solve_every = k > 1: a solve at the ticks t with t % k == 0 only, the
         ticks in between play the backup plan -- needs set_backup_steps(K) with K >= k - 1.
-        Returns dict(x_hist, u_hist, status_hist, age_hist, x_out, u_out, status_out, age_out)."""
+        d_hist (ticks, batch, nx): tick t's d_out, the disturbance estimates the solve of tick t + 1 reads (set_bias_estimator).
+        Returns dict(x_hist, u_hist, status_hist, age_hist, d_hist, x_out, u_out, status_out, age_out, d_out)."""
         ticks = int(ticks)
         if ticks < 0:
             raise ValueError("rollout: ticks < 0")
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out)
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out)
         b, nx, nu = self.batch, self.nx, self.nu
         wp, wt = self._device(disturbances, (ticks, b, nx), "disturbances")
         xp, xt = self._output(x_hist, (ticks + 1, b, nx), "x_hist")
@@ -470,10 +538,11 @@ class BatchLMPC:
         sp, stt = self._output(status_hist, (ticks, b), "status_hist", "int32")
         st.age_hist, at = self._output(age_hist, (ticks, b), "age_hist", "int32")
         st.solve_every = int(solve_every)
-        keep.extend([wt, xt, ut, stt, at])
+        st.d_hist, dt = self._output(d_hist, (ticks, b, nx), "d_hist")
+        keep.extend([wt, xt, ut, stt, at, dt])
         _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, wp, xp, up, sp, C.c_void_p(stream or 0)))
         self._tick_keep = keep
-        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at)
+        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at, d_hist=dt)
 
     def state(self):
         """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""

@@ -4,11 +4,14 @@
 // follows a schedule (copra_batch_set_reference_schedule) gets the window of the new tick behind every plant step (kernel: ref_window.hpp),
 // and so does a limit that follows one (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; kernel: limit_window.hpp).
 // copra_batch_set_backup_steps: an instance without a fresh solution plays the tail of its last plan (the store: d_plan, d_plan_next).
+// copra_batch_set_bias_estimator / _set_bias / _bias_device / _get_bias: the disturbance estimator -- the plant step moves every instance's d
+// (d_bias, the controller's d while the estimates are in force) by a gain times the model's prediction error, in the same launch.
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
 #include "ref_window.hpp"
 
+#include <cstddef>
 #include <cstring>
 
 namespace {
@@ -17,20 +20,22 @@ constexpr size_t kPlantLdsTarget = 24 * 1024; // a group's image: small enough f
 constexpr size_t kPlantLdsMax = 160 * 1024; // one instance's image at most (the CU's LDS)
 constexpr int kPlantGroupMax = 32;
 
-// the caller's struct as THIS library knows it: fields beyond the caller's struct_size keep their defaults (all zero)
-copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_t& out, const char* who)
+// the caller's struct as THIS library knows it -- the widest form, copra_plant_step_ex_t, whose first member is the struct a caller of ABI 10
+// passes: fields beyond the caller's struct_size keep their defaults (all zero)
+copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_ex_t& out, const char* who)
 {
     std::memset(&out, 0, sizeof out);
-    out.struct_size = (int)sizeof out;
+    out.step.struct_size = (int)sizeof out;
     if (!step) return COPRA_OK;
     if (step->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_plant_step_t::struct_size is not set (copra_plant_step_init)");
     const size_t known = (size_t)step->struct_size < sizeof out ? (size_t)step->struct_size : sizeof out;
     std::memcpy(&out, step, known);
-    out.struct_size = (int)sizeof out;
-    const int given = (out.A != nullptr) + (out.B != nullptr) + (out.d != nullptr);
+    out.step.struct_size = (int)sizeof out;
+    const int given = (out.step.A != nullptr) + (out.step.B != nullptr) + (out.step.d != nullptr);
     if (given != 0 && given != 3) return fail(COPRA_ERR_ARG, std::string(who) + ": a plant needs all of A, B and d (or none of them: the controller's model)");
     return COPRA_OK;
 }
+static_assert(offsetof(copra_plant_step_ex_t, d_out) == sizeof(copra_plant_step_t), "copra_plant_step_ex_t is copra_plant_step_t grown at its end");
 
 // what can be said before any solve: the handle takes part in closed-loop ticks at all
 copra_status_t check_handle(const copra_batch* h, const char* who)
@@ -132,9 +137,25 @@ copra_status_t own_schedule(LimitSchedule& ls, const double* sched, size_t count
     return COPRA_OK;
 }
 
+// instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes;
+// `one` is one instance's image in bytes
+int plant_group(size_t one)
+{
+    int group = (int)(kPlantLdsTarget / one);
+    group = group > kPlantGroupMax ? kPlantGroupMax : group < 1 ? 1 : group;
+    if (group > 1) group &= ~1;
+    return group;
+}
+
+// one instance's image with the disturbance estimator, in bytes: the widest the tick can ask for with this gain (a plant of its own, w, ages)
+size_t bias_image_bytes(int nx, int nu, int dense)
+{
+    return (size_t)plant_est_lds(nx, nu, 1, 0, 1, 1, 0, dense, 0).total * sizeof(double);
+}
+
 // one plant step behind the last launched solve; `st` has been through read_step
 copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const double* w, double* x_out, double* u_out, int* status_out, int* age_out,
-    hipStream_t s, const char* who)
+    double* d_out, hipStream_t s, const char* who)
 {
     const FusedPlan& HP = h->hp.plan;
     if (!h->ad.solved_once) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no solve has been launched (copra_batch_solve)");
@@ -177,23 +198,33 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
         P.plan = h->d_plan;
         P.next = h->d_plan_next;
     }
-    // instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes
-    const size_t one = (size_t)plant_lds(P.nx, P.nu, 1, 0, 1).total * sizeof(double);
+    if (h->bias_on) { // the disturbance estimator: the model beside the plant, the estimates (the controller's d) updated in place
+        if (h->shared || !h->A || !h->B || h->d != h->d_bias) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the disturbance estimator has lost its model");
+        P.est = 1;
+        P.same_model = st.A == nullptr; // (P.A, P.B, P.d are h->A, h->B and the estimates then)
+        P.Am = h->A, P.Bm = h->B;
+        P.dhat = h->d_bias;
+        P.gain = h->bias_gain;
+        P.gain_dense = h->bias_dense, P.gain_shared = !h->bias_per_instance;
+        P.d_out = d_out;
+    }
+    const size_t one = P.est ? bias_image_bytes(P.nx, P.nu, P.gain_dense) : (size_t)plant_lds(P.nx, P.nu, 1, 0, 1).total * sizeof(double);
     if (one > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's plant does not fit the LDS (xDim beyond about 130)");
-    int group = (int)(kPlantLdsTarget / one);
-    group = group > kPlantGroupMax ? kPlantGroupMax : group < 1 ? 1 : group;
-    if (group > 1) group &= ~1;
+    const int group = plant_group(one);
     P.group = group;
     P.vec2 = plant_vec2_ok(P);
-    const size_t lds_bytes = (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0).total * sizeof(double);
-    if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_plant_step_kernel, lds_bytes);
+    const size_t lds_doubles = P.est ? (size_t)plant_est_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0, P.same_model, P.gain_dense, P.gain_shared).total
+                                     : (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0).total;
+    const size_t lds_bytes = lds_doubles * sizeof(double);
+    void (*const kernel)(const PlantStepArgs) = P.est ? copra_plant_step_kernel<true> : copra_plant_step_kernel<false>;
+    if (lds_bytes > 48 * 1024) LDS_OPT_IN(kernel, lds_bytes);
     if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
         if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
         HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
     }
     const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
-    hipLaunchKernelGGL(copra_plant_step_kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
     HIP_TRY(hipGetLastError());
     h->x0 = h->own_x0;
     h->plan_fresh = false;
@@ -213,14 +244,22 @@ void copra_plant_step_init(copra_plant_step_t* step)
     step->struct_size = (int)sizeof *step;
 }
 
+void copra_plant_step_ex_init(copra_plant_step_ex_t* step)
+{
+    if (!step) return;
+    std::memset(step, 0, sizeof *step);
+    step->step.struct_size = (int)sizeof *step;
+}
+
 copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* step, void* hip_stream)
 {
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_advance: null handle");
-    copra_plant_step_t st;
-    copra_status_t rc = read_step(step, st, "copra_batch_advance");
+    copra_plant_step_ex_t ex;
+    copra_status_t rc = read_step(step, ex, "copra_batch_advance");
+    const copra_plant_step_t& st = ex.step;
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_advance");
     if (rc != COPRA_OK) return rc;
-    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, st.age_out, (hipStream_t)hip_stream, "copra_batch_advance");
+    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, st.age_out, ex.d_out, (hipStream_t)hip_stream, "copra_batch_advance");
 }
 
 copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* step, int ticks, const double* w_seq, double* x_hist, double* u_hist,
@@ -228,8 +267,9 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
 {
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_rollout: null handle");
     if (ticks < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative number of ticks");
-    copra_plant_step_t st;
-    copra_status_t rc = read_step(step, st, "copra_batch_rollout");
+    copra_plant_step_ex_t ex;
+    copra_status_t rc = read_step(step, ex, "copra_batch_rollout");
+    const copra_plant_step_t& st = ex.step;
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_rollout");
     if (rc != COPRA_OK) return rc;
     const int every = st.solve_every;
@@ -249,7 +289,8 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
             if (rc != COPRA_OK) return rc;
         }
         rc = advance(h, st, w_seq ? w_seq + (size_t)t * nd : st.w, x_hist ? x_hist + (size_t)(t + 1) * nd : st.x_out, u_hist ? u_hist + (size_t)t * nc : st.u_out,
-            status_hist ? status_hist + (size_t)t * nb : st.status_out, st.age_hist ? st.age_hist + (size_t)t * nb : st.age_out, s, "copra_batch_rollout");
+            status_hist ? status_hist + (size_t)t * nb : st.status_out, st.age_hist ? st.age_hist + (size_t)t * nb : st.age_out,
+            ex.d_hist ? ex.d_hist + (size_t)t * nd : ex.d_out, s, "copra_batch_rollout");
         if (rc != COPRA_OK) return rc;
     }
     return COPRA_OK;
@@ -277,6 +318,79 @@ copra_status_t copra_batch_set_backup_steps(copra_batch_t* h, int steps)
     }
     HIP_TRY(hipMemsetAsync(h->d_plan_next, 0, b * sizeof(int), h->last_stream)); // every plan is forgotten, behind the last solve / tick
     h->backup_steps = steps;
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_bias_estimator(copra_batch_t* h, const double* gain, int dense, int per_instance, int on_device)
+{
+    const char* const who = "copra_batch_set_bias_estimator";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    if (!gain) { // the estimator ends; the last estimates stay the model's d (h->d keeps pointing at them)
+        h->bias_on = false;
+        h->bias_gain = nullptr;
+        return COPRA_OK;
+    }
+    if (h->shared || h->shared_as_batch)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one model for the batch (copra_batch_set_shared_system) has one d; write the model out with copra_batch_set_system");
+    if (!h->A || !h->B || !h->d) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no preview system set (copra_batch_set_system)");
+    const FusedPlan& P = h->hp.plan;
+    if (bias_image_bytes(P.nx, P.nu, dense != 0) > kPlantLdsMax)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's model, plant and gain do not fit the LDS");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), nd = (size_t)P.batch * P.nx;
+    if (!on_device) { // the library's copy: a tick that still reads the old one first
+        const size_t count = (per_instance ? b : 1) * (size_t)P.nx * (dense ? P.nx : 1);
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        if (h->own_bias_gain.count() < count) {
+            h->bias_on = false; // (it may be the copy that goes)
+            OWN_TRY(h->own_bias_gain.alloc(count));
+        }
+        HIP_TRY(hipMemcpy(h->own_bias_gain, gain, count * sizeof(double), hipMemcpyHostToDevice));
+        gain = h->own_bias_gain;
+    }
+    if (!h->d_bias) OWN_TRY(h->d_bias.alloc(b * (size_t)P.nx));
+    if (h->d != h->d_bias) { // the d in force seeds the estimates, behind the last solve / tick; a caller's buffer is read, never written
+        if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
+        h->d = h->d_bias;
+    }
+    h->bias_gain = gain;
+    h->bias_dense = dense != 0, h->bias_per_instance = per_instance != 0;
+    h->bias_on = true;
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_device)
+{
+    const char* const who = "copra_batch_set_bias";
+    if (!h || !d) return fail(COPRA_ERR_ARG, std::string(who) + ": null argument");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    if (h->shared || h->shared_as_batch) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one model for the batch has no per-instance estimates");
+    if (!h->d_bias || h->d != h->d_bias)
+        return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the library's estimates are not the d in force (copra_batch_set_bias_estimator)");
+    const size_t bytes = (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double);
+    if (!bytes) return COPRA_OK;
+    if (on_device) {
+        HIP_TRY(hipMemcpyAsync(h->d_bias, d, bytes, hipMemcpyDeviceToDevice, h->last_stream));
+    } else {
+        HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a tick that still writes the estimates)
+        HIP_TRY(hipMemcpy(h->d_bias, d, bytes, hipMemcpyHostToDevice));
+    }
+    return COPRA_OK;
+}
+
+const double* copra_batch_bias_device(const copra_batch_t* h)
+{
+    return h && !h->shared ? h->d : nullptr;
+}
+
+copra_status_t copra_batch_get_bias(copra_batch_t* h, double* d)
+{
+    if (!h || !d) return fail(COPRA_ERR_ARG, "copra_batch_get_bias: null argument");
+    if (h->shared || !h->d) return fail(COPRA_ERR_RUNTIME, "copra_batch_get_bias: no per-instance preview system set (copra_batch_set_system)");
+    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    HIP_TRY(hipMemcpy(d, h->d, (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double), hipMemcpyDeviceToHost));
     return COPRA_OK;
 }
 

@@ -178,7 +178,7 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
         h->B = B;
         h->d = d;
         h->x0 = x0;
-        return COPRA_OK;
+        return bias_restart(h, h->last_stream); // (estimator on: the caller's d is copied, not adopted)
     }
     const size_t nA = b * P.nx * P.nx, nB = b * P.nx * P.nu, nd = b * P.nx;
     if (!h->own_A) {
@@ -195,7 +195,7 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
     h->B = h->own_B;
     h->d = h->own_d;
     h->x0 = h->own_x0;
-    return COPRA_OK;
+    return bias_restart(h, h->last_stream);
 }
 
 } // extern "C"
@@ -251,7 +251,7 @@ copra_status_t copra_batch_set_system_rowmajor_async(copra_batch_t* h, const dou
     h->B = h->own_B;
     h->d = d; // (vectors have no layout: used in place)
     h->x0 = x0;
-    return COPRA_OK;
+    return bias_restart(h, s); // (estimator on: d is read once more, on `s`, for the copy the estimates restart from)
 }
 
 int copra_batch_lanes_per_instance(const copra_batch_t* h)

@@ -196,6 +196,12 @@ struct copra_batch {
     Dev<double> d_plan; // [batch][K][nu]: controls of steps 1 .. K of every instance's last successful solve
     Dev<int> d_plan_next; // [batch]: the step of d_plan the next tick without a fresh solution applies (0: no plan, > K: used up)
     bool plan_fresh = false; // a solve has been launched since the previous plant step (set by copra_batch_solve, cleared by the tick)
+    // disturbance estimator of the tick (copra_batch_set_bias_estimator; copra_hip_plant.hip, plant_step.hpp)
+    bool bias_on = false;
+    int bias_dense = 0, bias_per_instance = 0;
+    const double* bias_gain = nullptr; // device: the caller's, or own_bias_gain
+    Dev<double> own_bias_gain; // the library's copy of a host gain
+    Dev<double> d_bias; // [batch][nx]: the estimates; the controller's d (h->d) from the moment the estimator is turned on -- never own_d
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -274,6 +280,22 @@ inline int live_limit_windows(const copra_batch* h)
     int n = (h->lb_sched.sched != nullptr) + (h->ub_sched.sched != nullptr);
     for (const auto& kv : h->cstr_sched) n += kv.second.sched != nullptr;
     return n;
+}
+
+// A new system (h->d) while the disturbance estimator is on: the estimates restart from its d -- copied on `s`, behind the last tick, into
+// the library's buffer, which stays the controller's d; the new d itself is only read
+inline copra_status_t bias_restart(copra_batch* h, hipStream_t s)
+{
+    if (!h->bias_on || !h->d_bias || h->d == h->d_bias) return COPRA_OK;
+    const size_t nd = (size_t)h->hp.plan.batch * h->hp.plan.nx;
+    if (s != h->last_stream) { // (a tick that still writes the estimates)
+        if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
+        HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
+    }
+    if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
+    h->d = h->d_bias;
+    return COPRA_OK;
 }
 
 // ---- copra_hip.hip ----

@@ -23,6 +23,17 @@
 //
 // The two phases are COPRA_DEV functions of (workgroup, thread) that also compile on the host: tests/emu/emu_plant.cpp walks them thread by
 // thread with a host buffer in the place of LDS.
+//
+// The disturbance estimator (copra_batch_set_bias_estimator, PlantStepArgs::est) adds a third phase to the same kernel, built with kEst = true;
+// est == 0 launches the kernel built with kEst = false: the two phases, the image and the copies above, nothing else.  With dhat the
+// controller's d (the buffer the next solve reads), Am / Bm the controller's MODEL of the instance and u the control this tick applied:
+//   pred_r = dhat_r + sum_j Am[r,j] x_j + sum_c Bm[r,c] u_c      (no w);      e_r = x+_r - pred_r
+//   dhat+_r = dhat_r + sum_j L[r,j] e_j  (dense gain, column-major)    |    dhat_r + l_r e_r  (diagonal gain);      d_out = dhat+
+// and an instance whose state is held keeps dhat bit for bit.  Phase 1 also stages Am, Bm, dhat and the gain -- with no plant of its own the
+// plant IS the model with d = dhat: A, B, d are then the same arrays and are staged once (same_model); a gain shared by the batch once per
+// workgroup.  Phase 2 leaves x+ in LDS as well.  Phase 3 (plant_estimate, behind the second barrier) forms e per (instance, row) into LDS;
+// the dense gain reads all rows' e of its instance, so the update (plant_estimate_store) stands behind a third barrier and stores dhat and
+// d_out as one contiguous range per group.  dhat is updated in place: every read of it is into LDS in phase 1, one workgroup owns an instance.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -64,6 +75,13 @@ struct PlantStepArgs {
     double* plan; // [batch][backup_steps][nu]
     int* next; // [batch]: the step of plan[b] the next tick without a fresh solution applies; 0: no plan yet, > backup_steps: used up
     int* age_out; // optional [batch]: 0 fresh solution | j >= 1 step j of the plan | kPlantAgeFallback | kPlantAgeHeld
+    int est; // the disturbance estimator is on (everything below is looked at only then)
+    int same_model; // no plant of its own: A, B ARE the model and d IS dhat (per instance, never `shared`); Am, Bm are not looked at
+    int gain_dense, gain_shared; // gain: [nx x nx] column-major | [nx];  one for the batch | one per instance
+    const double *Am, *Bm; // the controller's model, [batch][nx x nx], [batch][nx x nu]
+    const double* gain;
+    double* dhat; // [batch][nx]: the controller's d, read in phase 1, written behind the last barrier
+    double* d_out; // optional [batch][nx]: a copy of the new estimates
 };
 
 constexpr int kPlantAgeFallback = -1, kPlantAgeHeld = -2; // (COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD of include/copra_hip.h)
@@ -76,6 +94,7 @@ struct alignas(16) PlantPair {
 inline bool plant_vec2_ok(const PlantStepArgs& P)
 {
     const auto ok = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    if (P.est && !(ok(P.Am) && ok(P.Bm) && ok(P.gain) && ok(P.dhat))) return false;
     return P.group % 2 == 0 && ok(P.A) && ok(P.B) && ok(P.d) && ok(P.x0) && ok(P.w);
 }
 
@@ -100,6 +119,33 @@ COPRA_PLANT_HD PlantLds plant_lds(int nx, int nu, int group, int shared, int has
     L.oag = L.total;
     if (backup) L.total += plant_even((group + 1) / 2);
     return L;
+}
+
+// ... and with the estimator, behind it: [Am | Bm | dhat, with a plant of its own] | gain | x+ | e; with same_model dhat is the image's d
+struct PlantEstLds {
+    PlantLds base;
+    int oAm, oBm, odh, oG, oxn, oe, total;
+};
+COPRA_PLANT_HD PlantEstLds plant_est_lds(int nx, int nu, int group, int shared, int has_w, int backup, int same_model, int gain_dense, int gain_shared)
+{
+    PlantEstLds E;
+    E.base = plant_lds(nx, nu, group, shared, has_w, backup);
+    int o = E.base.total;
+    E.oAm = E.base.oA, E.oBm = E.base.oB, E.odh = E.base.od;
+    if (!same_model) {
+        E.oAm = o, o += plant_even(group * nx * nx);
+        E.oBm = o, o += plant_even(group * nx * nu);
+        E.odh = o, o += plant_even(group * nx);
+    }
+    E.oG = o, o += plant_even((gain_shared ? 1 : group) * (gain_dense ? nx * nx : nx));
+    E.oxn = o, o += plant_even(group * nx);
+    E.oe = o, o += plant_even(group * nx);
+    E.total = o;
+    return E;
+}
+COPRA_DEV PlantEstLds plant_est_lds(const PlantStepArgs& P, int backup)
+{
+    return plant_est_lds(P.nx, P.nu, P.group, P.shared, P.w != nullptr, backup, P.same_model, P.gain_dense, P.gain_shared);
 }
 
 // dst[0 .. count) = src[0 .. count), thread `tid` of `T`: consecutive lanes, consecutive addresses
@@ -136,7 +182,7 @@ COPRA_DEV int plant_age(const PlantStepArgs& P, size_t b)
 }
 
 // phase 1: everything workgroup `wg` reads, into its image `lds`
-template <bool kBackup>
+template <bool kBackup, bool kEst = false>
 COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
@@ -171,6 +217,16 @@ COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, 
         }
         lds[L.ou + e] = u;
     }
+    if (kEst) { // the model, the estimates and the gain (same_model: A, B, d above were the model and the estimates)
+        const PlantEstLds E = plant_est_lds(P, kBackup);
+        if (!P.same_model) {
+            plant_copy(lds + E.oAm, P.Am + (size_t)b0 * nx * nx, cnt * nx * nx, tid, T, P.vec2);
+            plant_copy(lds + E.oBm, P.Bm + (size_t)b0 * nx * nu, cnt * nx * nu, tid, T, P.vec2);
+            plant_copy(lds + E.odh, P.dhat + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+        }
+        const int g1 = P.gain_dense ? nx * nx : nx;
+        plant_copy(lds + E.oG, P.gain + (P.gain_shared ? 0 : (size_t)b0 * g1), (P.gain_shared ? 1 : cnt) * g1, tid, T, P.vec2);
+    }
 }
 COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
@@ -179,8 +235,8 @@ COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, doubl
 }
 
 // phase 2 (behind a barrier): the new states and the optional copies; with backup plans the tails of the fresh plans and every next[b]
-template <bool kBackup>
-COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
+template <bool kBackup, bool kEst = false>
+COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, const double* lds, double* xn_lds = nullptr)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
@@ -197,6 +253,7 @@ COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, 
         const size_t o = (size_t)b0 * nx + e;
         P.x0_next[o] = xn;
         if (P.x_out) P.x_out[o] = xn;
+        if (kEst) xn_lds[e] = xn; // (with the estimator: row r of x+ stays in the image for phase 3)
     }
     if (P.u_out)
         for (int e = tid; e < cnt * nu; e += T) P.u_out[(size_t)b0 * nu + e] = lds[L.ou + e];
@@ -237,14 +294,88 @@ COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const
     else plant_apply_body<false>(P, wg, tid, T, lds);
 }
 
+
+// ---- the same two phases with the estimator (est != 0), and its own ----
+COPRA_DEV void plant_stage_est(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+{
+    if (P.backup_steps > 0) plant_stage_body<true, true>(P, wg, tid, T, lds);
+    else plant_stage_body<false, true>(P, wg, tid, T, lds);
+}
+COPRA_DEV void plant_apply_est(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+{
+    if (P.backup_steps > 0) plant_apply_body<true, true>(P, wg, tid, T, lds, lds + plant_est_lds(P, 1).oxn);
+    else plant_apply_body<false, true>(P, wg, tid, T, lds, lds + plant_est_lds(P, 0).oxn);
+}
+
+// whether instance i of the group had a control applied (phase 2's own condition)
+COPRA_DEV bool plant_moved(const PlantStepArgs& P, const PlantLds& L, const double* lds, int i)
+{
+    if (P.backup_steps > 0) return reinterpret_cast<const int*>(lds + L.oag)[i] != kPlantAgeHeld;
+    return reinterpret_cast<const int*>(lds + L.ost)[i] == 0 || P.fallback_u;
+}
+
+// phase 3 (behind the second barrier): e_r = x+_r - pred_r per (instance, row), into the image; the model's prediction has no w
+COPRA_DEV void plant_estimate(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
+{
+    const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantEstLds E = plant_est_lds(P, P.backup_steps > 0);
+    const PlantLds& L = E.base;
+    for (int e = tid; e < cnt * nx; e += T) {
+        const int i = e / nx, r = e - i * nx;
+        double err = 0.0; // held: nothing was applied, nothing is learnt
+        if (plant_moved(P, L, lds, i))
+            err = lds[E.oxn + e]
+                - plant_row(nx, nu, r, lds + E.oAm + i * nx * nx, lds + E.oBm + i * nx * nu, lds + E.odh + i * nx, nullptr, lds + L.ox + i * nx, lds + L.ou + i * nu);
+        lds[E.oe + e] = err;
+    }
+}
+
+// ... and behind a third barrier (the dense gain reads every row's e of its instance): dhat+ and its copy, one contiguous range per group
+COPRA_DEV void plant_estimate_store(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
+{
+    const int nx = P.nx, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantEstLds E = plant_est_lds(P, P.backup_steps > 0);
+    for (int e = tid; e < cnt * nx; e += T) {
+        const int i = e / nx, r = e - i * nx;
+        double dn = lds[E.odh + e]; // held: bit for bit
+        if (plant_moved(P, E.base, lds, i)) {
+            if (P.gain_dense) {
+                const double* G = lds + E.oG + (P.gain_shared ? 0 : i * nx * nx);
+                for (int j = 0; j < nx; ++j) dn += G[r + nx * j] * lds[E.oe + i * nx + j];
+            } else {
+                dn += lds[E.oG + (P.gain_shared ? r : e)] * lds[E.oe + e];
+            }
+        }
+        const size_t o = (size_t)b0 * nx + e;
+        P.dhat[o] = dn;
+        if (P.d_out) P.d_out[o] = dn;
+    }
+}
+
 #if defined(__HIPCC__)
 constexpr int kPlantThreads = 256;
+template <bool kEst>
 __global__ __launch_bounds__(kPlantThreads) void copra_plant_step_kernel(const PlantStepArgs P)
 {
     extern __shared__ __align__(16) double plant_image[];
-    plant_stage(P, (int)blockIdx.x, (int)threadIdx.x, kPlantThreads, plant_image);
+    const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (!kEst) {
+        plant_stage(P, wg, tid, kPlantThreads, plant_image);
+        __syncthreads();
+        plant_apply(P, wg, tid, kPlantThreads, plant_image);
+        return;
+    }
+    plant_stage_est(P, wg, tid, kPlantThreads, plant_image);
     __syncthreads();
-    plant_apply(P, (int)blockIdx.x, (int)threadIdx.x, kPlantThreads, plant_image);
+    plant_apply_est(P, wg, tid, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_estimate(P, wg, tid, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_estimate_store(P, wg, tid, kPlantThreads, plant_image);
 }
 #endif
 

@@ -417,6 +417,56 @@ copra_status_t copra_batch_get_x0(copra_batch_t* h, double* x0);
 #define COPRA_PLAN_HELD (-2) /* age_out: the state was kept */
 copra_status_t copra_batch_set_backup_steps(copra_batch_t* h, int steps);
 
+/* ---- disturbance estimator: an offset-free tick (ABI 11).  The tick has taken a plant that differs from the model since ABI 7, but every
+ *      solve predicted with the d the caller set once: under a constant load or a mismatched plant every instance settles away from its
+ *      goal.  The reference leaves the correction to its caller, who changes the bias of the PreviewSystem between solves
+ *      (src/PreviewSystem.cpp:16-55).  Here the tick learns the difference itself, per instance, with the full state measured.  For
+ *      instance b, after the new state is formed, with dhat the d the controller's model holds for b and Am, Bm that model's A, B:
+ *        x+      = what the tick stores as the next state (plant, applied control, w)                          -- unchanged
+ *        pred_r  = dhat_r + sum_j Am[r,j] x_j + sum_c Bm[r,c] u_c        -- the controller's MODEL, no w; u = the control the tick applied
+ *        e_r     = x+_r - pred_r
+ *        dhat+_r = dhat_r + sum_j L[r,j] e_j   (dense gain)      |      dhat_r + l_r e_r   (diagonal gain)
+ *      dhat+ is the d the next copra_batch_solve reads for that instance.  u is whatever the tick applied: the fresh control, a step of
+ *      the backup plan, or fallback_u.  An instance whose state is HELD (no control applied) keeps dhat bit for bit, as it keeps x.  With
+ *      no plant given (copra_plant_step_t::A == NULL) the plant is the model with its current dhat, so e = w up to rounding: defined
+ *      behaviour, not an error.  With L = I and plant = model + a constant c, dhat = d + c after one tick, up to rounding, and the loop is
+ *      the nominal loop from then on.  Nothing is clamped and nothing is forgotten.
+ *      copra_batch_set_bias_estimator(h, gain, dense, per_instance, on_device): gain is [per_instance ? batch : 1][nx] with dense == 0 and
+ *      [per_instance ? batch : 1][nx x nx], column-major, with dense != 0.  A host gain is copied (the call synchronises the stream of the
+ *      last solve / tick once); with on_device != 0 it is used in place and must stay valid.  Turning the estimator on, the library takes
+ *      a buffer of its OWN, [batch][nx], seeds it with a stream-ordered copy of the d in force and makes it the controller's d: a device
+ *      buffer the caller gave to copra_batch_set_system / copra_batch_set_system_rowmajor_async is read for that copy and never written,
+ *      and neither is the library's copy of a host d.  A call while the estimator is on replaces the gain and keeps the estimates.
+ *      gain == NULL ends the estimator; the last estimates stay the model's d, as a schedule's last window stays.
+ *      copra_batch_set_system / copra_batch_set_system_rowmajor_async while the estimator is on keep it on: the estimates restart from the
+ *      new d, which is copied, not adopted.  copra_batch_set_shared_system ENDS the estimator: one d for the batch cannot hold
+ *      per-instance estimates.  A fleet that shares one model and wants estimates writes the model out with copra_batch_set_system.
+ *      copra_batch_set_bias(h, d, on_device): d [batch][nx] replaces the estimates -- a new episode (stream-ordered with on_device != 0).
+ *      copra_batch_bias_device: the buffer the next solve reads as d (the library's while the estimates are in force).
+ *      copra_batch_get_bias waits for the last tick and copies [batch][nx] to the host.
+ *      The tick hands the estimates out through copra_plant_step_ex_t: copra_plant_step_t with two fields appended behind it, in memory
+ *      exactly the struct of ABI 10 grown at its end (append-only, as ever) -- under a name of its own, so that copra_plant_step_t and
+ *      copra_plant_step_init keep the size every caller compiled against ABI 10 has.  copra_plant_step_ex_init zeroes it and sets
+ *      step.struct_size = sizeof(copra_plant_step_ex_t); copra_batch_advance / copra_batch_rollout take a pointer to it as the pointer to its
+ *      first member (&ex.step), and struct_size tells them which of the two they were given.
+ *      d_out, optional [batch][nx]: dhat+ of the tick (dhat of a held instance); ignored while the estimator is off.
+ *      d_hist, copra_batch_rollout only: [ticks][batch][nx], tick t's d_out.  The tick neither synchronises nor allocates.
+ *      COPRA_ERR_ARG: a NULL handle, copra_batch_set_bias / copra_batch_get_bias with a NULL d.  COPRA_ERR_RUNTIME: no system has been set
+ *      yet; copra_batch_set_bias while the library's estimates are not the d in force (the estimator was never on, or a system was set
+ *      after it ended).  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller; a handle whose model came from
+ *      copra_batch_set_shared_system, whether or not the library wrote it out per instance; an instance whose model, plant and gain do
+ *      not fit the LDS. ---- */
+typedef struct {
+    copra_plant_step_t step; /* first: its struct_size is sizeof(copra_plant_step_ex_t) */
+    double* d_out; /* optional [batch][nx], device: the disturbance estimates after the tick; ignored while the estimator is off */
+    double* d_hist; /* copra_batch_rollout only: [ticks][batch][nx], device; tick t's d_out */
+} copra_plant_step_ex_t;
+void copra_plant_step_ex_init(copra_plant_step_ex_t* step);
+copra_status_t copra_batch_set_bias_estimator(copra_batch_t* h, const double* gain, int dense, int per_instance, int on_device);
+copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_device);
+const double* copra_batch_bias_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_bias(copra_batch_t* h, double* d);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
