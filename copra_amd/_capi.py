@@ -69,6 +69,12 @@ class PlantStepEx(C.Structure):
     _fields_ = PlantStep._fields_ + [("d_out", C.c_void_p), ("d_hist", C.c_void_p)]
 
 
+class PlantStepObs(C.Structure):
+    """copra_plant_step_obs_t: copra_plant_step_ex_t grown at its end by the observer's inputs and outputs, written flat like PlantStepEx"""
+    _fields_ = PlantStepEx._fields_ + [("v", C.c_void_p), ("y_meas", C.c_void_p), ("y_out", C.c_void_p), ("xhat_out", C.c_void_p),
+                                       ("v_seq", C.c_void_p), ("y_hist", C.c_void_p), ("xhat_hist", C.c_void_p)]
+
+
 PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
@@ -366,7 +372,7 @@ def lib():
         L.copra_batch_advance.restype = C.c_int
         L.copra_plant_step_ex_init.restype = None
         L.copra_plant_step_ex_init.argtypes = [C.POINTER(PlantStepEx)]
-        L.copra_batch_advance.argtypes = [vp, vp, vp]  # (a PlantStep or a PlantStepEx by reference: struct_size says which)
+        L.copra_batch_advance.argtypes = [vp, vp, vp]  # (a PlantStep, PlantStepEx or PlantStepObs by reference: struct_size says which)
         L.copra_batch_rollout.restype = C.c_int
         L.copra_batch_rollout.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.copra_batch_set_backup_steps.restype = C.c_int
@@ -379,6 +385,16 @@ def lib():
         L.copra_batch_bias_device.argtypes = [vp]
         L.copra_batch_get_bias.restype = C.c_int
         L.copra_batch_get_bias.argtypes = [vp, vp]
+        L.copra_plant_step_obs_init.restype = None
+        L.copra_plant_step_obs_init.argtypes = [C.POINTER(PlantStepObs)]
+        L.copra_batch_set_observer.restype = C.c_int
+        L.copra_batch_set_observer.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int]
+        L.copra_batch_set_plant_state.restype = C.c_int
+        L.copra_batch_set_plant_state.argtypes = [vp, vp, C.c_int]
+        L.copra_batch_plant_state_device.restype = vp
+        L.copra_batch_plant_state_device.argtypes = [vp]
+        L.copra_batch_get_plant_state.restype = C.c_int
+        L.copra_batch_get_plant_state.argtypes = [vp, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -43,6 +43,7 @@ class BatchLMPC:
         self._w_keep = {}  # ... and as per-instance cost weights
         self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
         self._bias_keep = None  # ... and as the disturbance estimator's gain (set_bias_estimator)
+        self._obs_keep, self._ny = None, 0  # ... and as the observer's C and gains (set_observer); its number of outputs, 0: off
         self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
@@ -168,6 +169,7 @@ class BatchLMPC:
         Bc = np.ascontiguousarray(np.asarray(B, dtype=np.float64).T)
         dc = np.ascontiguousarray(d, dtype=np.float64)
         _capi.check(self._lib.copra_batch_set_shared_system(self._h, Ac.ctypes.data, Bc.ctypes.data, dc.ctypes.data, 0))
+        self._obs_keep, self._ny = None, 0  # (the library ends the observer)
 
     def set_cost_reference(self, cost_index, p):
         """per-instance reference of cost `cost_index`: p of shape (batch, rows) (numpy, or a torch CUDA tensor used in
@@ -472,9 +474,79 @@ class BatchLMPC:
         """device pointer of the d the next solve reads (copra_batch_bias_device)"""
         return int(self._lib.copra_batch_bias_device(self._h) or 0)
 
-    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None):
-        st = _capi.PlantStepEx()
-        self._lib.copra_plant_step_ex_init(C.byref(st))
+    def set_observer(self, C_out, Lx=None, Ld=None):
+        """The state observer of the tick (copra_batch_set_observer): output feedback.  From now on the plant keeps a state of its own
+        (plant_state(), seeded with the x0 in force) and the controller's x0 is the estimate: after every advance()
+          y = C xp+ (+ noise) | y_meas;   xpred = A xhat + B u + d;   xhat+ = xpred + Lx (y - C xpred);   d+ = d + Ld (y - C xpred)
+        C_out of shape (ny, nx), Lx and Ld of shape (nx, ny) in natural indexing, or (batch, ny, nx) / (batch, nx, ny): one per instance
+        (with one of them per instance, numpy matrices given once are written out per instance; tensors all the same way).  numpy: transposed to the ABI's column-major and copied; torch CUDA float64 tensors: in ABI layout already
+        ((.., nx, ny) for C_out, (.., ny, nx) for the gains), used in place and kept alive.  Ld None: a state observer only, d is not touched.
+        With Ld the estimates of d live in the library's buffer (bias(), bias_ptr(), set_bias()).  A call while on replaces C and the gains
+        and keeps every state; C_out None ends the observer.  Excludes set_bias_estimator; set_shared_system ends it."""
+        if C_out is None:
+            _capi.check(self._lib.copra_batch_set_observer(self._h, 0, None, None, None, 0, 0))
+            self._obs_keep, self._ny = None, 0
+            return
+        if Lx is None:
+            raise ValueError("set_observer: C needs a gain Lx")
+        b, nx = self.batch, self.nx
+        given = [m for m in (C_out, Lx, Ld) if m is not None]
+        torch_in = _is_torch(given[0])
+        if any(_is_torch(m) != torch_in for m in given):
+            raise ValueError("set_observer: C, Lx and Ld are all numpy or all torch CUDA tensors")
+        if torch_in:
+            for m in given:
+                if not (m.is_cuda and m.is_contiguous() and str(m.dtype) == "torch.float64"):
+                    raise ValueError("set_observer: contiguous CUDA float64 tensors are needed")
+            shapes = [tuple(m.shape) for m in given]
+            shapes[0] = shapes[0][:-2] + (shapes[0][-1], shapes[0][-2])  # (ABI layout: C arrives as (.., nx, ny))
+            shapes[1:] = [sh[:-2] + (sh[-1], sh[-2]) for sh in shapes[1:]]
+        else:
+            given = [np.asarray(m, dtype=np.float64) for m in given]
+            if any(m.ndim == 3 for m in given):  # (one flag covers all three: a matrix given once is written out per instance)
+                given = [np.broadcast_to(m, (b,) + m.shape) if m.ndim == 2 else m for m in given]
+            shapes = [tuple(m.shape) for m in given]
+        ny = shapes[0][-2] if len(shapes[0]) >= 2 else 0
+        per = len(shapes[0]) == 3
+        lead = (b,) if per else ()
+        want = [lead + (ny, nx)] + [lead + (nx, ny)] * (len(given) - 1)
+        if ny < 1 or shapes != want:
+            raise _capi.CopraDomainError("set_observer: expected C %s and gains %s (or one of each per instance), got %s" % ((ny, nx), (nx, ny), shapes))
+        if torch_in:
+            ptrs = [m.data_ptr() for m in given]
+        else:
+            given = [np.ascontiguousarray(np.swapaxes(m, -1, -2)) for m in given]
+            ptrs = [m.ctypes.data for m in given]
+        ptrs += [None] * (3 - len(ptrs))
+        _capi.check(self._lib.copra_batch_set_observer(self._h, ny, ptrs[0], ptrs[1], ptrs[2], 1 if per else 0, 1 if torch_in else 0))
+        self._obs_keep, self._ny = (given if torch_in else None), ny
+
+    def set_plant_state(self, x):
+        """the plant's own state while the observer is or was on (copra_batch_set_plant_state): (batch, nx), numpy (copied) or a torch CUDA
+        float64 tensor (copied on the stream of the last tick).  set_x0 sets the estimate; a new episode sets both."""
+        if _is_torch(x):
+            ptr, _ = self._device(x, (self.batch, self.nx), "set_plant_state")
+            _capi.check(self._lib.copra_batch_set_plant_state(self._h, ptr, 1))
+        else:
+            xb = np.ascontiguousarray(x, dtype=np.float64)
+            if xb.shape != (self.batch, self.nx):
+                raise _capi.CopraDomainError("set_plant_state: expected %s, got %s" % ((self.batch, self.nx), xb.shape))
+            _capi.check(self._lib.copra_batch_set_plant_state(self._h, xb.ctypes.data, 0))
+
+    def plant_state(self):
+        """the plant's own state, (batch, nx), as a numpy copy (copra_batch_get_plant_state: waits for the last tick)"""
+        out = np.empty((self.batch, self.nx))
+        _capi.check(self._lib.copra_batch_get_plant_state(self._h, out.ctypes.data))
+        return out
+
+    def plant_state_ptr(self):
+        """device pointer of the plant's own state (copra_batch_plant_state_device); 0 while the observer was never on"""
+        return int(self._lib.copra_batch_plant_state_device(self._h) or 0)
+
+    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None, noise=None,
+                    y_meas=None, y_out=None, xhat_out=None):
+        st = _capi.PlantStepObs()
+        self._lib.copra_plant_step_obs_init(C.byref(st))
         b, nx, nu = self.batch, self.nx, self.nu
         if plant is not None:
             A, B, d = plant
@@ -493,11 +565,18 @@ class BatchLMPC:
         st.status_out, so = self._output(status_out, (b,), "status_out", "int32")
         st.age_out, ao = self._output(age_out, (b,), "age_out", "int32")
         st.d_out, do = self._output(d_out, (b, nx), "d_out")
-        keep.extend([t1, t2, xo, uo, so, ao, do])
-        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao, d_out=do)
+        ny = self._ny  # (the observer's outputs: shapes are known only while it is on)
+        if ny == 0 and any(a is not None and a is not False for a in (noise, y_meas, y_out, xhat_out)):
+            raise ValueError("noise, y_meas, y_out and xhat_out belong to the observer (set_observer)")
+        st.v, t3 = self._device(noise, (b, ny), "noise")
+        st.y_meas, t4 = self._device(y_meas, (b, ny), "y_meas")
+        st.y_out, yo = self._output(y_out, (b, ny), "y_out")
+        st.xhat_out, ho = self._output(xhat_out, (b, nx), "xhat_out")
+        keep.extend([t1, t2, xo, uo, so, ao, do, t3, t4, yo, ho])
+        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao, d_out=do, y_out=yo, xhat_out=ho)
 
     def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None,
-                age_out=None, d_out=None):
+                age_out=None, d_out=None, noise=None, y_meas=None, y_out=None, xhat_out=None):
         """The second half of a tick (copra_batch_advance): apply the first control of the last solve to the plant and make the result the next
         initial state -- x+ = A x0 + B u + d (+ disturbance) where the solve succeeded (or fallback_control (batch, nu) is given); an instance
         whose solve failed keeps its state otherwise.  Asynchronous on `stream`, behind the solve.
@@ -509,29 +588,46 @@ class BatchLMPC:
         a solve status_out is the last solve's and only age_out tells.  Returns dict(x_out, u_out, status_out, age_out) of those tensors
         (None where not asked for).  d_out: (batch, nx), the same way: the disturbance estimates after the tick (set_bias_estimator; not written
         while the estimator is off), returned under "d_out".  The state lives in a buffer of the library afterwards (state(), state_ptr()): a tensor given to set_x0
-        is not written."""
+        is not written.
+        With the observer on (set_observer): x_out is the plant's own state; noise (batch, ny) is added to the outputs; y_out (batch, ny) and
+        xhat_out (batch, nx) receive the outputs and the new estimates.  y_meas (batch, ny): the measurement of a REAL plant after it applied
+        the control -- no plant is simulated, plant_state() is left alone, x_out is not written, plant / disturbance / noise are ignored."""
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out)
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out, noise, y_meas,
+                                    y_out, xhat_out)
         _capi.check(self._lib.copra_batch_advance(self._h, C.byref(st), C.c_void_p(stream or 0)))
         self._tick_keep = keep
         return outs
 
     def rollout(self, ticks, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None,
                 disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None, age_out=None, age_hist=None, solve_every=1,
-                d_out=None, d_hist=None):
+                d_out=None, d_hist=None, noise=None, y_out=None, xhat_out=None, y_hist=None, xhat_hist=None):
         """`ticks` x (solve(), advance(...)) enqueued on `stream` by ONE call (copra_batch_rollout): the closed loop never returns to the host.
         disturbances: (ticks, batch, nx), tick t's replaces `disturbance`; x_hist (ticks + 1, batch, nx) -- [0] is the state the first solve
         read --, u_hist (ticks, batch, nu), status_hist int32 (ticks, batch): torch CUDA tensors written in place, or True (allocated here).
         age_hist int32 (ticks, batch): tick t's age_out (see advance).  solve_every = k > 1: a solve at the ticks t with t % k == 0 only, the
         ticks in between play the backup plan -- needs set_backup_steps(K) with K >= k - 1.
         d_hist (ticks, batch, nx): tick t's d_out, the disturbance estimates the solve of tick t + 1 reads (set_bias_estimator).
-        Returns dict(x_hist, u_hist, status_hist, age_hist, d_hist, x_out, u_out, status_out, age_out, d_out)."""
+        With the observer on (set_observer): x_hist is the plant's own state ([0]: before the first tick); noise (batch, ny), or
+        (ticks, batch, ny): tick t's; y_hist (ticks, batch, ny): tick t's outputs; xhat_hist (ticks, batch, nx): the estimate the solve of
+        tick t + 1 reads.
+        Returns dict(x_hist, u_hist, status_hist, age_hist, d_hist, y_hist, xhat_hist, x_out, u_out, status_out, age_out, d_out, y_out,
+        xhat_out)."""
         ticks = int(ticks)
         if ticks < 0:
             raise ValueError("rollout: ticks < 0")
         keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out)
+        ny = self._ny
+        noise_seq = noise is not None and len(getattr(noise, "shape", ())) == 3
+        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out,
+                                    None if noise_seq else noise, None, y_out, xhat_out)
         b, nx, nu = self.batch, self.nx, self.nu
+        if ny == 0 and any(a is not None and a is not False for a in (y_hist, xhat_hist)):
+            raise ValueError("y_hist and xhat_hist belong to the observer (set_observer)")
+        st.v_seq, vt = self._device(noise if noise_seq else None, (ticks, b, ny), "noise")
+        st.y_hist, yt = self._output(y_hist, (ticks, b, ny), "y_hist")
+        st.xhat_hist, ht = self._output(xhat_hist, (ticks, b, nx), "xhat_hist")
+        keep.extend([vt, yt, ht])
         wp, wt = self._device(disturbances, (ticks, b, nx), "disturbances")
         xp, xt = self._output(x_hist, (ticks + 1, b, nx), "x_hist")
         up, ut = self._output(u_hist, (ticks, b, nu), "u_hist")
@@ -542,7 +638,7 @@ class BatchLMPC:
         keep.extend([wt, xt, ut, stt, at, dt])
         _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, wp, xp, up, sp, C.c_void_p(stream or 0)))
         self._tick_keep = keep
-        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at, d_hist=dt)
+        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at, d_hist=dt, y_hist=yt, xhat_hist=ht)
 
     def state(self):
         """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""

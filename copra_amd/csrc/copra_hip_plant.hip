@@ -6,6 +6,8 @@
 // copra_batch_set_backup_steps: an instance without a fresh solution plays the tail of its last plan (the store: d_plan, d_plan_next).
 // copra_batch_set_bias_estimator / _set_bias / _bias_device / _get_bias: the disturbance estimator -- the plant step moves every instance's d
 // (d_bias, the controller's d while the estimates are in force) by a gain times the model's prediction error, in the same launch.
+// copra_batch_set_observer / _set_plant_state / _plant_state_device / _get_plant_state: output feedback -- the plant keeps a state of its own
+// (d_xp), the controller's x0 is the estimate, which the same launch corrects with the innovation of ny measured outputs.
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
@@ -20,22 +22,24 @@ constexpr size_t kPlantLdsTarget = 24 * 1024; // a group's image: small enough f
 constexpr size_t kPlantLdsMax = 160 * 1024; // one instance's image at most (the CU's LDS)
 constexpr int kPlantGroupMax = 32;
 
-// the caller's struct as THIS library knows it -- the widest form, copra_plant_step_ex_t, whose first member is the struct a caller of ABI 10
-// passes: fields beyond the caller's struct_size keep their defaults (all zero)
-copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_ex_t& out, const char* who)
+// the caller's struct as THIS library knows it -- the widest form, copra_plant_step_obs_t, whose first bytes are the struct a caller of ABI 10
+// (copra_plant_step_t) or ABI 11 (copra_plant_step_ex_t) passes: fields beyond the caller's struct_size keep their defaults (all zero)
+copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_obs_t& wide, const char* who)
 {
-    std::memset(&out, 0, sizeof out);
-    out.step.struct_size = (int)sizeof out;
+    std::memset(&wide, 0, sizeof wide);
+    copra_plant_step_ex_t& out = wide.ex;
+    out.step.struct_size = (int)sizeof wide;
     if (!step) return COPRA_OK;
     if (step->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_plant_step_t::struct_size is not set (copra_plant_step_init)");
-    const size_t known = (size_t)step->struct_size < sizeof out ? (size_t)step->struct_size : sizeof out;
-    std::memcpy(&out, step, known);
-    out.step.struct_size = (int)sizeof out;
+    const size_t known = (size_t)step->struct_size < sizeof wide ? (size_t)step->struct_size : sizeof wide;
+    std::memcpy(&wide, step, known);
+    out.step.struct_size = (int)sizeof wide;
     const int given = (out.step.A != nullptr) + (out.step.B != nullptr) + (out.step.d != nullptr);
     if (given != 0 && given != 3) return fail(COPRA_ERR_ARG, std::string(who) + ": a plant needs all of A, B and d (or none of them: the controller's model)");
     return COPRA_OK;
 }
 static_assert(offsetof(copra_plant_step_ex_t, d_out) == sizeof(copra_plant_step_t), "copra_plant_step_ex_t is copra_plant_step_t grown at its end");
+static_assert(offsetof(copra_plant_step_obs_t, v) == sizeof(copra_plant_step_ex_t), "copra_plant_step_obs_t is copra_plant_step_ex_t grown at its end");
 
 // what can be said before any solve: the handle takes part in closed-loop ticks at all
 copra_status_t check_handle(const copra_batch* h, const char* who)
@@ -153,10 +157,68 @@ size_t bias_image_bytes(int nx, int nu, int dense)
     return (size_t)plant_est_lds(nx, nu, 1, 0, 1, 1, 0, dense, 0).total * sizeof(double);
 }
 
-// one plant step behind the last launched solve; `st` has been through read_step
-copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const double* w, double* x_out, double* u_out, int* status_out, int* age_out,
-    double* d_out, hipStream_t s, const char* who)
+// ... and with the observer: the widest the tick can ask for at this ny (a plant of its own, w, ages, Ld, per-instance gains, v)
+size_t observer_image_bytes(int nx, int nu, int ny)
 {
+    return (size_t)plant_obs_lds(nx, nu, ny, 1, 0, 1, 1, 0, 0, 1, 0, 1).total * sizeof(double);
+}
+
+// what one tick reads and writes beside the step's plant: the step's own pointers, or a rollout's rows of tick t
+struct TickIO {
+    const double* w;
+    double *x_out, *u_out;
+    int *status_out, *age_out;
+    double* d_out;
+    const double *v, *y_meas; // (the observer's, as the three below)
+    double *y_out, *xhat_out;
+};
+
+// the tick with the observer on: P is the tick as filled in by advance() -- its plant, controls, plans and copies
+copra_status_t launch_observer(copra_batch* h, const PlantStepArgs& P, const copra_plant_step_t& st, const TickIO& io, hipStream_t s, const char* who)
+{
+    const FusedPlan& HP = h->hp.plan;
+    if (h->shared || !h->A || !h->B || !h->d || !h->d_xp || (h->obs_Ld && h->d != h->d_bias))
+        return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the observer has lost its model");
+    PlantObsArgs Q {};
+    Q.s = P;
+    Q.ny = h->obs_ny;
+    Q.meas = io.y_meas != nullptr;
+    Q.same_model = Q.meas || st.A == nullptr;
+    Q.gain_shared = !h->obs_per_instance;
+    Q.Am = h->A, Q.Bm = h->B;
+    Q.dhat = h->d;
+    Q.dhat_next = h->obs_Ld ? (double*)h->d_bias : nullptr;
+    Q.xhat = h->x0; // (a caller's device buffer is read this once more, never written)
+    Q.xhat_next = h->own_x0;
+    Q.C = h->obs_C, Q.Lx = h->obs_Lx, Q.Ld = h->obs_Ld;
+    Q.yv = Q.meas ? io.y_meas : io.v;
+    Q.y_out = io.y_out, Q.xhat_out = io.xhat_out, Q.d_out = io.d_out;
+    if (Q.same_model) Q.s.A = h->A, Q.s.B = h->B, Q.s.d = h->d, Q.s.shared = 0;
+    if (Q.meas) { // a real plant: the state of the tick's image is the estimate, nothing of the simulated plant is looked at
+        Q.s.x0 = h->x0, Q.s.x0_next = nullptr, Q.s.x_out = nullptr, Q.s.w = nullptr;
+    } else {
+        Q.s.x0 = h->d_xp, Q.s.x0_next = h->d_xp;
+    }
+    const size_t one = observer_image_bytes(HP.nx, HP.nu, Q.ny);
+    if (one > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's model, plant and observer do not fit the LDS");
+    const int group = plant_group(one);
+    Q.s.group = group;
+    Q.s.vec2 = plant_obs_vec2_ok(Q);
+    const size_t lds_bytes = (size_t)plant_obs_lds(HP.nx, HP.nu, Q.ny, group, Q.s.shared, Q.s.w != nullptr, Q.s.backup_steps > 0, Q.same_model, Q.meas,
+                                 Q.Ld != nullptr, Q.gain_shared, Q.yv != nullptr).total * sizeof(double);
+    if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_plant_observer_kernel, lds_bytes);
+    const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
+    hipLaunchKernelGGL(copra_plant_observer_kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, Q);
+    HIP_TRY(hipGetLastError());
+    return COPRA_OK;
+}
+
+// one plant step behind the last launched solve; `st` has been through read_step
+copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickIO& io, hipStream_t s, const char* who)
+{
+    const double* const w = io.w;
+    double *const x_out = io.x_out, *const u_out = io.u_out, *const d_out = io.d_out;
+    int *const status_out = io.status_out, *const age_out = io.age_out;
     const FusedPlan& HP = h->hp.plan;
     if (!h->ad.solved_once) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no solve has been launched (copra_batch_solve)");
     if (HP.batch == 0) return COPRA_OK;
@@ -217,15 +279,20 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const doubl
                                      : (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0).total;
     const size_t lds_bytes = lds_doubles * sizeof(double);
     void (*const kernel)(const PlantStepArgs) = P.est ? copra_plant_step_kernel<true> : copra_plant_step_kernel<false>;
-    if (lds_bytes > 48 * 1024) LDS_OPT_IN(kernel, lds_bytes);
+    if (lds_bytes > 48 * 1024 && !h->obs_on) LDS_OPT_IN(kernel, lds_bytes);
     if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
         if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
         HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
     }
-    const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
-    HIP_TRY(hipGetLastError());
+    if (h->obs_on) { // the observer: its own build of the kernel, with a group and an image of its own
+        const copra_status_t rc = launch_observer(h, P, st, io, s, who);
+        if (rc != COPRA_OK) return rc;
+    } else {
+        const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, P);
+        HIP_TRY(hipGetLastError());
+    }
     h->x0 = h->own_x0;
     h->plan_fresh = false;
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
@@ -251,15 +318,23 @@ void copra_plant_step_ex_init(copra_plant_step_ex_t* step)
     step->step.struct_size = (int)sizeof *step;
 }
 
+void copra_plant_step_obs_init(copra_plant_step_obs_t* step)
+{
+    if (!step) return;
+    std::memset(step, 0, sizeof *step);
+    step->ex.step.struct_size = (int)sizeof *step;
+}
+
 copra_status_t copra_batch_advance(copra_batch_t* h, const copra_plant_step_t* step, void* hip_stream)
 {
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_advance: null handle");
-    copra_plant_step_ex_t ex;
-    copra_status_t rc = read_step(step, ex, "copra_batch_advance");
-    const copra_plant_step_t& st = ex.step;
+    copra_plant_step_obs_t obs;
+    copra_status_t rc = read_step(step, obs, "copra_batch_advance");
+    const copra_plant_step_t& st = obs.ex.step;
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_advance");
     if (rc != COPRA_OK) return rc;
-    return advance(h, st, st.w, st.x_out, st.u_out, st.status_out, st.age_out, ex.d_out, (hipStream_t)hip_stream, "copra_batch_advance");
+    const TickIO io { st.w, st.x_out, st.u_out, st.status_out, st.age_out, obs.ex.d_out, obs.v, obs.y_meas, obs.y_out, obs.xhat_out };
+    return advance(h, st, io, (hipStream_t)hip_stream, "copra_batch_advance");
 }
 
 copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* step, int ticks, const double* w_seq, double* x_hist, double* u_hist,
@@ -267,11 +342,13 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
 {
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_rollout: null handle");
     if (ticks < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative number of ticks");
-    copra_plant_step_ex_t ex;
-    copra_status_t rc = read_step(step, ex, "copra_batch_rollout");
+    copra_plant_step_obs_t obs;
+    copra_status_t rc = read_step(step, obs, "copra_batch_rollout");
+    const copra_plant_step_ex_t& ex = obs.ex;
     const copra_plant_step_t& st = ex.step;
     if (rc == COPRA_OK) rc = check_handle(h, "copra_batch_rollout");
     if (rc != COPRA_OK) return rc;
+    if (obs.y_meas) return fail(COPRA_ERR_ARG, "copra_batch_rollout: y_meas is the measurement of a real plant, one tick at a time (copra_batch_advance)");
     const int every = st.solve_every;
     if (every < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative solve_every");
     if (every > 1 && h->backup_steps < every - 1)
@@ -279,18 +356,23 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
     hipStream_t s = (hipStream_t)hip_stream;
     const FusedPlan& HP = h->hp.plan;
     const size_t nd = (size_t)HP.batch * HP.nx, nc = (size_t)HP.batch * HP.nu, nb = (size_t)HP.batch;
-    if (x_hist && nd) { // the state the first solve reads
+    const size_t ny = h->obs_on ? (size_t)HP.batch * h->obs_ny : 0;
+    if (x_hist && nd) { // the state the first solve reads -- with the observer on the plant's own state: the truth
         if (!h->x0) return fail(COPRA_ERR_RUNTIME, "copra_batch_rollout: no initial states set");
-        HIP_TRY(hipMemcpyAsync(x_hist, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
+        const double* const truth = h->obs_on && h->d_xp ? (const double*)h->d_xp : h->x0;
+        if (h->obs_on && s != h->last_stream) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (xp may still be written on the last tick's stream)
+        HIP_TRY(hipMemcpyAsync(x_hist, truth, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     for (int t = 0; t < ticks; ++t) {
         if (every <= 1 || t % every == 0) { // (the ticks in between play the plan)
             rc = copra_batch_solve(h, hip_stream);
             if (rc != COPRA_OK) return rc;
         }
-        rc = advance(h, st, w_seq ? w_seq + (size_t)t * nd : st.w, x_hist ? x_hist + (size_t)(t + 1) * nd : st.x_out, u_hist ? u_hist + (size_t)t * nc : st.u_out,
+        const TickIO io { w_seq ? w_seq + (size_t)t * nd : st.w, x_hist ? x_hist + (size_t)(t + 1) * nd : st.x_out, u_hist ? u_hist + (size_t)t * nc : st.u_out,
             status_hist ? status_hist + (size_t)t * nb : st.status_out, st.age_hist ? st.age_hist + (size_t)t * nb : st.age_out,
-            ex.d_hist ? ex.d_hist + (size_t)t * nd : ex.d_out, s, "copra_batch_rollout");
+            ex.d_hist ? ex.d_hist + (size_t)t * nd : ex.d_out, obs.v_seq ? obs.v_seq + (size_t)t * ny : obs.v, nullptr,
+            obs.y_hist ? obs.y_hist + (size_t)t * ny : obs.y_out, obs.xhat_hist ? obs.xhat_hist + (size_t)t * nd : obs.xhat_out };
+        rc = advance(h, st, io, s, "copra_batch_rollout");
         if (rc != COPRA_OK) return rc;
     }
     return COPRA_OK;
@@ -332,6 +414,7 @@ copra_status_t copra_batch_set_bias_estimator(copra_batch_t* h, const double* ga
         h->bias_gain = nullptr;
         return COPRA_OK;
     }
+    if (h->obs_on) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the observer is on (copra_batch_set_observer): its gain Ld estimates d");
     if (h->shared || h->shared_as_batch)
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one model for the batch (copra_batch_set_shared_system) has one d; write the model out with copra_batch_set_system");
     if (!h->A || !h->B || !h->d) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no preview system set (copra_batch_set_system)");
@@ -377,6 +460,99 @@ copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_de
         HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a tick that still writes the estimates)
         HIP_TRY(hipMemcpy(h->d_bias, d, bytes, hipMemcpyHostToDevice));
     }
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* C, const double* Lx, const double* Ld, int per_instance, int on_device)
+{
+    const char* const who = "copra_batch_set_observer";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    if (!C) { // the observer ends; x0 and d stay as the last tick left them
+        h->obs_on = false;
+        h->obs_C = h->obs_Lx = h->obs_Ld = nullptr;
+        return COPRA_OK;
+    }
+    if (ny < 1) return fail(COPRA_ERR_ARG, std::string(who) + ": ny < 1");
+    if (!Lx) return fail(COPRA_ERR_ARG, std::string(who) + ": C needs a gain Lx");
+    if (h->shared || h->shared_as_batch)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one model for the batch (copra_batch_set_shared_system); write the model out with copra_batch_set_system");
+    if (!h->A || !h->B || !h->d) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no preview system set (copra_batch_set_system)");
+    if (!h->x0) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no initial states set");
+    if (h->bias_on) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the disturbance estimator is on (copra_batch_set_bias_estimator): end it first, Ld takes its place");
+    const FusedPlan& P = h->hp.plan;
+    if ((double)ny * P.nx > 1e6 || observer_image_bytes(P.nx, P.nu, ny) > kPlantLdsMax)
+        return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's model, plant and observer do not fit the LDS");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), nd = (size_t)P.batch * P.nx;
+    const bool was_on = h->obs_on;
+    if (!on_device) { // the library's copies: a tick that still reads the old ones first
+        const size_t count = (per_instance ? b : 1) * (size_t)P.nx * ny;
+        HIP_TRY(hipStreamSynchronize(h->last_stream));
+        copra_status_t err = COPRA_OK;
+        const auto own = [&](Dev<double>& buf, const double*& src) {
+            if (!src || err != COPRA_OK) return;
+            if (buf.count() < count) {
+                h->obs_on = false; // (it may be the copy that goes)
+                if (buf.alloc(count) != 0) {
+                    err = fail(COPRA_ERR_HIP, std::string(who) + ": no device memory for the observer's matrices");
+                    return;
+                }
+            }
+            if (hipMemcpy(buf, src, count * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+                err = fail(COPRA_ERR_HIP, std::string(who) + ": copying the observer's matrices failed");
+                return;
+            }
+            src = buf;
+        };
+        own(h->own_obs_C, C), own(h->own_obs_Lx, Lx), own(h->own_obs_Ld, Ld);
+        if (err != COPRA_OK) return err;
+    }
+    if (Ld) { // the estimates of d: the buffer and the seed of copra_batch_set_bias_estimator
+        if (!h->d_bias) OWN_TRY(h->d_bias.alloc(b * (size_t)P.nx));
+        if (h->d != h->d_bias) {
+            if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
+            h->d = h->d_bias;
+        }
+    }
+    if (!was_on) { // turned on: the plant starts from the x0 in force, behind the last solve / tick
+        if (!h->d_xp) OWN_TRY(h->d_xp.alloc(b * (size_t)P.nx));
+        if (nd) HIP_TRY(hipMemcpyAsync(h->d_xp, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
+    }
+    h->obs_ny = ny, h->obs_per_instance = per_instance != 0;
+    h->obs_C = C, h->obs_Lx = Lx, h->obs_Ld = Ld;
+    h->obs_on = true;
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_set_plant_state(copra_batch_t* h, const double* x, int on_device)
+{
+    const char* const who = "copra_batch_set_plant_state";
+    if (!h || !x) return fail(COPRA_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->d_xp) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the plant has no state of its own: the observer was never on (copra_batch_set_observer)");
+    const size_t bytes = (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double);
+    if (!bytes) return COPRA_OK;
+    if (on_device) {
+        HIP_TRY(hipMemcpyAsync(h->d_xp, x, bytes, hipMemcpyDeviceToDevice, h->last_stream));
+    } else {
+        HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a tick that still writes the state)
+        HIP_TRY(hipMemcpy(h->d_xp, x, bytes, hipMemcpyHostToDevice));
+    }
+    return COPRA_OK;
+}
+
+const double* copra_batch_plant_state_device(const copra_batch_t* h)
+{
+    return h ? (const double*)h->d_xp : nullptr;
+}
+
+copra_status_t copra_batch_get_plant_state(copra_batch_t* h, double* x)
+{
+    const char* const who = "copra_batch_get_plant_state";
+    if (!h || !x) return fail(COPRA_ERR_ARG, std::string(who) + ": null argument");
+    if (!h->d_xp) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the plant has no state of its own: the observer was never on (copra_batch_set_observer)");
+    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    HIP_TRY(hipMemcpy(x, h->d_xp, (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double), hipMemcpyDeviceToHost));
     return COPRA_OK;
 }
 

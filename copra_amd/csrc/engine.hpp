@@ -202,6 +202,12 @@ struct copra_batch {
     const double* bias_gain = nullptr; // device: the caller's, or own_bias_gain
     Dev<double> own_bias_gain; // the library's copy of a host gain
     Dev<double> d_bias; // [batch][nx]: the estimates; the controller's d (h->d) from the moment the estimator is turned on -- never own_d
+    // state observer of the tick (copra_batch_set_observer; copra_hip_plant.hip, plant_step.hpp): x0 is the estimate while it is on
+    bool obs_on = false;
+    int obs_ny = 0, obs_per_instance = 0;
+    const double *obs_C = nullptr, *obs_Lx = nullptr, *obs_Ld = nullptr; // device: the caller's, or the copies below; obs_Ld null: d is not estimated
+    Dev<double> own_obs_C, own_obs_Lx, own_obs_Ld; // the library's copies of host arrays
+    Dev<double> d_xp; // [batch][nx]: the plant's own state, from the first time the observer is turned on
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -283,10 +289,11 @@ inline int live_limit_windows(const copra_batch* h)
 }
 
 // A new system (h->d) while the disturbance estimator is on: the estimates restart from its d -- copied on `s`, behind the last tick, into
-// the library's buffer, which stays the controller's d; the new d itself is only read
+// the library's buffer, which stays the controller's d; the new d itself is only read.  The observer with a gain Ld estimates d the same way
 inline copra_status_t bias_restart(copra_batch* h, hipStream_t s)
 {
-    if (!h->bias_on || !h->d_bias || h->d == h->d_bias) return COPRA_OK;
+    const bool estimates = h->bias_on || (h->obs_on && h->obs_Ld);
+    if (!estimates || !h->d_bias || h->d == h->d_bias) return COPRA_OK;
     const size_t nd = (size_t)h->hp.plan.batch * h->hp.plan.nx;
     if (s != h->last_stream) { // (a tick that still writes the estimates)
         if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));

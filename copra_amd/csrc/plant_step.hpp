@@ -34,6 +34,10 @@
 // workgroup.  Phase 2 leaves x+ in LDS as well.  Phase 3 (plant_estimate, behind the second barrier) forms e per (instance, row) into LDS;
 // the dense gain reads all rows' e of its instance, so the update (plant_estimate_store) stands behind a third barrier and stores dhat and
 // d_out as one contiguous range per group.  dhat is updated in place: every read of it is into LDS in phase 1, one workgroup owns an instance.
+//
+// The state observer (copra_batch_set_observer, PlantObsArgs) is a third build, copra_plant_observer_kernel: the two phases of the tick on the
+// plant's OWN state xp, then the innovation of ny measured outputs and the update of the estimate xhat (the controller's x0) and, optionally,
+// of dhat -- its rule, image and phases stand in front of its code below.  The two builds above do not know of it.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -235,7 +239,7 @@ COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, doubl
 }
 
 // phase 2 (behind a barrier): the new states and the optional copies; with backup plans the tails of the fresh plans and every next[b]
-template <bool kBackup, bool kEst = false>
+template <bool kBackup, bool kEst = false, bool kPlant = true>
 COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, const double* lds, double* xn_lds = nullptr)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
@@ -244,7 +248,7 @@ COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, 
     const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr, kBackup);
     const int* st = reinterpret_cast<const int*>(lds + L.ost);
     const int* ag = reinterpret_cast<const int*>(lds + L.oag); // (read with backup plans only)
-    for (int e = tid; e < cnt * nx; e += T) {
+    for (int e = tid; kPlant && e < cnt * nx; e += T) { // (kPlant = false: the observer fed with measured outputs moves no plant)
         const int i = e / nx, r = e - i * nx, is = P.shared ? 0 : i;
         double xn = lds[L.ox + e]; // held
         if (kBackup ? ag[i] != kPlantAgeHeld : (st[i] == 0 || P.fallback_u))
@@ -356,6 +360,188 @@ COPRA_DEV void plant_estimate_store(const PlantStepArgs& P, int wg, int tid, int
     }
 }
 
+// ---- the state observer (copra_batch_set_observer, ABI 12): output feedback in the same launch, a third build of the kernel ----
+// The plant has a state of its OWN, xp, and the controller's x0 is the estimate xhat.  With C [ny x nx], Lx, Ld [nx x ny] column-major:
+//   xp+ = Ap xp + Bp u + dp (+ w);   y = C xp+ (+ v)  |  y_meas;   xpred = Am xhat + Bm u + dhat;   inn = y - C xpred
+//   xhat+ = xpred + Lx inn;   dhat+ = dhat + Ld inn  (Ld optional);   a held instance keeps xp, xhat, dhat bit for bit, y_out = C xp (+ v)
+// `s` is the tick WITHOUT an estimator whose state is the plant's: s.x0 = s.x0_next = xp, s.A, s.B, s.d the plant -- phase 1 and phase 2 are
+// the bodies above over the image of plant_lds, so u, the ages, the plans and every copy are theirs.  With measured outputs (meas) no plant
+// is simulated: s.x0 IS xhat (staged once, xp is not looked at), s.A, s.B, s.d are the model and phase 2 runs without its plant loop.
+// Behind the image of plant_lds:  [Am | Bm | dhat, with a plant of its own] | [xhat, unless meas] | C | Lx | [Ld] | [v or y_meas] | xp+ |
+// xpred | inn.  Phases, a barrier between two:
+//   1  stage       everything the workgroup reads: xp, xhat and dhat are complete in LDS before the first barrier
+//   2  apply       xp+ (global, x_out, LDS) per (instance, row);  xpred per (instance, row) into LDS -- both read only what phase 1 staged
+//   3  innovate    per (instance, output): y, y_out, inn into LDS (0 for a held instance)
+//   4  update      per (instance, row): xhat+ and dhat+ as contiguous ranges per group, with their copies
+// xp is written in phase 2, xhat and dhat in phase 4: each behind the barrier that follows its last read (phase 1).
+// LDS banks: lanes of phase 3 read C[o + ny j] with consecutive o inside an instance and a stride of ny nx doubles between instances, lanes
+// of phase 4 read Lx[r + nx o] likewise -- the pattern of plant_row over A; the blocks cannot be padded apart without giving up the one
+// contiguous copy per array.  A C or gain shared by the batch is one block staged once: every instance's lanes read the same words (broadcast).
+struct PlantObsArgs {
+    PlantStepArgs s; // est == 0
+    int ny;
+    int meas; // yv is y_meas: no plant
+    int same_model; // no plant of its own (or meas): s.A, s.B ARE the model and s.d IS dhat; Am, Bm are not looked at
+    int gain_shared; // C, Lx, Ld hold one block for the batch
+    const double *Am, *Bm; // the controller's model
+    const double* dhat; // [batch][nx]: the controller's d
+    double* dhat_next; // == dhat with Ld (updated in place), null without
+    const double* xhat; // [batch][nx]: the controller's x0
+    double* xhat_next; // [batch][nx]; may be xhat
+    const double *C, *Lx, *Ld; // Ld may be null
+    const double* yv; // [batch][ny]: v (may be null) or y_meas
+    double *y_out, *xhat_out, *d_out; // optional copies
+};
+
+inline bool plant_obs_vec2_ok(const PlantObsArgs& Q)
+{
+    const auto ok = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    if (!Q.same_model && !(ok(Q.Am) && ok(Q.Bm))) return false;
+    return plant_vec2_ok(Q.s) && ok(Q.dhat) && ok(Q.xhat) && ok(Q.C) && ok(Q.Lx) && ok(Q.Ld) && ok(Q.yv);
+}
+
+struct PlantObsLds {
+    PlantLds base;
+    int oAm, oBm, odh, oxh, oC, oLx, oLd, oyv, oxn, oxp, oin, total;
+};
+COPRA_PLANT_HD PlantObsLds plant_obs_lds(int nx, int nu, int ny, int group, int shared, int has_w, int backup, int same_model, int meas, int has_Ld,
+    int gain_shared, int has_yv)
+{
+    PlantObsLds E;
+    E.base = plant_lds(nx, nu, group, shared, has_w, backup);
+    int o = E.base.total;
+    E.oAm = E.base.oA, E.oBm = E.base.oB, E.odh = E.base.od, E.oxh = E.base.ox;
+    if (!same_model) {
+        E.oAm = o, o += plant_even(group * nx * nx);
+        E.oBm = o, o += plant_even(group * nx * nu);
+        E.odh = o, o += plant_even(group * nx);
+    }
+    if (!meas) E.oxh = o, o += plant_even(group * nx);
+    const int gs = gain_shared ? 1 : group;
+    E.oC = o, o += plant_even(gs * ny * nx);
+    E.oLx = o, o += plant_even(gs * nx * ny);
+    E.oLd = o, o += has_Ld ? plant_even(gs * nx * ny) : 0;
+    E.oyv = o, o += has_yv ? plant_even(group * ny) : 0;
+    E.oxn = o, o += meas ? 0 : plant_even(group * nx);
+    E.oxp = o, o += plant_even(group * nx);
+    E.oin = o, o += plant_even(group * ny);
+    E.total = o;
+    return E;
+}
+COPRA_DEV PlantObsLds plant_obs_lds(const PlantObsArgs& Q)
+{
+    return plant_obs_lds(Q.s.nx, Q.s.nu, Q.ny, Q.s.group, Q.s.shared, Q.s.w != nullptr, Q.s.backup_steps > 0, Q.same_model, Q.meas, Q.Ld != nullptr,
+        Q.gain_shared, Q.yv != nullptr);
+}
+
+// phase 1: the image of the tick, then what the observer reads beside it
+COPRA_DEV void plant_obs_stage(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
+{
+    const PlantStepArgs& P = Q.s;
+    plant_stage(P, wg, tid, T, lds);
+    const int nx = P.nx, nu = P.nu, ny = Q.ny, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantObsLds E = plant_obs_lds(Q);
+    if (!Q.same_model) {
+        plant_copy(lds + E.oAm, Q.Am + (size_t)b0 * nx * nx, cnt * nx * nx, tid, T, P.vec2);
+        plant_copy(lds + E.oBm, Q.Bm + (size_t)b0 * nx * nu, cnt * nx * nu, tid, T, P.vec2);
+        plant_copy(lds + E.odh, Q.dhat + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+    }
+    if (!Q.meas) plant_copy(lds + E.oxh, Q.xhat + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+    const int g1 = ny * nx, gcnt = Q.gain_shared ? 1 : cnt;
+    const size_t g0 = Q.gain_shared ? 0 : (size_t)b0 * g1;
+    plant_copy(lds + E.oC, Q.C + g0, gcnt * g1, tid, T, P.vec2);
+    plant_copy(lds + E.oLx, Q.Lx + g0, gcnt * g1, tid, T, P.vec2);
+    if (Q.Ld) plant_copy(lds + E.oLd, Q.Ld + g0, gcnt * g1, tid, T, P.vec2);
+    if (Q.yv) plant_copy(lds + E.oyv, Q.yv + (size_t)b0 * ny, cnt * ny, tid, T, P.vec2);
+}
+
+// phase 2 (behind a barrier): the plant's new state -- the tick's own phase 2 on xp, which leaves xp+ in the image -- and the model's prediction
+COPRA_DEV void plant_obs_apply(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
+{
+    const PlantStepArgs& P = Q.s;
+    const PlantObsLds E = plant_obs_lds(Q);
+    if (Q.meas) {
+        if (P.backup_steps > 0) plant_apply_body<true, false, false>(P, wg, tid, T, lds);
+        else plant_apply_body<false, false, false>(P, wg, tid, T, lds);
+    } else {
+        if (P.backup_steps > 0) plant_apply_body<true, true>(P, wg, tid, T, lds, lds + E.oxn);
+        else plant_apply_body<false, true>(P, wg, tid, T, lds, lds + E.oxn);
+    }
+    const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    // (the rows are handed out from the LAST thread down: the plant's rows above went to the first threads, so with fewer than T / 2 rows --
+    //  the launch's group at small xDim -- the two sums of a row run on different waves, side by side)
+    for (int e = T - 1 - tid; e < cnt * nx; e += T) {
+        const int i = e / nx, r = e - i * nx;
+        double xp = lds[E.oxh + e]; // held: the estimate itself
+        if (plant_moved(P, E.base, lds, i))
+            xp = plant_row(nx, nu, r, lds + E.oAm + i * nx * nx, lds + E.oBm + i * nx * nu, lds + E.odh + i * nx, nullptr, lds + E.oxh + i * nx, lds + E.base.ou + i * nu);
+        lds[E.oxp + e] = xp;
+    }
+}
+
+// phase 3 (behind the second barrier): y and the innovation per (instance, output)
+COPRA_DEV void plant_obs_innovate(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
+{
+    const PlantStepArgs& P = Q.s;
+    const int nx = P.nx, ny = Q.ny, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantObsLds E = plant_obs_lds(Q);
+    for (int e = tid; e < cnt * ny; e += T) {
+        const int i = e / ny, o = e - i * ny;
+        const double* Cm = lds + E.oC + (Q.gain_shared ? 0 : i * ny * nx);
+        double y;
+        if (Q.meas) {
+            y = lds[E.oyv + e];
+        } else { // (a held instance's xp+ in the image is its unchanged xp)
+            y = Q.yv ? lds[E.oyv + e] : 0.0;
+            for (int j = 0; j < nx; ++j) y += Cm[o + ny * j] * lds[E.oxn + i * nx + j];
+        }
+        double inn = 0.0; // held: nothing was applied, nothing is learnt
+        if (plant_moved(P, E.base, lds, i)) {
+            double cp = 0.0;
+            for (int j = 0; j < nx; ++j) cp += Cm[o + ny * j] * lds[E.oxp + i * nx + j];
+            inn = y - cp;
+        }
+        lds[E.oin + e] = inn;
+        if (Q.y_out) Q.y_out[(size_t)b0 * ny + e] = y;
+    }
+}
+
+// phase 4 (behind the third barrier: a row reads every innovation of its instance): xhat+, dhat+ and their copies
+COPRA_DEV void plant_obs_update(const PlantObsArgs& Q, int wg, int tid, int T, const double* lds)
+{
+    const PlantStepArgs& P = Q.s;
+    const int nx = P.nx, ny = Q.ny, b0 = wg * P.group;
+    const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
+    if (cnt <= 0) return;
+    const PlantObsLds E = plant_obs_lds(Q);
+    for (int e = tid; e < cnt * nx; e += T) {
+        const int i = e / nx, r = e - i * nx;
+        const int g = Q.gain_shared ? 0 : i * nx * ny;
+        double xn = lds[E.oxp + e]; // held: phase 2 left the old estimate here, bit for bit
+        if (plant_moved(P, E.base, lds, i))
+            for (int o = 0; o < ny; ++o) xn += lds[E.oLx + g + r + nx * o] * lds[E.oin + i * ny + o];
+        const size_t at = (size_t)b0 * nx + e;
+        Q.xhat_next[at] = xn;
+        if (Q.xhat_out) Q.xhat_out[at] = xn;
+    }
+    if (!Q.Ld) return;
+    for (int e = T - 1 - tid; e < cnt * nx; e += T) { // (from the last thread down, as in phase 2: beside the rows of xhat+)
+        const int i = e / nx, r = e - i * nx;
+        const int g = Q.gain_shared ? 0 : i * nx * ny;
+        double dn = lds[E.odh + e]; // held: bit for bit
+        if (plant_moved(P, E.base, lds, i))
+            for (int o = 0; o < ny; ++o) dn += lds[E.oLd + g + r + nx * o] * lds[E.oin + i * ny + o];
+        const size_t at = (size_t)b0 * nx + e;
+        Q.dhat_next[at] = dn;
+        if (Q.d_out) Q.d_out[at] = dn;
+    }
+}
+
 #if defined(__HIPCC__)
 constexpr int kPlantThreads = 256;
 template <bool kEst>
@@ -376,6 +562,20 @@ __global__ __launch_bounds__(kPlantThreads) void copra_plant_step_kernel(const P
     plant_estimate(P, wg, tid, kPlantThreads, plant_image);
     __syncthreads();
     plant_estimate_store(P, wg, tid, kPlantThreads, plant_image);
+}
+
+// the third build: the tick with the state observer (its arguments carry the tick's own as their first member)
+__global__ __launch_bounds__(kPlantThreads) void copra_plant_observer_kernel(const PlantObsArgs Q)
+{
+    extern __shared__ __align__(16) double plant_image[];
+    const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
+    plant_obs_stage(Q, wg, tid, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_obs_apply(Q, wg, tid, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_obs_innovate(Q, wg, tid, kPlantThreads, plant_image);
+    __syncthreads();
+    plant_obs_update(Q, wg, tid, kPlantThreads, plant_image);
 }
 #endif
 

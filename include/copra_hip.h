@@ -467,6 +467,63 @@ copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_de
 const double* copra_batch_bias_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_bias(copra_batch_t* h, double* d);
 
+/* ---- output feedback: a state observer in the tick (ABI 12).  Everything above takes the state the plant step writes for the state the
+ *      next solve reads: the full state is measured.  A machine gives y = C x + v with fewer outputs than states, and the reference's loop
+ *      (include/LMPC.h:108, include/PreviewSystem.h:52) leaves the observer between measurement and xInit to its caller.  Here the tick
+ *      runs it, in the same launch.  The plant gets a state of its OWN, xp [batch][nx], a buffer of the library; the controller's x0 becomes
+ *      the ESTIMATE xhat.  For instance b, with dhat the controller's d, Am, Bm the controller's model, Ap, Bp, dp the plant (the step's, or
+ *      the model with d = dhat when the step gives none) and u the control the tick applied -- chosen exactly as above: fresh solution,
+ *      backup plan, fallback_u, or none:
+ *        xp+   = Ap xp + Bp u + dp (+ w)                  the plant moves its OWN state, not xhat
+ *        y     = C xp+ (+ v)                              ny outputs; v optional [batch][ny]; or y = y_meas[b] (below)
+ *        xpred = Am xhat + Bm u + dhat                    the model's prediction, no w  (the `pred` of the disturbance estimator)
+ *        inn   = y - C xpred                              ny innovations
+ *        xhat+ = xpred + Lx inn                           Lx [nx x ny]
+ *        dhat+ = dhat + Ld inn                            Ld [nx x ny], optional
+ *        x0 <- xhat+ ;  d <- dhat+                        the next solve reads both
+ *      An instance to which no control was applied is HELD: xp, xhat and dhat keep their bits, its y_out row is C xp (+ v) of the unchanged
+ *      state.  With C = I, Lx = I, Ld = L and no v this is the disturbance estimator above, up to rounding.  All matrices column-major.
+ *      copra_batch_set_observer(h, ny, C, Lx, Ld, per_instance, on_device): C is [ny x nx], Lx and Ld are [nx x ny], each given once for
+ *      the batch or, with per_instance != 0, [batch] times (one flag for all three).  Host arrays are copied (the call synchronises the
+ *      stream of the last solve / tick once); device arrays are used in place and must stay valid.  Ld == NULL: a state observer only -- d
+ *      is not touched and no buffer is taken for it.  With Ld the library takes its buffer of estimates and seeds it exactly as
+ *      copra_batch_set_bias_estimator does; copra_batch_set_bias, copra_batch_get_bias and copra_batch_bias_device work on it.  Turning the
+ *      observer on seeds xp with a stream-ordered copy of the x0 in force.  A call while the observer is on replaces C and the gains and
+ *      keeps xp, xhat and dhat.  C == NULL ends the observer: x0 and d stay as the last tick left them.
+ *      copra_batch_set_plant_state(h, x, on_device) / copra_batch_plant_state_device / copra_batch_get_plant_state handle the true state
+ *      xp, [batch][nx].  copra_batch_set_x0 keeps its meaning: it sets the controller's x0, which is now the estimate.  A new episode sets
+ *      both.
+ *      copra_plant_step_obs_t is copra_plant_step_ex_t as its first member with the observer's fields appended (append-only; the two
+ *      smaller structs keep their fields and sizes, struct_size tells the three apart; copra_plant_step_obs_init zeroes it and sets
+ *      ex.step.struct_size).  While the observer is on x_out / x_hist are the plant's state xp -- the truth, what they have always held --,
+ *      x_hist[0] is xp before the first tick, xhat_out is xhat+ and xhat_hist[t] the estimate the solve of tick t + 1 reads, y_out / y_hist[t]
+ *      the outputs y, v_seq[t] replaces v.  While the observer is off the new fields are ignored.
+ *      y_meas (copra_batch_advance only): the caller's measurement of a REAL plant after it applied u.  No plant is simulated: xp is neither
+ *      read nor written, x_out is not written, the step's plant, w and v are ignored; everything from xpred on is as above (y_out receives
+ *      y_meas).  copra_batch_rollout with y_meas != NULL returns COPRA_ERR_ARG.
+ *      The observer and the disturbance estimator exclude each other: whichever is asked for second gets COPRA_ERR_RUNTIME.  Backup plans,
+ *      solve_every and all schedules are untouched: they decide u and the windows, not the state.  copra_batch_set_system keeps the observer
+ *      on (with Ld, dhat restarts from the new d, as for the estimator); copra_batch_set_shared_system ends it.
+ *      COPRA_ERR_ARG: a NULL handle, ny < 1 (ny > nx is no error: redundant sensors exist), C without Lx, a NULL x for
+ *      copra_batch_set_plant_state / copra_batch_get_plant_state.  COPRA_ERR_RUNTIME: no system or no x0 set yet; the plant-state calls
+ *      while the observer was never on.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller; a handle whose model came from
+ *      copra_batch_set_shared_system; an instance whose image does not fit the LDS. ---- */
+typedef struct {
+    copra_plant_step_ex_t ex; /* first: ex.step.struct_size is sizeof(copra_plant_step_obs_t) */
+    const double* v; /* optional sensor noise [batch][ny], device */
+    const double* y_meas; /* copra_batch_advance only: measured outputs [batch][ny], device; no plant is simulated */
+    double* y_out; /* optional [batch][ny], device: the outputs the observer read */
+    double* xhat_out; /* optional [batch][nx], device: the estimates after the tick */
+    const double* v_seq; /* copra_batch_rollout only: [ticks][batch][ny], device; tick t's replaces v */
+    double* y_hist; /* copra_batch_rollout only: [ticks][batch][ny], device; tick t's y_out */
+    double* xhat_hist; /* copra_batch_rollout only: [ticks][batch][nx], device; tick t's xhat_out */
+} copra_plant_step_obs_t;
+void copra_plant_step_obs_init(copra_plant_step_obs_t* step);
+copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* C, const double* Lx, const double* Ld, int per_instance, int on_device);
+copra_status_t copra_batch_set_plant_state(copra_batch_t* h, const double* x, int on_device);
+const double* copra_batch_plant_state_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_plant_state(copra_batch_t* h, double* x);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,

@@ -1,0 +1,550 @@
+"""The state observer of the tick (copra_batch_set_observer, ABI 12) without a GPU: declared, exported, bound -- and the rule itself on the phases
+of the plant-step kernel (copra_amd/csrc/plant_step.hpp), which compile on the host: tests/emu/emu_plant_observer.cpp walks them thread by thread
+over a NaN-filled image, this file compiles that harness itself.
+
+The expectation is a numpy.longdouble restatement of the rule in include/copra_hip.h (reference_observer).  xp+ is compared with reference_step
+within step_bound, both of tests/test_closed_loop_abi.py.  The other bounds are derived the way bias_bound is (tests/test_bias_estimator_abi.py):
+every rounding of a partial sum is at most u = 2^-53 times the sum of the absolute values of its terms, a chain of n products and n additions is
+counted as 2 (n + 1) roundings, as step_bound counts its own, and an error already present in an operand passes through the absolute values of
+the matrix that multiplies it.  With |M| v the product of absolute values:
+
+  xp+ as computed differs from the exact xp+ of the same inputs by at most    Ex = step_bound(nx, nu, Sx),  Sx = |dp| + |Ap||xp| + |Bp||u| + |w|
+  y = v + C xp+ (nx products on top of v):                                    Sy = |v| + |C| Sx,            Ey = |C| Ex + 2 (nx + 1) u Sy
+      (y = y_meas is a copy: Sy = |y_meas|, Ey = 0; so is the y_out of a held instance when C xp (+ v) has one term per row -- in general it is
+      within Ey of C xp + v with Ex = 0)
+  xpred has the chain of xp+ without w:                                       Ep = step_bound(nx, nu, Sp),  Sp = |dhat| + |Am||xhat| + |Bm||u|
+  C xpred, nx products:                                                       Sc = |C| Sp,                  Ec = |C| Ep + 2 (nx + 1) u Sc
+  inn = fl(y - C xpred), one more rounding of a difference of size <= Si:     Si = Sy + Sc,                 Ei = Ey + Ec + u Si
+  xhat+ = xpred + Lx inn, ny products on top of xpred:                        Eh = Ep + |Lx| Ei + 2 (ny + 1) u (Sp + |Lx| Si)
+  dhat+ = dhat + Ld inn, likewise:                                            Ed = |Ld| Ei + 2 (ny + 1) u (|dhat| + |Ld| Si)
+Nothing in it is fitted to what the kernel gives.  u_out, ages, held states and estimates, and the copies x_out, xhat_out, d_out are compared bit
+for bit.  The figures the comparisons print are max error / bound."""
+import ctypes
+import itertools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_backup_plan_abi import BATCH, FRESH, _rule, _same_bits, _script
+from test_bias_estimator_abi import reference_bias
+from test_closed_loop_abi import reference_step, step_bound
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, "tests", "emu")
+FALLBACK, HELD = -1, -2
+NEW = ("copra_batch_set_observer", "copra_batch_set_plant_state", "copra_batch_plant_state_device", "copra_batch_get_plant_state")
+FIELDS = ["ex", "v", "y_meas", "y_out", "xhat_out", "v_seq", "y_hist", "xhat_hist"]
+LD = np.longdouble
+U = 2.0 ** -53
+SHAPES = [(6, 3, 3), (9, 3, 3), (2, 1, 1), (3, 3, 3), (2, 1, 3)]  # (nx, nu, ny): the issue's five cases
+LDS_TARGET, GROUP_MAX = 24 * 1024, 32  # kPlantLdsTarget, kPlantGroupMax of copra_hip_plant.hip
+
+
+def _lib():
+    from copra_amd import _capi
+    if not os.path.exists(_capi.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return ctypes.CDLL(_capi.LIB_PATH)
+
+
+# ---- the rule, restated ----
+def _each(v, batch, ndim):
+    v = np.asarray(v, dtype=LD)
+    return np.broadcast_to(v, (batch,) + v.shape) if v.ndim == ndim else v
+
+
+def _mv(M, x):
+    return (M * x[:, None, :]).sum(axis=2)
+
+
+def reference_observer(Am, Bm, dhat, xhat, u, C, Lx, Ld=None, xplus=None, Sx=None, v=None, y_meas=None):
+    """The rule of include/copra_hip.h in numpy.longdouble with the bounds derived above.  Natural indexing: Am (b, nx, nx), Bm (b, nx, nu),
+    C (ny, nx) or (b, ny, nx), Lx / Ld (nx, ny) or (b, nx, ny).  Either xplus, Sx (the exact next plant state of the same inputs and its scale:
+    reference_step) and the optional noise v, or y_meas.  Returns dict(y, Ey, xpred, xhat, Eh, dhat, Ed); rows of instances that were held are
+    meaningless: the caller masks them."""
+    Am, Bm, dhat, xhat, u = (np.asarray(a, dtype=LD) for a in (Am, Bm, dhat, xhat, u))
+    b, nx = xhat.shape
+    nu = u.shape[1]
+    C, Lx = _each(C, b, 2), _each(Lx, b, 2)
+    ny = C.shape[1]
+    aC = np.abs(C)
+    if y_meas is not None:
+        y = np.asarray(y_meas, dtype=LD)
+        Sy, Ey = np.abs(y), np.zeros_like(y)
+    else:
+        vv = np.zeros((b, ny), dtype=LD) if v is None else np.asarray(v, dtype=LD)
+        y = vv + _mv(C, np.asarray(xplus, dtype=LD))
+        Sy = np.abs(vv) + _mv(aC, np.asarray(Sx, dtype=LD))
+        Ey = _mv(aC, step_bound(nx, nu, np.asarray(Sx, dtype=LD))) + 2 * (nx + 1) * U * Sy
+    xpred = dhat + _mv(Am, xhat) + _mv(Bm, u)
+    Sp = np.abs(dhat) + _mv(np.abs(Am), np.abs(xhat)) + _mv(np.abs(Bm), np.abs(u))
+    Ep = step_bound(nx, nu, Sp)
+    Sc = _mv(aC, Sp)
+    Ec = _mv(aC, Ep) + 2 * (nx + 1) * U * Sc
+    inn = y - _mv(C, xpred)
+    Si = Sy + Sc
+    Ei = Ey + Ec + U * Si
+    aL = np.abs(Lx)
+    out = dict(y=y, Ey=Ey, xpred=xpred, inn=inn, xhat=xpred + _mv(Lx, inn), Eh=Ep + _mv(aL, Ei) + 2 * (ny + 1) * U * (Sp + _mv(aL, Si)), dhat=dhat, Ed=None)
+    if Ld is not None:
+        Ld = _each(Ld, b, 2)
+        aD = np.abs(Ld)
+        out["dhat"] = dhat + _mv(Ld, inn)
+        out["Ed"] = _mv(aD, Ei) + 2 * (ny + 1) * U * (np.abs(dhat) + _mv(aD, Si))
+    return out
+
+
+def held_output(C, xp, v):
+    """y_out of a held instance: C xp (+ v) of the unchanged state, and its bound (Ey with Ex = 0)"""
+    xp = np.asarray(xp, dtype=LD)
+    b, nx = xp.shape
+    C = _each(C, b, 2)
+    vv = np.zeros((b, C.shape[1]), dtype=LD) if v is None else np.asarray(v, dtype=LD)
+    return vv + _mv(C, xp), 2 * (nx + 1) * U * (np.abs(vv) + _mv(np.abs(C), np.abs(xp)))
+
+
+def abi(m):
+    """natural indexing -> the ABI's column-major blocks"""
+    return np.ascontiguousarray(np.swapaxes(np.asarray(m, dtype=np.float64), -1, -2))
+
+
+# ---- surface ----
+def test_header_declares_the_observer():
+    text = open(os.path.join(ROOT, "include", "copra_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, code), name
+    assert re.search(r"\bcopra_plant_step_obs_init\s*\(\s*copra_plant_step_obs_t\s*\*", code)
+    end = code.index("} copra_plant_step_obs_t;")
+    body = code[code.rindex("typedef struct {", 0, end):end]
+    assert re.findall(r"(\w+)\s*;", body) == FIELDS  # exactly `ex` and the new fields, in order
+    assert re.search(r"copra_plant_step_ex_t\s+ex\s*;", body)
+    for name in ("v", "y_meas", "v_seq"):
+        assert re.search(r"const\s+double\s*\*\s*%s\s*;" % name, body), name
+    for name in ("y_out", "xhat_out", "y_hist", "xhat_hist"):
+        assert re.search(r"(?<!const )double\s*\*\s*%s\s*;" % name, body), name
+    assert code.index("} copra_plant_step_ex_t;") < end
+    assert re.search(r"copra_batch_set_observer\s*\(\s*copra_batch_t\s*\*\s*h\s*,\s*int\s+ny\s*,\s*const\s+double\s*\*\s*C\s*,\s*const\s+double\s*\*\s*Lx\s*,"
+                     r"\s*const\s+double\s*\*\s*Ld\s*,\s*int\s+per_instance\s*,\s*int\s+on_device\s*\)", code)
+    assert "include/LMPC.h:108" in text and "include/PreviewSystem.h:52" in text and "xhat+ = xpred + Lx inn" in text
+
+
+def test_library_exports_the_observer_with_abi_12():
+    lib = _lib()
+    for name in NEW + ("copra_plant_step_obs_init",):
+        assert hasattr(lib, name), name
+    lib.copra_abi_version.restype = ctypes.c_int
+    assert lib.copra_abi_version() >= 12
+    from copra_amd import _capi
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.copra_batch_set_observer.restype = ci
+    lib.copra_batch_set_observer.argtypes = [vp, ci, vp, vp, vp, ci, ci]
+    lib.copra_batch_set_plant_state.restype = ci
+    lib.copra_batch_set_plant_state.argtypes = [vp, vp, ci]
+    lib.copra_batch_get_plant_state.restype = ci
+    lib.copra_batch_get_plant_state.argtypes = [vp, vp]
+    lib.copra_batch_plant_state_device.restype = vp
+    lib.copra_batch_plant_state_device.argtypes = [vp]
+    one = np.ones(4)
+    # (a NULL handle is refused before anything touches a device)
+    assert lib.copra_batch_set_observer(None, 1, one.ctypes.data, one.ctypes.data, None, 0, 0) == _capi.COPRA_ERR_ARG
+    assert lib.copra_batch_set_observer(None, 1, None, None, None, 0, 0) == _capi.COPRA_ERR_ARG
+    assert lib.copra_batch_set_plant_state(None, one.ctypes.data, 0) == _capi.COPRA_ERR_ARG
+    assert lib.copra_batch_get_plant_state(None, one.ctypes.data) == _capi.COPRA_ERR_ARG
+    assert not lib.copra_batch_plant_state_device(None)
+
+
+def test_plant_step_obs_init_sets_the_new_size():
+    """the mirror of copra_plant_step_obs_t is the mirror of copra_plant_step_ex_t with the observer's fields last; its init sets the new size
+    and zeroes everything else; the two smaller structs keep their sizes"""
+    from copra_amd import _capi
+    lib = _lib()
+    old = [n for n, _ in _capi.PlantStepEx._fields_]
+    names = [n for n, _ in _capi.PlantStepObs._fields_]
+    assert names == old + FIELDS[1:]
+    assert _capi.PlantStepObs.v.offset == ctypes.sizeof(_capi.PlantStepEx)  # grown at its end: no padding in between
+    for n in old:
+        assert getattr(_capi.PlantStepObs, n).offset == getattr(_capi.PlantStepEx, n).offset, n
+    st = _capi.PlantStepObs()
+    ctypes.memset(ctypes.byref(st), 0xff, ctypes.sizeof(st))
+    lib.copra_plant_step_obs_init.restype = None
+    lib.copra_plant_step_obs_init.argtypes = [ctypes.POINTER(_capi.PlantStepObs)]
+    lib.copra_plant_step_obs_init(ctypes.byref(st))
+    assert st.struct_size == ctypes.sizeof(_capi.PlantStepObs) == ctypes.sizeof(_capi.PlantStepEx) + 7 * ctypes.sizeof(ctypes.c_void_p)
+    assert not any(getattr(st, n) for n in names if n != "struct_size")
+    for cls, init in ((_capi.PlantStep, "copra_plant_step_init"), (_capi.PlantStepEx, "copra_plant_step_ex_init")):
+        small = cls()
+        getattr(lib, init).restype = None
+        getattr(lib, init).argtypes = [ctypes.POINTER(cls)]
+        getattr(lib, init)(ctypes.byref(small))
+        assert small.struct_size == ctypes.sizeof(cls)
+
+
+def test_python_binding_has_the_observer():
+    import inspect
+    from copra_amd import BatchLMPC
+    for name in ("set_observer", "set_plant_state", "plant_state", "plant_state_ptr"):
+        assert callable(getattr(BatchLMPC, name, None)), name
+    assert inspect.signature(BatchLMPC.set_observer).parameters["Ld"].default is None
+    adv = inspect.signature(BatchLMPC.advance).parameters
+    assert all(adv[n].default is None for n in ("noise", "y_meas", "y_out", "xhat_out"))
+    ro = inspect.signature(BatchLMPC.rollout).parameters
+    assert all(ro[n].default is None for n in ("noise", "y_hist", "xhat_hist")) and "y_meas" not in ro
+
+
+# ---- the kernel bodies on the host ----
+VP, CI = ctypes.c_void_p, ctypes.c_int
+
+
+class Tick(ctypes.Structure):
+    """EmuObserverTick of tests/emu/emu_plant_observer.cpp"""
+    _fields_ = ([(n, CI) for n in ("batch", "nx", "nu", "ny", "N", "group", "threads", "shared")]
+                + [(n, VP) for n in ("A", "B", "d", "xp", "w", "fallback_u", "status", "control", "x_out", "u_out", "status_out")]
+                + [("backup_steps", CI), ("fresh", CI), ("plan", VP), ("next", VP), ("age_out", VP), ("gain_shared", CI)]
+                + [(n, VP) for n in ("Am", "Bm", "dhat", "xhat", "xhat_next", "C", "Lx", "Ld", "v", "y_meas", "y_out", "xhat_out", "d_out")]
+                + [("vec2_mode", CI), ("vec2_used", CI)])
+
+
+@pytest.fixture(scope="module")
+def emu(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("emu_plant_observer") / "libemu_plant_observer.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", os.path.join(EMU, "emu_plant_observer.cpp"), "-o", so])
+    lib = ctypes.CDLL(so)
+    lib.emu_plant_observer_step.restype = CI
+    lib.emu_plant_observer_step.argtypes = [ctypes.POINTER(Tick)]
+    lib.emu_plant_observer_lds_doubles.restype = CI
+    lib.emu_plant_observer_lds_doubles.argtypes = [CI] * 12
+    return lib
+
+
+def launch_group(emu, nx, nu, ny):
+    """the group copra_hip_plant.hip launches with: from one instance's widest image at this ny"""
+    one = 8 * emu.emu_plant_observer_lds_doubles(nx, nu, ny, 1, 0, 1, 1, 0, 0, 1, 0, 1)
+    g = min(GROUP_MAX, max(1, LDS_TARGET // one))
+    return g & ~1 if g > 1 else g
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _model(rng, batch, nx, nu, ny, N=5, failed=0):
+    """a controller's model, the plant's state and the estimate, the last solve's results (`failed` instances without a solution), noise, a
+    measurement and a fallback control"""
+    status = np.zeros(batch, dtype=np.int32)
+    bad = rng.choice(batch, failed, replace=False) if failed else np.zeros(0, dtype=int)
+    status[bad] = rng.integers(1, 4, bad.size)
+    control = rng.standard_normal((batch, nu * N))
+    control[bad] = np.nan  # what the engine leaves in a failed instance
+    xp = rng.standard_normal((batch, nx)) * 10.0 ** rng.integers(-2, 2, (batch, 1))
+    return dict(Am=0.5 * rng.standard_normal((batch, nx, nx)), Bm=rng.standard_normal((batch, nx, nu)), dhat=rng.standard_normal((batch, nx)),
+                xp=xp, xhat=xp + 0.1 * rng.standard_normal((batch, nx)), w=0.01 * rng.standard_normal((batch, nx)),
+                v=0.01 * rng.standard_normal((batch, ny)), ym=rng.standard_normal((batch, ny)),
+                status=status, control=control, fb=rng.standard_normal((batch, nu)), N=N)
+
+
+def _gains(rng, batch, nx, ny, per):
+    lead = (batch,) if per else ()
+    return rng.standard_normal(lead + (ny, nx)), rng.uniform(-1.0, 1.0, lead + (nx, ny)), rng.uniform(-0.5, 0.5, lead + (nx, ny))
+
+
+def _plant(rng, c, kind):
+    """'own': a plant per instance, 'shared': one for the batch, 'none': the model with its estimates.  (A, B, d) in natural indexing, or None"""
+    batch, nx = c["xp"].shape
+    nu = c["fb"].shape[1]
+    if kind == "none":
+        return None
+    lead = (batch,) if kind == "own" else ()
+    return 0.5 * rng.standard_normal(lead + (nx, nx)), rng.standard_normal(lead + (nx, nu)), rng.standard_normal(lead + (nx,))
+
+
+GUARD = -3.5
+
+
+def _guarded(a, extra=4):
+    buf = np.full(a.size + extra, GUARD)
+    buf[:a.size] = a.ravel()
+    return buf
+
+
+def _tick(emu, c, plant, gains, with_Ld, with_w, with_v, with_fb, with_y_meas, group, threads=256, vec2_mode=-1, backup=None, misalign=False):
+    """one tick with the observer on, in place; returns dict(xp, xhat, dhat, x_out, u_out, y_out, xhat_out, d_out, s_out, a_out, vec2)"""
+    batch, nx = c["xp"].shape
+    nu, ny = c["fb"].shape[1], c["v"].shape[1]
+    keep = []
+
+    def dev(a):  # (misalign: the array starts 8 bytes into a 16-byte aligned buffer)
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        raw = np.empty(a.size + 3)
+        off = (-(raw.ctypes.data // 8) % 2) + (1 if misalign else 0)
+        view = raw[off:off + a.size]
+        view[:] = a.ravel()
+        assert view.ctypes.data % 16 == (8 if misalign else 0)
+        keep.append(raw)
+        return view
+    Cn, Lxn, Ldn = gains
+    T = Tick()
+    T.batch, T.nx, T.nu, T.ny, T.N, T.group, T.threads = batch, nx, nu, ny, c["N"], group, threads
+    if plant is not None:
+        T.A, T.B, T.d = _ptr(dev(abi(plant[0]))), _ptr(dev(abi(plant[1]))), _ptr(dev(plant[2]))
+        T.shared = int(plant[0].ndim == 2)
+    xp, xhat, dhat = _guarded(c["xp"]), _guarded(c["xhat"]), _guarded(c["dhat"])
+    x_out, xhat_out, d_out = (np.full(batch * nx + 4, GUARD) for _ in range(3))
+    y_out, u_out = np.full(batch * ny + 4, GUARD), np.full((batch, nu), 7.0)
+    s_out, a_out = np.full(batch, -1, dtype=np.int32), np.full(batch, -99, dtype=np.int32)
+    T.xp, T.w, T.fallback_u = _ptr(xp), _ptr(dev(c["w"]) if with_w else None), _ptr(c["fb"] if with_fb else None)
+    T.status, T.control = _ptr(c["status"]), _ptr(c["control"])
+    T.x_out, T.u_out, T.status_out, T.age_out = _ptr(x_out), _ptr(u_out), _ptr(s_out), _ptr(a_out)
+    K, fresh, plan, nxt = backup if backup else (0, 1, None, None)
+    T.backup_steps, T.fresh, T.plan, T.next = K, fresh, _ptr(plan), _ptr(nxt)
+    T.gain_shared = int(np.ndim(Cn) == 2)
+    T.Am, T.Bm, T.dhat = _ptr(dev(abi(c["Am"]))), _ptr(dev(abi(c["Bm"]))), _ptr(dhat)
+    T.xhat, T.xhat_next = _ptr(xhat), _ptr(xhat)
+    T.C, T.Lx, T.Ld = _ptr(dev(abi(Cn))), _ptr(dev(abi(Lxn))), _ptr(dev(abi(Ldn)) if with_Ld else None)
+    T.v, T.y_meas = _ptr(dev(c["v"]) if with_v else None), _ptr(dev(c["ym"]) if with_y_meas else None)
+    T.y_out, T.xhat_out, T.d_out = _ptr(y_out), _ptr(xhat_out), _ptr(d_out)
+    T.vec2_mode, T.vec2_used = vec2_mode, -1
+    assert emu.emu_plant_observer_step(ctypes.byref(T)) == 0
+    for buf, n in ((xp, nx), (xhat, nx), (dhat, nx), (x_out, nx), (xhat_out, nx), (d_out, nx), (y_out, ny)):
+        assert (buf[batch * n:] == GUARD).all()
+    cut = lambda buf, n: buf[:batch * n].reshape(batch, n).copy()  # noqa: E731
+    return dict(xp=cut(xp, nx), xhat=cut(xhat, nx), dhat=cut(dhat, nx), x_out=cut(x_out, nx), xhat_out=cut(xhat_out, nx), d_out=cut(d_out, nx),
+                y_out=cut(y_out, ny), u_out=u_out, s_out=s_out, a_out=a_out, vec2=T.vec2_used)
+
+
+def _expect(c, plant, u, gains, with_Ld, with_w, with_v, with_y_meas):
+    """(xp+ exact or None, Sx, reference_observer's dict) of one tick for the applied controls u"""
+    Cn, Lxn, Ldn = gains
+    if with_y_meas:
+        return None, None, reference_observer(c["Am"], c["Bm"], c["dhat"], c["xhat"], u, Cn, Lxn, Ldn if with_Ld else None, y_meas=c["ym"])
+    if plant is None:
+        plant = (c["Am"], c["Bm"], c["dhat"])
+    ref, Sx = reference_step(plant[0], plant[1], plant[2], c["xp"], u, c["w"] if with_w else None)
+    return ref, Sx, reference_observer(c["Am"], c["Bm"], c["dhat"], c["xhat"], u, Cn, Lxn, Ldn if with_Ld else None, xplus=ref, Sx=Sx,
+                                       v=c["v"] if with_v else None)
+
+
+def _ratio(got, ref, bound):
+    err = np.abs(got.astype(LD) - ref)
+    return float((err / bound).max()) if err.size else 0.0
+
+
+def _check(got, c, ref, Sx, R, moved, gains, with_Ld, with_v, with_y_meas, what):
+    """every output of one tick against the rule; returns the worst error / bound seen"""
+    nx, nu = c["xp"].shape[1], c["fb"].shape[1]
+    for k in ("xp", "xhat", "dhat", "y_out"):
+        assert not np.isnan(got[k]).any(), (what, k)
+    worst = []
+    if with_y_meas:  # no plant: xp is not touched, x_out is not written, y_out is the measurement
+        assert _same_bits(got["xp"], c["xp"]) and (got["x_out"] == GUARD).all(), what
+        assert _same_bits(got["y_out"], c["ym"]), what
+    else:
+        worst.append(_ratio(got["xp"][moved], ref[moved], step_bound(nx, nu, Sx[moved])))
+        assert _same_bits(got["xp"][~moved], c["xp"][~moved]) and _same_bits(got["x_out"], got["xp"]), what  # held, bit for bit; the copy
+        worst.append(_ratio(got["y_out"][moved], R["y"][moved], R["Ey"][moved]))
+        yh, Eh = held_output(gains[0], c["xp"], c["v"] if with_v else None)
+        worst.append(_ratio(got["y_out"][~moved], yh[~moved], Eh[~moved]))
+    worst.append(_ratio(got["xhat"][moved], R["xhat"][moved], R["Eh"][moved]))
+    assert _same_bits(got["xhat"][~moved], c["xhat"][~moved]) and _same_bits(got["xhat_out"], got["xhat"]), what
+    if with_Ld:
+        worst.append(_ratio(got["dhat"][moved], R["dhat"][moved], R["Ed"][moved]))
+        assert _same_bits(got["dhat"][~moved], c["dhat"][~moved]) and _same_bits(got["d_out"], got["dhat"]), what
+    else:  # a state observer only: d is not touched, d_out is not written
+        assert _same_bits(got["dhat"], c["dhat"]) and (got["d_out"] == GUARD).all(), what
+    assert max(worst) <= 1.0, (what, worst)
+    return max(worst)
+
+
+@pytest.mark.parametrize("nx,nu,ny", SHAPES)
+def test_the_rule_on_the_kernel_bodies(emu, nx, nu, ny):
+    """xp+, y, xhat+ and dhat+ against the longdouble statement within the derived bounds: batches 1, 2, 67, groups 1, 2 and the launch's, a
+    plant given (per instance, shared) or not, w and v given or not, y_meas, Ld and per-instance gains on and off; once with misaligned pointers"""
+    runs, seen_vec2, worst = 0, set(), 0.0
+    for batch in (1, 2, 67):
+        rng = np.random.default_rng(1000 * nx + 100 * ny + 10 * nu + batch)
+        c = _model(rng, batch, nx, nu, ny, failed=batch // 5)
+        ok = c["status"] == 0
+        u = np.where(ok[:, None], c["control"][:, :nu], c["fb"])
+        moved = np.ones(batch, dtype=bool)
+        for with_y_meas, with_Ld, per_instance in itertools.product((False, True), (False, True), (False, True)):
+            gains = _gains(rng, batch, nx, ny, per_instance)
+            for kind, with_w, with_v in itertools.product(("own", "shared", "none"), (False, True), (False, True)):
+                if with_y_meas and (kind != "own" or with_w != with_v):  # (all three are ignored: one case with them, one without)
+                    continue
+                plant = _plant(rng, c, kind)
+                ref, Sx, R = _expect(c, plant, u, gains, with_Ld, with_w, with_v, with_y_meas)
+                for group in sorted({1, 2, launch_group(emu, nx, nu, ny)}):
+                    what = (nx, nu, ny, batch, with_y_meas, with_Ld, per_instance, kind, with_w, with_v, group)
+                    got = _tick(emu, c, plant, gains, with_Ld, with_w, with_v, True, with_y_meas, group)
+                    worst = max(worst, _check(got, c, ref, Sx, R, moved, gains, with_Ld, with_v, with_y_meas, what))
+                    assert _same_bits(got["u_out"], u) and np.array_equal(got["s_out"], c["status"]), what
+                    assert got["vec2"] == (1 if group % 2 == 0 else 0), what
+                    seen_vec2.add(got["vec2"])
+                    runs += 1
+        # misaligned pointers: the 16-byte copies are refused, the results pass the same checks
+        gains, plant = _gains(rng, batch, nx, ny, True), _plant(rng, c, "own")
+        ref, Sx, R = _expect(c, plant, u, gains, True, True, True, False)
+        got = _tick(emu, c, plant, gains, True, True, True, True, False, 2, misalign=True)
+        assert got["vec2"] == 0
+        worst = max(worst, _check(got, c, ref, Sx, R, moved, gains, True, True, False, (nx, nu, ny, batch, "misaligned")))
+    print("nx %d nu %d ny %d: %d runs, max err / bound = %.3f" % (nx, nu, ny, runs, worst))
+    assert seen_vec2 == {0, 1} and runs >= 3 * 4 * (12 + 2) * 2
+
+
+def test_the_launch_group_leaves_a_partial_last_group(emu):
+    """batch 67 ends in a partial last group at the launch's own group size, and that size is even; at (6, 3, 3) it is 12 instances"""
+    for nx, nu, ny in SHAPES:
+        g = launch_group(emu, nx, nu, ny)
+        assert g >= 2 and g % 2 == 0 and 67 % g != 0, (nx, nu, ny, g)
+    assert launch_group(emu, 6, 3, 3) == 12
+
+
+def test_held_instances_keep_every_state(emu):
+    """no fallback: a failed instance keeps xp, xhat and dhat bit for bit, y_out is C xp (+ v) of the unchanged state, u_out NaN"""
+    nx, nu, ny, batch = 6, 3, 3, 67
+    rng = np.random.default_rng(7)
+    c = _model(rng, batch, nx, nu, ny, failed=13)
+    ok = c["status"] == 0
+    assert 0 < (~ok).sum() < batch
+    u = np.where(ok[:, None], c["control"][:, :nu], 0.0)
+    for with_y_meas, with_Ld, per_instance, kind, group in itertools.product((False, True), (False, True), (False, True), ("own", "none"), (1, 2, 12)):
+        gains, plant = _gains(rng, batch, nx, ny, per_instance), _plant(rng, c, kind)
+        ref, Sx, R = _expect(c, plant, u, gains, with_Ld, True, True, with_y_meas)
+        got = _tick(emu, c, plant, gains, with_Ld, True, True, False, with_y_meas, group)
+        _check(got, c, ref, Sx, R, ok, gains, with_Ld, True, with_y_meas, (with_y_meas, with_Ld, per_instance, kind, group))
+        assert np.isnan(got["u_out"][~ok]).all() and _same_bits(got["u_out"][ok], c["control"][ok, :nu])
+        assert (got["a_out"][ok] == 0).all() and (got["a_out"][~ok] == HELD).all()
+    # a selector C has one term per row: the held y_out is a copy of the measured states, bit for bit
+    sel = np.eye(nx)[:ny]
+    got = _tick(emu, c, None, (sel, gains[1][0], gains[2][0]), True, False, False, False, False, 12)
+    assert _same_bits(got["y_out"][~ok], c["xp"][~ok][:, :ny])
+
+
+def _play(emu, nx, nu, ny, N, K, group, threads, with_Ld, per_instance, kind, with_w, with_v, with_fb, seed):
+    """the five-tick script of tests/test_backup_plan_abi.py with the observer on: the ages, and every state against the rule with the control
+    the tick APPLIED (fresh, plan step, fallback) or kept (held)"""
+    s = _script(nx, nu, N, 0, seed)
+    rng = np.random.default_rng(seed + 1)
+    gains = _gains(rng, BATCH, nx, ny, per_instance)
+    c = dict(Am=s["A"], Bm=s["B"], dhat=s["d"].copy(), xp=s["x0"].copy(), xhat=s["x0"] + 0.1 * rng.standard_normal((BATCH, nx)), fb=s["fb"], N=N,
+             ym=np.zeros((BATCH, ny)))
+    plant = _plant(rng, c, kind)
+    plan_buf = np.full(BATCH * K * nu, np.nan)
+    next_buf = np.zeros(BATCH, dtype=np.int32)
+    want_plan, want_next = plan_buf.reshape(BATCH, K, nu).copy(), next_buf.copy()
+    ages = []
+    for t in range(len(FRESH)):
+        u, age, want_plan, want_next = _rule(s, t, K, nu, with_fb, want_plan, want_next)
+        moved = age != HELD
+        c["w"], c["status"], c["control"], c["v"] = s["w"][t], s["status"][t], s["control"][t], 0.01 * rng.standard_normal((BATCH, ny))
+        ref, Sx, R = _expect(c, plant, np.where(moved[:, None], u, 0.0), gains, with_Ld, with_w, with_v, False)
+        got = _tick(emu, c, plant, gains, with_Ld, with_w, with_v, with_fb, False, group, threads, backup=(K, FRESH[t], plan_buf, next_buf))
+        what = (K, group, threads, with_Ld, per_instance, kind, with_w, with_v, with_fb, t)
+        assert np.array_equal(got["a_out"], age), what
+        assert _same_bits(got["u_out"], u), what
+        assert _same_bits(plan_buf.reshape(BATCH, K, nu), want_plan) and np.array_equal(next_buf, want_next), what
+        _check(got, c, ref, Sx, R, moved, gains, with_Ld, with_v, False, what)
+        c["xp"], c["xhat"], c["dhat"] = got["xp"], got["xhat"], got["dhat"]
+        ages.append(age)
+    return np.stack(ages)
+
+
+def test_backup_plan_and_fallback_ticks_move_the_estimate(emu):
+    """(6, 3, 3), K = 3: ages 0, 1 .. K, -1 and -2 all occur; the states follow the applied control on every one of them but -2"""
+    nx, nu, ny, N, K = 6, 3, 3, 4, 3
+    for with_Ld, per_instance, kind, noisy in itertools.product((False, True), (False, True), ("own", "none"), (False, True)):
+        for group, threads in ((1, 64), (2, 3), (4, 64)):
+            seen = set()
+            for with_fb in (False, True):
+                ages = _play(emu, nx, nu, ny, N, K, group, threads, with_Ld, per_instance, kind, noisy, noisy, with_fb, seed=11 + 2 * with_Ld + per_instance)
+                assert set(ages.ravel().tolist()) == set(range(0, K + 1)) | {FALLBACK if with_fb else HELD}
+                seen |= set(ages.ravel().tolist())
+            assert seen == set(range(-2, K + 1))
+
+
+@pytest.mark.parametrize("nx,nu", [(2, 1), (6, 3), (9, 3)])
+def test_full_state_observer_is_the_bias_estimator(emu, nx, nu):
+    """the identity: C = I, Lx = I, Ld the dense gain of ABI 11, no v -- xhat+ is xp+ and dhat+ is reference_bias' result, each within the sum of
+    the two derived bounds (the statement of the one rule and of the other agree exactly: both bounds are about the computed values)"""
+    batch = 67
+    rng = np.random.default_rng(90 + nx)
+    c = _model(rng, batch, nx, nu, nx)
+    c["xhat"] = c["xp"].copy()  # the full state is measured: the estimate IS the state
+    L = rng.uniform(-1.0, 1.0, (nx, nx))
+    gains = (np.eye(nx), np.eye(nx), L)
+    u = c["control"][:, :nu]
+    worst = 0.0
+    for kind, with_w, group in itertools.product(("own", "none"), (False, True), (1, 2, launch_group(emu, nx, nu, nx))):
+        plant = _plant(rng, c, kind)
+        ref, Sx, R = _expect(c, plant, u, gains, True, with_w, False, False)
+        dref, dbound = reference_bias(c["Am"], c["Bm"], c["dhat"], c["xp"], u, ref, Sx, L, True)
+        got = _tick(emu, c, plant, gains, True, with_w, False, False, False, group)
+        worst = max(worst, _ratio(got["xhat"], ref, step_bound(nx, nu, Sx) + R["Eh"]), _ratio(got["dhat"], dref, dbound + R["Ed"]))
+    print("nx %d: full-state observer against the estimator, max err / bound = %.3f" % (nx, worst))
+    assert worst <= 1.0
+
+
+# ---- memory errors on the host ----
+def test_kernel_bodies_under_the_address_and_ub_sanitizers(tmp_path):
+    """tests/emu/emu_plant_observer_main.cpp -- the backup script at (6, 3, 3), K = 3, batch 5, group 4 with the observer on, plus per-instance
+    matrices at (2, 1, 3) and (9, 3, 3), batch 7 -- as a stand-alone program built with -fsanitize=address,undefined; every array has exactly the
+    elements the kernel may touch.  Exit status 0 and an empty stderr."""
+    exe = str(tmp_path / "emu_plant_observer_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", os.path.join(EMU, "emu_plant_observer.cpp"), os.path.join(EMU, "emu_plant_observer_main.cpp"),
+                           "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stderr == "", r.stderr
+
+
+# ---- observer design ----
+def _riccati_residual(A, C, Qw, Rv, P, K):
+    """relative residual of the filter Riccati equation P = A (P - K C P) A' + Qw with K = P C' (C P C' + Rv)^-1"""
+    S = C @ P @ C.T + Rv
+    assert np.abs(K - P @ C.T @ np.linalg.inv(S)).max() <= 1e-9 * max(1.0, np.abs(K).max())
+    return np.abs(A @ (P - K @ C @ P) @ A.T + Qw - P).max() / np.abs(P).max()
+
+
+@pytest.mark.parametrize("with_bias", [False, True])
+def test_kalman_gain_on_the_double_integrator(with_bias):
+    from copra_amd.observer_design import kalman_gain
+    dt = 0.1
+    A = np.array([[1.0, dt], [0.0, 1.0]])
+    C = np.array([[1.0, 0.0]])
+    Qw, Rv = 1e-3 * np.eye(2), 1e-2 * np.eye(1)
+    if not with_bias:
+        Lx, info = kalman_gain(A, C, Qw, Rv, return_info=True)
+        assert Lx.shape == (2, 1)
+        assert _riccati_residual(A, C, Qw, Rv, info["P"], Lx) < 1e-9
+        err = (np.eye(2) - Lx @ C) @ A  # xhat+ - x+ = (I - Lx C) A (xhat - x)
+    else:
+        Qd = 1e-4 * np.eye(2)
+        with pytest.raises(ValueError):  # two disturbance states, one output: not observable
+            kalman_gain(A, C, Qw, Rv, with_bias=True, Qd=Qd)
+        # one disturbance direction (a force: it enters the velocity) is observable from the position
+        G = np.array([[0.0], [1.0]])
+        Lx, Ld, info = kalman_gain(A, C, Qw, Rv, with_bias=True, Qd=1e-4 * np.eye(1), Gd=G, return_info=True)
+        assert Lx.shape == (2, 1) and Ld.shape == (2, 1)
+        Aa, Ca, Qa = info["A"], info["C"], info["Q"]
+        Ka = np.vstack([Lx, np.linalg.pinv(G) @ Ld])
+        assert np.allclose(G @ (np.linalg.pinv(G) @ Ld), Ld)  # (Ld moves d along G only)
+        assert _riccati_residual(Aa, Ca, Qa, Rv, info["P"], Ka) < 1e-9
+        err = (np.eye(3) - Ka @ Ca) @ Aa
+    assert np.abs(np.linalg.eigvals(err)).max() < 1.0
+    # batched: a stack of systems gives the stack of gains
+    stack = kalman_gain(np.stack([A, A]), np.stack([C, C]), Qw, Rv)
+    assert stack.shape == (2, 2, 1) and np.allclose(stack[0], stack[1]) and np.allclose(stack[0], kalman_gain(A, C, Qw, Rv))
+
+
+def test_kalman_gain_refuses_an_unobservable_pair():
+    from copra_amd.observer_design import kalman_gain
+    A = np.array([[1.0, 0.1], [0.0, 1.0]])
+    with pytest.raises(ValueError):
+        kalman_gain(A, np.zeros((1, 2)), 1e-3 * np.eye(2), 1e-2 * np.eye(1))
