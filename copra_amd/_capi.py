@@ -75,6 +75,12 @@ class PlantStepObs(C.Structure):
                                        ("v_seq", C.c_void_p), ("y_hist", C.c_void_p), ("xhat_hist", C.c_void_p)]
 
 
+class Noise(C.Structure):
+    """copra_noise_t: what copra_batch_set_noise draws process and sensor noise from, on the device"""
+    _fields_ = [("struct_size", C.c_int), ("seed", C.c_ulonglong), ("first_instance", C.c_ulonglong), ("sigma_w", C.c_void_p),
+                ("sigma_v", C.c_void_p), ("per_instance", C.c_int), ("on_device", C.c_int)]
+
+
 PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
@@ -395,6 +401,16 @@ def lib():
         L.copra_batch_plant_state_device.argtypes = [vp]
         L.copra_batch_get_plant_state.restype = C.c_int
         L.copra_batch_get_plant_state.argtypes = [vp, vp]
+        L.copra_noise_init.restype = None
+        L.copra_noise_init.argtypes = [C.POINTER(Noise)]
+        L.copra_batch_set_noise.restype = C.c_int
+        L.copra_batch_set_noise.argtypes = [vp, C.POINTER(Noise)]
+        L.copra_batch_noise_seek.restype = C.c_int
+        L.copra_batch_noise_seek.argtypes = [vp, C.c_ulonglong]
+        L.copra_batch_noise_tick.restype = C.c_ulonglong
+        L.copra_batch_noise_tick.argtypes = [vp]
+        L.copra_batch_draw_noise.restype = C.c_int
+        L.copra_batch_draw_noise.argtypes = [vp, C.c_ulonglong, C.c_int, vp, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -44,6 +44,7 @@ class BatchLMPC:
         self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
         self._bias_keep = None  # ... and as the disturbance estimator's gain (set_bias_estimator)
         self._obs_keep, self._ny = None, 0  # ... and as the observer's C and gains (set_observer); its number of outputs, 0: off
+        self._noise_keep = None  # ... and as the standard deviations of the noise drawn on the device (set_noise)
         self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
@@ -542,6 +543,69 @@ class BatchLMPC:
     def plant_state_ptr(self):
         """device pointer of the plant's own state (copra_batch_plant_state_device); 0 while the observer was never on"""
         return int(self._lib.copra_batch_plant_state_device(self._h) or 0)
+
+    def set_noise(self, seed, process=None, sensor=None, first_instance=0):
+        """Noise drawn on the device (copra_batch_set_noise): from now on every advance() / tick of rollout() adds process * n to the plant's
+        disturbance and, with the observer on, sensor * n to its outputs, n standard normal from a counter-based generator -- the draw of
+        instance b at noise tick t depends on (seed, first_instance + b, row, t) alone, so it is the same in any batch, on any shard, and for
+        every controller variant run on the same seed; no array of noise is held.  process: standard deviations (nx,) or (batch, nx); sensor:
+        (ny,) or (batch, ny) (both the same way); numpy: copied; torch CUDA float64 tensors: used in place and kept alive.  A given
+        disturbance / noise is kept and the drawn term added.  Resets noise_tick to 0.  Both None: off."""
+        n = _capi.Noise()
+        self._lib.copra_noise_init(C.byref(n))
+        if process is None and sensor is None:
+            _capi.check(self._lib.copra_batch_set_noise(self._h, None))
+            self._noise_keep = None
+            return
+        given = [(a, rows, what) for a, rows, what in ((process, self.nx, "process"), (sensor, self._ny, "sensor")) if a is not None]
+        torch_in = _is_torch(given[0][0])
+        if any(_is_torch(a) != torch_in for a, _, _ in given):
+            raise ValueError("set_noise: process and sensor are both numpy or both torch CUDA tensors")
+        ptrs, keep, pers = {}, [], set()
+        for a, rows, what in given:
+            if torch_in:
+                if not (a.is_cuda and a.is_contiguous() and str(a.dtype) == "torch.float64"):
+                    raise ValueError("set_noise: contiguous CUDA float64 tensors are needed")
+                arr, ptr = a, a.data_ptr()
+            else:
+                arr = np.ascontiguousarray(a, dtype=np.float64)
+                ptr = arr.ctypes.data
+            if what == "sensor" and rows == 0:
+                rows = arr.shape[-1] if arr.ndim else 0  # (the observer is off: the library says so)
+            if tuple(arr.shape) not in ((rows,), (self.batch, rows)):
+                raise _capi.CopraDomainError("set_noise: %s of shape (%d,) or (%d, %d) expected, got %s" % (what, rows, self.batch, rows, tuple(arr.shape)))
+            pers.add(len(arr.shape) == 2)
+            ptrs[what] = ptr
+            keep.append(arr)
+        if len(pers) != 1:
+            raise _capi.CopraDomainError("set_noise: process and sensor are both given once or both per instance")
+        n.seed, n.first_instance = int(seed), int(first_instance)
+        n.sigma_w, n.sigma_v = ptrs.get("process"), ptrs.get("sensor")
+        n.per_instance, n.on_device = int(pers.pop()), int(torch_in)
+        _capi.check(self._lib.copra_batch_set_noise(self._h, C.byref(n)))
+        self._noise_keep = keep if torch_in else None
+
+    def noise_seek(self, tick):
+        """the noise tick the next advance() draws at (copra_batch_noise_seek)"""
+        _capi.check(self._lib.copra_batch_noise_seek(self._h, int(tick)))
+
+    @property
+    def noise_tick(self):
+        """plant steps since set_noise, or what noise_seek set plus the steps since (copra_batch_noise_tick)"""
+        return int(self._lib.copra_batch_noise_tick(self._h))
+
+    def draw_noise(self, tick, stream="process", out=None, hip_stream=None):
+        """the noise terms of one noise tick (copra_batch_draw_noise), bit for bit what the plant step of that tick adds: a torch CUDA tensor
+        (batch, nx) for stream "process", (batch, ny) for "sensor"; written into `out` if given"""
+        if stream not in ("process", "sensor"):
+            raise ValueError("draw_noise: stream is 'process' or 'sensor'")
+        rows = self.nx if stream == "process" else self._ny
+        if out is None:
+            import torch
+            out = torch.empty((self.batch, rows), dtype=torch.float64, device="cuda")
+        ptr, t = self._device(out, (self.batch, rows), "draw_noise out")
+        _capi.check(self._lib.copra_batch_draw_noise(self._h, int(tick), 0 if stream == "process" else 1, ptr, C.c_void_p(hip_stream or 0)))
+        return t
 
     def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None, noise=None,
                     y_meas=None, y_out=None, xhat_out=None):

@@ -8,6 +8,8 @@
 // (d_bias, the controller's d while the estimates are in force) by a gain times the model's prediction error, in the same launch.
 // copra_batch_set_observer / _set_plant_state / _plant_state_device / _get_plant_state: output feedback -- the plant keeps a state of its own
 // (d_xp), the controller's x0 is the estimate, which the same launch corrects with the innovation of ny measured outputs.
+// copra_batch_set_noise / _noise_seek / _noise_tick / _draw_noise: Monte-Carlo ticks -- phase 1 of the plant step draws process and sensor
+// noise from a counter-based generator (plant_noise.hpp) at the handle's noise tick; builds of the kernels of their own, no memory.
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
@@ -192,10 +194,11 @@ copra_status_t launch_observer(copra_batch* h, const PlantStepArgs& P, const cop
     Q.xhat_next = h->own_x0;
     Q.C = h->obs_C, Q.Lx = h->obs_Lx, Q.Ld = h->obs_Ld;
     Q.yv = Q.meas ? io.y_meas : io.v;
+    if (!Q.meas && h->noise_sv && h->noise_ny == Q.ny) Q.sigma_v = h->noise_sv;
     Q.y_out = io.y_out, Q.xhat_out = io.xhat_out, Q.d_out = io.d_out;
     if (Q.same_model) Q.s.A = h->A, Q.s.B = h->B, Q.s.d = h->d, Q.s.shared = 0;
     if (Q.meas) { // a real plant: the state of the tick's image is the estimate, nothing of the simulated plant is looked at
-        Q.s.x0 = h->x0, Q.s.x0_next = nullptr, Q.s.x_out = nullptr, Q.s.w = nullptr;
+        Q.s.x0 = h->x0, Q.s.x0_next = nullptr, Q.s.x_out = nullptr, Q.s.w = nullptr, Q.s.sigma_w = nullptr;
     } else {
         Q.s.x0 = h->d_xp, Q.s.x0_next = h->d_xp;
     }
@@ -204,11 +207,12 @@ copra_status_t launch_observer(copra_batch* h, const PlantStepArgs& P, const cop
     const int group = plant_group(one);
     Q.s.group = group;
     Q.s.vec2 = plant_obs_vec2_ok(Q);
-    const size_t lds_bytes = (size_t)plant_obs_lds(HP.nx, HP.nu, Q.ny, group, Q.s.shared, Q.s.w != nullptr, Q.s.backup_steps > 0, Q.same_model, Q.meas,
-                                 Q.Ld != nullptr, Q.gain_shared, Q.yv != nullptr).total * sizeof(double);
-    if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_plant_observer_kernel, lds_bytes);
+    const size_t lds_bytes = (size_t)plant_obs_lds(HP.nx, HP.nu, Q.ny, group, Q.s.shared, plant_has_w(Q.s), Q.s.backup_steps > 0, Q.same_model, Q.meas,
+                                 Q.Ld != nullptr, Q.gain_shared, plant_obs_has_yv(Q)).total * sizeof(double);
+    void (*const kernel)(const PlantObsArgs) = Q.s.sigma_w || Q.sigma_v ? copra_plant_observer_noise_kernel : copra_plant_observer_kernel;
+    if (lds_bytes > 48 * 1024) LDS_OPT_IN(kernel, lds_bytes);
     const unsigned grid = (unsigned)((HP.batch + group - 1) / group);
-    hipLaunchKernelGGL(copra_plant_observer_kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, Q);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPlantThreads), lds_bytes, s, Q);
     HIP_TRY(hipGetLastError());
     return COPRA_OK;
 }
@@ -247,6 +251,11 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     P.x0 = h->x0; // (a caller's device buffer is read this once more, never written)
     P.x0_next = h->own_x0;
     P.w = w;
+    if (h->noise_sw || h->noise_sv) { // drawn in phase 1, at the handle's noise tick
+        P.sigma_w = h->noise_sw;
+        P.sigma_per_instance = h->noise_per_instance;
+        P.noise = NoiseGen { h->noise_seed, h->noise_first, h->noise_tick };
+    }
     P.fallback_u = st.fallback_u;
     P.status = h->ad.last_status;
     P.control = h->ad.last_control;
@@ -275,10 +284,11 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     const int group = plant_group(one);
     P.group = group;
     P.vec2 = plant_vec2_ok(P);
-    const size_t lds_doubles = P.est ? (size_t)plant_est_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0, P.same_model, P.gain_dense, P.gain_shared).total
-                                     : (size_t)plant_lds(P.nx, P.nu, group, P.shared, P.w != nullptr, P.backup_steps > 0).total;
+    const size_t lds_doubles = P.est ? (size_t)plant_est_lds(P.nx, P.nu, group, P.shared, plant_has_w(P), P.backup_steps > 0, P.same_model, P.gain_dense, P.gain_shared).total
+                                     : (size_t)plant_lds(P.nx, P.nu, group, P.shared, plant_has_w(P), P.backup_steps > 0).total;
     const size_t lds_bytes = lds_doubles * sizeof(double);
-    void (*const kernel)(const PlantStepArgs) = P.est ? copra_plant_step_kernel<true> : copra_plant_step_kernel<false>;
+    void (*const kernel)(const PlantStepArgs) = P.sigma_w ? (P.est ? copra_plant_step_kernel<true, true> : copra_plant_step_kernel<false, true>)
+                                                          : (P.est ? copra_plant_step_kernel<true> : copra_plant_step_kernel<false>);
     if (lds_bytes > 48 * 1024 && !h->obs_on) LDS_OPT_IN(kernel, lds_bytes);
     if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
         if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
@@ -296,6 +306,7 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     h->x0 = h->own_x0;
     h->plan_fresh = false;
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
+    h->noise_tick += 1; // (counted whether noise is drawn or not: a seek or a new copra_batch_set_noise says where the draws stand)
     h->sched_tick += 1; // time moves on for every instance, a failed one included: the next solve reads the next window
     return write_windows(h, s, who);
 }
@@ -476,6 +487,8 @@ copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* 
     }
     if (ny < 1) return fail(COPRA_ERR_ARG, std::string(who) + ": ny < 1");
     if (!Lx) return fail(COPRA_ERR_ARG, std::string(who) + ": C needs a gain Lx");
+    if (h->noise_sv && ny != h->noise_ny)
+        return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the sensor noise in force was given for another ny: call copra_batch_set_noise again first");
     if (h->shared || h->shared_as_batch)
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one model for the batch (copra_batch_set_shared_system); write the model out with copra_batch_set_system");
     if (!h->A || !h->B || !h->d) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no preview system set (copra_batch_set_system)");
@@ -553,6 +566,109 @@ copra_status_t copra_batch_get_plant_state(copra_batch_t* h, double* x)
     if (!h->d_xp) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the plant has no state of its own: the observer was never on (copra_batch_set_observer)");
     HIP_TRY(hipStreamSynchronize(h->last_stream));
     HIP_TRY(hipMemcpy(x, h->d_xp, (size_t)h->hp.plan.batch * h->hp.plan.nx * sizeof(double), hipMemcpyDeviceToHost));
+    return COPRA_OK;
+}
+
+void copra_noise_init(copra_noise_t* noise)
+{
+    if (!noise) return;
+    std::memset(noise, 0, sizeof *noise);
+    noise->struct_size = (int)sizeof *noise;
+}
+
+copra_status_t copra_batch_set_noise(copra_batch_t* h, const copra_noise_t* noise)
+{
+    const char* const who = "copra_batch_set_noise";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    copra_noise_t n;
+    std::memset(&n, 0, sizeof n);
+    if (noise) { // (fields beyond the caller's struct_size keep their defaults: all zero)
+        if (noise->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_noise_t::struct_size is not set (copra_noise_init)");
+        std::memcpy(&n, noise, (size_t)noise->struct_size < sizeof n ? (size_t)noise->struct_size : sizeof n);
+    }
+    if (!n.sigma_w && !n.sigma_v) { // off: nothing is drawn; the library's copies stay for the next time
+        h->noise_sw = h->noise_sv = nullptr;
+        h->noise_tick = 0;
+        return COPRA_OK;
+    }
+    const FusedPlan& P = h->hp.plan;
+    const unsigned long long top = 1ull << 32;
+    if (n.first_instance > top || (unsigned long long)(P.batch > 0 ? P.batch : 0) > top - n.first_instance)
+        return fail(COPRA_ERR_ARG, std::string(who) + ": first_instance + batch beyond 2^32");
+    if (n.sigma_v && !h->obs_on) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": sensor noise needs the observer (copra_batch_set_observer)");
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    const size_t cw = (n.per_instance ? b : 1) * (size_t)P.nx, cv = (n.per_instance ? b : 1) * (size_t)h->obs_ny;
+    if (!n.on_device) {
+        const auto bad = [](const double* a, size_t count) {
+            for (size_t i = 0; a && i < count; ++i)
+                if (!(a[i] >= 0.0)) return true;
+            return false;
+        };
+        if (bad(n.sigma_w, cw) || bad(n.sigma_v, cv)) return fail(COPRA_ERR_ARG, std::string(who) + ": a negative or NaN sigma");
+        HIP_TRY(hipStreamSynchronize(h->last_stream)); // the library's copies: a tick that still reads the old ones first
+        if (n.sigma_w) {
+            if (h->own_noise_sw.count() < cw) {
+                h->noise_sw = nullptr; // (it may be the copy that goes)
+                OWN_TRY(h->own_noise_sw.alloc(cw));
+            }
+            HIP_TRY(hipMemcpy(h->own_noise_sw, n.sigma_w, cw * sizeof(double), hipMemcpyHostToDevice));
+            n.sigma_w = h->own_noise_sw;
+        }
+        if (n.sigma_v) {
+            if (h->own_noise_sv.count() < cv) {
+                h->noise_sv = nullptr;
+                OWN_TRY(h->own_noise_sv.alloc(cv));
+            }
+            HIP_TRY(hipMemcpy(h->own_noise_sv, n.sigma_v, cv * sizeof(double), hipMemcpyHostToDevice));
+            n.sigma_v = h->own_noise_sv;
+        }
+    }
+    h->noise_sw = n.sigma_w, h->noise_sv = n.sigma_v;
+    h->noise_per_instance = n.per_instance != 0;
+    h->noise_ny = n.sigma_v ? h->obs_ny : 0;
+    h->noise_seed = n.seed, h->noise_first = n.first_instance;
+    h->noise_tick = 0;
+    return COPRA_OK;
+}
+
+copra_status_t copra_batch_noise_seek(copra_batch_t* h, unsigned long long tick)
+{
+    if (!h) return fail(COPRA_ERR_ARG, "copra_batch_noise_seek: null handle");
+    const copra_status_t rc = check_handle(h, "copra_batch_noise_seek");
+    if (rc != COPRA_OK) return rc;
+    h->noise_tick = tick;
+    return COPRA_OK;
+}
+
+unsigned long long copra_batch_noise_tick(const copra_batch_t* h)
+{
+    return h ? h->noise_tick : 0;
+}
+
+copra_status_t copra_batch_draw_noise(copra_batch_t* h, unsigned long long tick, int stream, double* out_device, void* hip_stream)
+{
+    const char* const who = "copra_batch_draw_noise";
+    if (!h) return fail(COPRA_ERR_ARG, std::string(who) + ": null handle");
+    if (stream != 0 && stream != 1) return fail(COPRA_ERR_ARG, std::string(who) + ": stream is 0 (process noise) or 1 (sensor noise)");
+    if (!out_device) return fail(COPRA_ERR_ARG, std::string(who) + ": null out_device");
+    const copra_status_t rc = check_handle(h, who);
+    if (rc != COPRA_OK) return rc;
+    if (stream == 1 && !h->obs_on) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": sensor noise needs the observer (copra_batch_set_observer)");
+    const double* const sigma = stream == 0 ? h->noise_sw : (h->noise_ny == h->obs_ny ? h->noise_sv : nullptr);
+    if (!sigma) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": no sigma set for this stream (copra_batch_set_noise)");
+    const FusedPlan& P = h->hp.plan;
+    if (P.batch <= 0) return COPRA_OK;
+    NoiseFillArgs F {};
+    F.batch = P.batch, F.rows = stream == 0 ? P.nx : h->obs_ny, F.stream = stream, F.per_instance = h->noise_per_instance;
+    F.gen = NoiseGen { h->noise_seed, h->noise_first, tick };
+    F.sigma = sigma, F.out = out_device;
+    const int pairs = (F.rows + 1) / 2; // one thread per pair: a group fills the workgroup
+    F.group = pairs >= kNoiseFillThreads ? 1 : kNoiseFillThreads / pairs;
+    const unsigned grid = (unsigned)((F.batch + F.group - 1) / F.group);
+    hipLaunchKernelGGL(copra_noise_fill_kernel, dim3(grid), dim3(kNoiseFillThreads), 0, (hipStream_t)hip_stream, F);
+    HIP_TRY(hipGetLastError());
     return COPRA_OK;
 }
 

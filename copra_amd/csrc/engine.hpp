@@ -9,7 +9,8 @@
 //   copra_hip_packed16/32.hip  the one-wave bodies with 16 / 32 lanes per instance
 //   copra_hip_plant.hip    the receding-horizon tick: copra_batch_advance / copra_batch_rollout and their kernel (plant_step.hpp); reference
 //                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp); limit schedules
-//                          (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule, limit_window.hpp)
+//                          (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule, limit_window.hpp); noise drawn in
+//                          the plant step and its fill kernel (copra_batch_set_noise, copra_batch_draw_noise, plant_noise.hpp)
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -208,6 +209,12 @@ struct copra_batch {
     const double *obs_C = nullptr, *obs_Lx = nullptr, *obs_Ld = nullptr; // device: the caller's, or the copies below; obs_Ld null: d is not estimated
     Dev<double> own_obs_C, own_obs_Lx, own_obs_Ld; // the library's copies of host arrays
     Dev<double> d_xp; // [batch][nx]: the plant's own state, from the first time the observer is turned on
+    // noise drawn on the device (copra_batch_set_noise; copra_hip_plant.hip, plant_noise.hpp)
+    const double *noise_sw = nullptr, *noise_sv = nullptr; // device: the caller's, or the copies below; null: that stream is off
+    Dev<double> own_noise_sw, own_noise_sv; // the library's copies of host arrays
+    int noise_per_instance = 0, noise_ny = 0; // (noise_ny: the observer's ny that noise_sv was given for)
+    unsigned long long noise_seed = 0, noise_first = 0;
+    unsigned long long noise_tick = 0; // plant steps since copra_batch_set_noise, or what copra_batch_noise_seek set
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation

@@ -38,10 +38,18 @@
 // The state observer (copra_batch_set_observer, PlantObsArgs) is a third build, copra_plant_observer_kernel: the two phases of the tick on the
 // plant's OWN state xp, then the innovation of ny measured outputs and the update of the estimate xhat (the controller's x0) and, optionally,
 // of dhat -- its rule, image and phases stand in front of its code below.  The two builds above do not know of it.
+//
+// Noise drawn on the device (copra_batch_set_noise, ABI 13; plant_noise.hpp): with kNoise phase 1 fills the w slot of the image -- and the
+// observer's yv slot -- from a counter-based generator, w = (w given ? w : 0) + sigma_w n, one thread per pair of rows, which reads the given
+// w of its two rows itself (no barrier between a copy and the sum).  kNoise is a template value of every phase and of the kernels: the builds
+// without it hold none of the generator's code and never load the sigmas -- they are the code of ABI 12; plant_has_w / plant_obs_has_yv say
+// for every build whether the image has the slot.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+
+#include "plant_noise.hpp"
 
 #ifndef COPRA_DEV
 #if defined(__HIPCC__)
@@ -86,7 +94,16 @@ struct PlantStepArgs {
     const double* gain;
     double* dhat; // [batch][nx]: the controller's d, read in phase 1, written behind the last barrier
     double* d_out; // optional [batch][nx]: a copy of the new estimates
+    // noise drawn on the device (plant_noise.hpp; all zero: off -- the builds without kNoise never look at them)
+    const double* sigma_w; // [nx] or [batch][nx]: process noise, w = (w given ? w : 0) + sigma_w n; null: none
+    int sigma_per_instance; // sigma_w (and the observer's sigma_v) hold one block per instance
+    NoiseGen noise; // seed, global index of instance 0, noise tick
 };
+
+// whether the image has a w slot: a w is given or process noise is drawn -- what every caller of the layout functions passes as has_w.
+// kNoise = false is the answer of the builds without noise, which are launched only while sigma_w is null and do not load it
+template <bool kNoise = true>
+COPRA_PLANT_HD bool plant_has_w(const PlantStepArgs& P) { return P.w != nullptr || (kNoise && P.sigma_w != nullptr); }
 
 constexpr int kPlantAgeFallback = -1, kPlantAgeHeld = -2; // (COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD of include/copra_hip.h)
 
@@ -147,9 +164,10 @@ COPRA_PLANT_HD PlantEstLds plant_est_lds(int nx, int nu, int group, int shared, 
     E.total = o;
     return E;
 }
+template <bool kNoise = false>
 COPRA_DEV PlantEstLds plant_est_lds(const PlantStepArgs& P, int backup)
 {
-    return plant_est_lds(P.nx, P.nu, P.group, P.shared, P.w != nullptr, backup, P.same_model, P.gain_dense, P.gain_shared);
+    return plant_est_lds(P.nx, P.nu, P.group, P.shared, plant_has_w<kNoise>(P), backup, P.same_model, P.gain_dense, P.gain_shared);
 }
 
 // dst[0 .. count) = src[0 .. count), thread `tid` of `T`: consecutive lanes, consecutive addresses
@@ -186,20 +204,22 @@ COPRA_DEV int plant_age(const PlantStepArgs& P, size_t b)
 }
 
 // phase 1: everything workgroup `wg` reads, into its image `lds`
-template <bool kBackup, bool kEst = false>
+template <bool kBackup, bool kEst = false, bool kNoise = false>
 COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr, kBackup);
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, plant_has_w<kNoise>(P), kBackup);
     const size_t s0 = P.shared ? 0 : (size_t)b0;
     const int scnt = P.shared ? 1 : cnt;
     plant_copy(lds + L.oA, P.A + s0 * nx * nx, scnt * nx * nx, tid, T, P.vec2);
     plant_copy(lds + L.oB, P.B + s0 * nx * nu, scnt * nx * nu, tid, T, P.vec2);
     plant_copy(lds + L.od, P.d + s0 * nx, scnt * nx, tid, T, P.vec2);
     plant_copy(lds + L.ox, P.x0 + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
-    if (P.w) plant_copy(lds + L.ow, P.w + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
+    if (kNoise && P.sigma_w) // (the thread that draws a pair reads the given w of its two rows itself: no barrier between a copy and the sum)
+        noise_stage(P.noise, 0, P.sigma_w, P.sigma_per_instance, P.w, (size_t)b0, cnt, nx, lds + L.ow, tid, T);
+    else if (P.w) plant_copy(lds + L.ow, P.w + (size_t)b0 * nx, cnt * nx, tid, T, P.vec2);
     int* st = reinterpret_cast<int*>(lds + L.ost);
     for (int i = tid; i < cnt; i += T) st[i] = P.status[b0 + i];
     if (kBackup) {
@@ -222,7 +242,7 @@ COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, 
         lds[L.ou + e] = u;
     }
     if (kEst) { // the model, the estimates and the gain (same_model: A, B, d above were the model and the estimates)
-        const PlantEstLds E = plant_est_lds(P, kBackup);
+        const PlantEstLds E = plant_est_lds<kNoise>(P, kBackup);
         if (!P.same_model) {
             plant_copy(lds + E.oAm, P.Am + (size_t)b0 * nx * nx, cnt * nx * nx, tid, T, P.vec2);
             plant_copy(lds + E.oBm, P.Bm + (size_t)b0 * nx * nu, cnt * nx * nu, tid, T, P.vec2);
@@ -232,27 +252,28 @@ COPRA_DEV void plant_stage_body(const PlantStepArgs& P, int wg, int tid, int T, 
         plant_copy(lds + E.oG, P.gain + (P.gain_shared ? 0 : (size_t)b0 * g1), (P.gain_shared ? 1 : cnt) * g1, tid, T, P.vec2);
     }
 }
+template <bool kNoise = false>
 COPRA_DEV void plant_stage(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
-    if (P.backup_steps > 0) plant_stage_body<true>(P, wg, tid, T, lds);
-    else plant_stage_body<false>(P, wg, tid, T, lds);
+    if (P.backup_steps > 0) plant_stage_body<true, false, kNoise>(P, wg, tid, T, lds);
+    else plant_stage_body<false, false, kNoise>(P, wg, tid, T, lds);
 }
 
 // phase 2 (behind a barrier): the new states and the optional copies; with backup plans the tails of the fresh plans and every next[b]
-template <bool kBackup, bool kEst = false, bool kPlant = true>
+template <bool kBackup, bool kEst = false, bool kPlant = true, bool kNoise = false>
 COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, const double* lds, double* xn_lds = nullptr)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, P.w != nullptr, kBackup);
+    const PlantLds L = plant_lds(nx, nu, P.group, P.shared, plant_has_w<kNoise>(P), kBackup);
     const int* st = reinterpret_cast<const int*>(lds + L.ost);
     const int* ag = reinterpret_cast<const int*>(lds + L.oag); // (read with backup plans only)
     for (int e = tid; kPlant && e < cnt * nx; e += T) { // (kPlant = false: the observer fed with measured outputs moves no plant)
         const int i = e / nx, r = e - i * nx, is = P.shared ? 0 : i;
         double xn = lds[L.ox + e]; // held
         if (kBackup ? ag[i] != kPlantAgeHeld : (st[i] == 0 || P.fallback_u))
-            xn = plant_row(nx, nu, r, lds + L.oA + is * nx * nx, lds + L.oB + is * nx * nu, lds + L.od + is * nx, P.w ? lds + L.ow + i * nx : nullptr,
+            xn = plant_row(nx, nu, r, lds + L.oA + is * nx * nx, lds + L.oB + is * nx * nu, lds + L.od + is * nx, plant_has_w<kNoise>(P) ? lds + L.ow + i * nx : nullptr,
                 lds + L.ox + i * nx, lds + L.ou + i * nu);
         const size_t o = (size_t)b0 * nx + e;
         P.x0_next[o] = xn;
@@ -292,23 +313,26 @@ COPRA_DEV void plant_apply_body(const PlantStepArgs& P, int wg, int tid, int T, 
         if (P.age_out) P.age_out[b0 + i] = age;
     }
 }
+template <bool kNoise = false>
 COPRA_DEV void plant_apply(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
 {
-    if (P.backup_steps > 0) plant_apply_body<true>(P, wg, tid, T, lds);
-    else plant_apply_body<false>(P, wg, tid, T, lds);
+    if (P.backup_steps > 0) plant_apply_body<true, false, true, kNoise>(P, wg, tid, T, lds);
+    else plant_apply_body<false, false, true, kNoise>(P, wg, tid, T, lds);
 }
 
 
 // ---- the same two phases with the estimator (est != 0), and its own ----
+template <bool kNoise = false>
 COPRA_DEV void plant_stage_est(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
-    if (P.backup_steps > 0) plant_stage_body<true, true>(P, wg, tid, T, lds);
-    else plant_stage_body<false, true>(P, wg, tid, T, lds);
+    if (P.backup_steps > 0) plant_stage_body<true, true, kNoise>(P, wg, tid, T, lds);
+    else plant_stage_body<false, true, kNoise>(P, wg, tid, T, lds);
 }
+template <bool kNoise = false>
 COPRA_DEV void plant_apply_est(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
-    if (P.backup_steps > 0) plant_apply_body<true, true>(P, wg, tid, T, lds, lds + plant_est_lds(P, 1).oxn);
-    else plant_apply_body<false, true>(P, wg, tid, T, lds, lds + plant_est_lds(P, 0).oxn);
+    if (P.backup_steps > 0) plant_apply_body<true, true, true, kNoise>(P, wg, tid, T, lds, lds + plant_est_lds<kNoise>(P, 1).oxn);
+    else plant_apply_body<false, true, true, kNoise>(P, wg, tid, T, lds, lds + plant_est_lds<kNoise>(P, 0).oxn);
 }
 
 // whether instance i of the group had a control applied (phase 2's own condition)
@@ -319,12 +343,13 @@ COPRA_DEV bool plant_moved(const PlantStepArgs& P, const PlantLds& L, const doub
 }
 
 // phase 3 (behind the second barrier): e_r = x+_r - pred_r per (instance, row), into the image; the model's prediction has no w
+template <bool kNoise = false>
 COPRA_DEV void plant_estimate(const PlantStepArgs& P, int wg, int tid, int T, double* lds)
 {
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantEstLds E = plant_est_lds(P, P.backup_steps > 0);
+    const PlantEstLds E = plant_est_lds<kNoise>(P, P.backup_steps > 0);
     const PlantLds& L = E.base;
     for (int e = tid; e < cnt * nx; e += T) {
         const int i = e / nx, r = e - i * nx;
@@ -337,12 +362,13 @@ COPRA_DEV void plant_estimate(const PlantStepArgs& P, int wg, int tid, int T, do
 }
 
 // ... and behind a third barrier (the dense gain reads every row's e of its instance): dhat+ and its copy, one contiguous range per group
+template <bool kNoise = false>
 COPRA_DEV void plant_estimate_store(const PlantStepArgs& P, int wg, int tid, int T, const double* lds)
 {
     const int nx = P.nx, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantEstLds E = plant_est_lds(P, P.backup_steps > 0);
+    const PlantEstLds E = plant_est_lds<kNoise>(P, P.backup_steps > 0);
     for (int e = tid; e < cnt * nx; e += T) {
         const int i = e / nx, r = e - i * nx;
         double dn = lds[E.odh + e]; // held: bit for bit
@@ -391,7 +417,12 @@ struct PlantObsArgs {
     const double *C, *Lx, *Ld; // Ld may be null
     const double* yv; // [batch][ny]: v (may be null) or y_meas
     double *y_out, *xhat_out, *d_out; // optional copies
+    const double* sigma_v; // [ny] or [batch][ny] (s.sigma_per_instance): sensor noise drawn on the device, v = (v given ? v : 0) + sigma_v n; null: none
 };
+
+// whether the image has a yv slot: y_meas or a v is given, or sensor noise is drawn (never with y_meas, where v is ignored)
+template <bool kNoise = true>
+COPRA_PLANT_HD bool plant_obs_has_yv(const PlantObsArgs& Q) { return Q.yv != nullptr || (kNoise && !Q.meas && Q.sigma_v != nullptr); }
 
 inline bool plant_obs_vec2_ok(const PlantObsArgs& Q)
 {
@@ -428,21 +459,23 @@ COPRA_PLANT_HD PlantObsLds plant_obs_lds(int nx, int nu, int ny, int group, int 
     E.total = o;
     return E;
 }
+template <bool kNoise = false>
 COPRA_DEV PlantObsLds plant_obs_lds(const PlantObsArgs& Q)
 {
-    return plant_obs_lds(Q.s.nx, Q.s.nu, Q.ny, Q.s.group, Q.s.shared, Q.s.w != nullptr, Q.s.backup_steps > 0, Q.same_model, Q.meas, Q.Ld != nullptr,
-        Q.gain_shared, Q.yv != nullptr);
+    return plant_obs_lds(Q.s.nx, Q.s.nu, Q.ny, Q.s.group, Q.s.shared, plant_has_w<kNoise>(Q.s), Q.s.backup_steps > 0, Q.same_model, Q.meas, Q.Ld != nullptr,
+        Q.gain_shared, plant_obs_has_yv<kNoise>(Q));
 }
 
 // phase 1: the image of the tick, then what the observer reads beside it
+template <bool kNoise = false>
 COPRA_DEV void plant_obs_stage(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
 {
     const PlantStepArgs& P = Q.s;
-    plant_stage(P, wg, tid, T, lds);
+    plant_stage<kNoise>(P, wg, tid, T, lds);
     const int nx = P.nx, nu = P.nu, ny = Q.ny, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantObsLds E = plant_obs_lds(Q);
+    const PlantObsLds E = plant_obs_lds<kNoise>(Q);
     if (!Q.same_model) {
         plant_copy(lds + E.oAm, Q.Am + (size_t)b0 * nx * nx, cnt * nx * nx, tid, T, P.vec2);
         plant_copy(lds + E.oBm, Q.Bm + (size_t)b0 * nx * nu, cnt * nx * nu, tid, T, P.vec2);
@@ -454,20 +487,22 @@ COPRA_DEV void plant_obs_stage(const PlantObsArgs& Q, int wg, int tid, int T, do
     plant_copy(lds + E.oC, Q.C + g0, gcnt * g1, tid, T, P.vec2);
     plant_copy(lds + E.oLx, Q.Lx + g0, gcnt * g1, tid, T, P.vec2);
     if (Q.Ld) plant_copy(lds + E.oLd, Q.Ld + g0, gcnt * g1, tid, T, P.vec2);
-    if (Q.yv) plant_copy(lds + E.oyv, Q.yv + (size_t)b0 * ny, cnt * ny, tid, T, P.vec2);
+    if (kNoise && !Q.meas && Q.sigma_v) noise_stage(P.noise, 1, Q.sigma_v, P.sigma_per_instance, Q.yv, (size_t)b0, cnt, ny, lds + E.oyv, tid, T);
+    else if (Q.yv) plant_copy(lds + E.oyv, Q.yv + (size_t)b0 * ny, cnt * ny, tid, T, P.vec2);
 }
 
 // phase 2 (behind a barrier): the plant's new state -- the tick's own phase 2 on xp, which leaves xp+ in the image -- and the model's prediction
+template <bool kNoise = false>
 COPRA_DEV void plant_obs_apply(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
 {
     const PlantStepArgs& P = Q.s;
-    const PlantObsLds E = plant_obs_lds(Q);
+    const PlantObsLds E = plant_obs_lds<kNoise>(Q);
     if (Q.meas) {
-        if (P.backup_steps > 0) plant_apply_body<true, false, false>(P, wg, tid, T, lds);
-        else plant_apply_body<false, false, false>(P, wg, tid, T, lds);
+        if (P.backup_steps > 0) plant_apply_body<true, false, false, kNoise>(P, wg, tid, T, lds);
+        else plant_apply_body<false, false, false, kNoise>(P, wg, tid, T, lds);
     } else {
-        if (P.backup_steps > 0) plant_apply_body<true, true>(P, wg, tid, T, lds, lds + E.oxn);
-        else plant_apply_body<false, true>(P, wg, tid, T, lds, lds + E.oxn);
+        if (P.backup_steps > 0) plant_apply_body<true, true, true, kNoise>(P, wg, tid, T, lds, lds + E.oxn);
+        else plant_apply_body<false, true, true, kNoise>(P, wg, tid, T, lds, lds + E.oxn);
     }
     const int nx = P.nx, nu = P.nu, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
@@ -483,13 +518,14 @@ COPRA_DEV void plant_obs_apply(const PlantObsArgs& Q, int wg, int tid, int T, do
 }
 
 // phase 3 (behind the second barrier): y and the innovation per (instance, output)
+template <bool kNoise = false>
 COPRA_DEV void plant_obs_innovate(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)
 {
     const PlantStepArgs& P = Q.s;
     const int nx = P.nx, ny = Q.ny, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantObsLds E = plant_obs_lds(Q);
+    const PlantObsLds E = plant_obs_lds<kNoise>(Q);
     for (int e = tid; e < cnt * ny; e += T) {
         const int i = e / ny, o = e - i * ny;
         const double* Cm = lds + E.oC + (Q.gain_shared ? 0 : i * ny * nx);
@@ -497,7 +533,7 @@ COPRA_DEV void plant_obs_innovate(const PlantObsArgs& Q, int wg, int tid, int T,
         if (Q.meas) {
             y = lds[E.oyv + e];
         } else { // (a held instance's xp+ in the image is its unchanged xp)
-            y = Q.yv ? lds[E.oyv + e] : 0.0;
+            y = plant_obs_has_yv<kNoise>(Q) ? lds[E.oyv + e] : 0.0;
             for (int j = 0; j < nx; ++j) y += Cm[o + ny * j] * lds[E.oxn + i * nx + j];
         }
         double inn = 0.0; // held: nothing was applied, nothing is learnt
@@ -512,13 +548,14 @@ COPRA_DEV void plant_obs_innovate(const PlantObsArgs& Q, int wg, int tid, int T,
 }
 
 // phase 4 (behind the third barrier: a row reads every innovation of its instance): xhat+, dhat+ and their copies
+template <bool kNoise = false>
 COPRA_DEV void plant_obs_update(const PlantObsArgs& Q, int wg, int tid, int T, const double* lds)
 {
     const PlantStepArgs& P = Q.s;
     const int nx = P.nx, ny = Q.ny, b0 = wg * P.group;
     const int cnt = (P.batch - b0 < P.group) ? P.batch - b0 : P.group;
     if (cnt <= 0) return;
-    const PlantObsLds E = plant_obs_lds(Q);
+    const PlantObsLds E = plant_obs_lds<kNoise>(Q);
     for (int e = tid; e < cnt * nx; e += T) {
         const int i = e / nx, r = e - i * nx;
         const int g = Q.gain_shared ? 0 : i * nx * ny;
@@ -544,38 +581,50 @@ COPRA_DEV void plant_obs_update(const PlantObsArgs& Q, int wg, int tid, int T, c
 
 #if defined(__HIPCC__)
 constexpr int kPlantThreads = 256;
-template <bool kEst>
+// (kNoise: phase 1 draws the process noise -- builds of their own, so that the builds without it hold none of the generator's code)
+template <bool kEst, bool kNoise = false>
 __global__ __launch_bounds__(kPlantThreads) void copra_plant_step_kernel(const PlantStepArgs P)
 {
     extern __shared__ __align__(16) double plant_image[];
     const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
     if (!kEst) {
-        plant_stage(P, wg, tid, kPlantThreads, plant_image);
+        plant_stage<kNoise>(P, wg, tid, kPlantThreads, plant_image);
         __syncthreads();
-        plant_apply(P, wg, tid, kPlantThreads, plant_image);
+        plant_apply<kNoise>(P, wg, tid, kPlantThreads, plant_image);
         return;
     }
-    plant_stage_est(P, wg, tid, kPlantThreads, plant_image);
+    plant_stage_est<kNoise>(P, wg, tid, kPlantThreads, plant_image);
     __syncthreads();
-    plant_apply_est(P, wg, tid, kPlantThreads, plant_image);
+    plant_apply_est<kNoise>(P, wg, tid, kPlantThreads, plant_image);
     __syncthreads();
-    plant_estimate(P, wg, tid, kPlantThreads, plant_image);
+    plant_estimate<kNoise>(P, wg, tid, kPlantThreads, plant_image);
     __syncthreads();
-    plant_estimate_store(P, wg, tid, kPlantThreads, plant_image);
+    plant_estimate_store<kNoise>(P, wg, tid, kPlantThreads, plant_image);
 }
 
 // the third build: the tick with the state observer (its arguments carry the tick's own as their first member)
+template <bool kNoise>
+__device__ __forceinline__ void plant_observer_tick(const PlantObsArgs& Q, double* image)
+{
+    const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
+    plant_obs_stage<kNoise>(Q, wg, tid, kPlantThreads, image);
+    __syncthreads();
+    plant_obs_apply<kNoise>(Q, wg, tid, kPlantThreads, image);
+    __syncthreads();
+    plant_obs_innovate<kNoise>(Q, wg, tid, kPlantThreads, image);
+    __syncthreads();
+    plant_obs_update<kNoise>(Q, wg, tid, kPlantThreads, image);
+}
 __global__ __launch_bounds__(kPlantThreads) void copra_plant_observer_kernel(const PlantObsArgs Q)
 {
     extern __shared__ __align__(16) double plant_image[];
-    const int wg = (int)blockIdx.x, tid = (int)threadIdx.x;
-    plant_obs_stage(Q, wg, tid, kPlantThreads, plant_image);
-    __syncthreads();
-    plant_obs_apply(Q, wg, tid, kPlantThreads, plant_image);
-    __syncthreads();
-    plant_obs_innovate(Q, wg, tid, kPlantThreads, plant_image);
-    __syncthreads();
-    plant_obs_update(Q, wg, tid, kPlantThreads, plant_image);
+    plant_observer_tick<false>(Q, plant_image);
+}
+// ... and its build that draws process and sensor noise in phase 1
+__global__ __launch_bounds__(kPlantThreads) void copra_plant_observer_noise_kernel(const PlantObsArgs Q)
+{
+    extern __shared__ __align__(16) double plant_image[];
+    plant_observer_tick<true>(Q, plant_image);
 }
 #endif
 

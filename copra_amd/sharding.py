@@ -13,6 +13,16 @@ def shard_range(total, rank, world):
     return lo, hi
 
 
+def set_shard_noise(controller, total, rank, world, seed, process=None, sensor=None):
+    """BatchLMPC.set_noise for the controller of `rank`'s shard of a batch of `total`: the shard's first global index becomes first_instance,
+    so that instance lo + b of the whole batch draws the same noise on whichever rank it lives; standard deviations given per instance of
+    the WHOLE batch, (total, rows), are cut to the shard's rows"""
+    lo, hi = shard_range(total, rank, world)
+    cut = lambda a: a if a is None or len(a.shape) == 1 else a[lo:hi]  # noqa: E731
+    controller.set_noise(seed, process=cut(process), sensor=cut(sensor), first_instance=lo)
+    return lo, hi
+
+
 def slab_layout(batch, n, X):
     """byte offsets of the four result arrays inside one flat slab (all 8-byte aligned): [U | status | iter | X].  The
     trajectory comes LAST so that the head of the slab -- controls, status, iteration counts: 492 of the 1500 bytes per instance at

@@ -524,6 +524,48 @@ copra_status_t copra_batch_set_plant_state(copra_batch_t* h, const double* x, in
 const double* copra_batch_plant_state_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_plant_state(copra_batch_t* h, double* x);
 
+/* ---- Monte-Carlo ticks: process and sensor noise drawn on the device (ABI 13).  w and v above are arrays the caller fills; a rollout of
+ *      many ticks needs [ticks][batch][nx] of them, and a C caller has no generator.  copra_batch_set_noise makes the plant step draw them
+ *      itself, inside its launch, from a counter-based generator -- Philox4x32-10 -- so that the draw of instance b at noise tick t depends
+ *      on (seed, first_instance + b, stream, row, t) and on nothing else: not on the batch, the launch, or the GPU a shard of a larger
+ *      batch runs on, and the same seed gives the same noise to every controller variant (common random numbers).  It costs no memory.
+ *      Rows 2j and 2j + 1 of instance b share one call; stream s is 0 for process noise w, 1 for sensor noise v:
+ *        key     = (seed & 0xffffffff, seed >> 32)
+ *        counter = ((first_instance + b) & 0xffffffff, (s << 16) | j, t & 0xffffffff, t >> 32)        -> words o0 .. o3
+ *        u1 = (((o0 << 32 | o1) >> 12) + 0.5) 2^-52,  u2 likewise from (o2, o3);   rad = sqrt(-2 log u1),  ang = 6.283185307179586 u2
+ *        n[2j] = rad cos ang,  n[2j + 1] = rad sin ang          (an odd number of rows drops the last sin)
+ *      The noise term of row r is sigma[r] n[r], rounded once; the tick uses w = term where the step gives no w and w = w_given + term
+ *      where it does (w_seq of a rollout included), and v likewise.  With y_meas no v exists and none is drawn.  An instance whose state
+ *      is held shows no process noise; draws are indexed by tick, so no other draw moves.
+ *      copra_batch_set_noise(h, noise): sigma_w is [nx] or, with per_instance != 0, [batch][nx]; sigma_v [ny] or [batch][ny] (one flag
+ *      for both).  Host arrays are copied (the call synchronises the stream of the last solve / tick once), device arrays (on_device != 0)
+ *      are used in place and must stay valid.  noise == NULL or both sigmas NULL: off.  first_instance is the global index of this
+ *      handle's instance 0 where a batch is spread over several handles; first_instance + batch <= 2^32.
+ *      The handle keeps a NOISE TICK of its own, apart from the schedule tick (replicas share schedules, not seeds): every plant step --
+ *      copra_batch_advance, every tick of copra_batch_rollout, with or without a solve -- adds one; copra_batch_set_noise sets it to 0,
+ *      copra_batch_noise_seek to `tick`; copra_batch_set_x0, copra_batch_set_system and the schedule calls leave it alone.
+ *      copra_batch_draw_noise writes the terms of one tick and one stream (0: process, 1: sensor) to out_device, [batch][nx] or [batch][ny],
+ *      on hip_stream: bit for bit what the plant step of that noise tick adds.  The tick neither synchronises nor allocates for the noise.
+ *      Turning the observer off while sigma_v is set drops the sensor noise; turning it on again with another ny returns
+ *      COPRA_ERR_RUNTIME until copra_batch_set_noise is called again.
+ *      COPRA_ERR_ARG: a NULL handle; a negative or NaN sigma in a host array; first_instance + batch > 2^32; a stream outside {0, 1}; a
+ *      NULL out_device.  COPRA_ERR_RUNTIME: sigma_v, or stream 1, while the observer is off; copra_batch_draw_noise for a stream whose
+ *      sigma is not set.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller. ---- */
+typedef struct {
+    int struct_size; /* append-only, set by copra_noise_init */
+    unsigned long long seed;
+    unsigned long long first_instance; /* global index of this handle's instance 0 (shards) */
+    const double* sigma_w; /* [nx] or [batch][nx]; NULL: no process noise */
+    const double* sigma_v; /* [ny] or [batch][ny]; NULL: no sensor noise */
+    int per_instance; /* one flag for both */
+    int on_device; /* used in place, must stay valid; else copied */
+} copra_noise_t;
+void copra_noise_init(copra_noise_t* noise);
+copra_status_t copra_batch_set_noise(copra_batch_t* h, const copra_noise_t* noise);
+copra_status_t copra_batch_noise_seek(copra_batch_t* h, unsigned long long tick);
+unsigned long long copra_batch_noise_tick(const copra_batch_t* h);
+copra_status_t copra_batch_draw_noise(copra_batch_t* h, unsigned long long tick, int stream, double* out_device, void* hip_stream);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
