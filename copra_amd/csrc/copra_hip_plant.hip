@@ -20,10 +20,6 @@
 
 namespace {
 
-constexpr size_t kPlantLdsTarget = 24 * 1024; // a group's image: small enough for several workgroups per CU
-constexpr size_t kPlantLdsMax = 160 * 1024; // one instance's image at most (the CU's LDS)
-constexpr int kPlantGroupMax = 32;
-
 // the caller's struct as THIS library knows it -- the widest form, copra_plant_step_obs_t, whose first bytes are the struct a caller of ABI 10
 // (copra_plant_step_t) or ABI 11 (copra_plant_step_ex_t) passes: fields beyond the caller's struct_size keep their defaults (all zero)
 copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_obs_t& wide, const char* who)
@@ -143,28 +139,6 @@ copra_status_t own_schedule(LimitSchedule& ls, const double* sched, size_t count
     return COPRA_OK;
 }
 
-// instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes;
-// `one` is one instance's image in bytes
-int plant_group(size_t one)
-{
-    int group = (int)(kPlantLdsTarget / one);
-    group = group > kPlantGroupMax ? kPlantGroupMax : group < 1 ? 1 : group;
-    if (group > 1) group &= ~1;
-    return group;
-}
-
-// one instance's image with the disturbance estimator, in bytes: the widest the tick can ask for with this gain (a plant of its own, w, ages)
-size_t bias_image_bytes(int nx, int nu, int dense)
-{
-    return (size_t)plant_est_lds(nx, nu, 1, 0, 1, 1, 0, dense, 0).total * sizeof(double);
-}
-
-// ... and with the observer: the widest the tick can ask for at this ny (a plant of its own, w, ages, Ld, per-instance gains, v)
-size_t observer_image_bytes(int nx, int nu, int ny)
-{
-    return (size_t)plant_obs_lds(nx, nu, ny, 1, 0, 1, 1, 0, 0, 1, 0, 1).total * sizeof(double);
-}
-
 // what one tick reads and writes beside the step's plant: the step's own pointers, or a rollout's rows of tick t
 struct TickIO {
     const double* w;
@@ -279,7 +253,7 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
         P.gain_dense = h->bias_dense, P.gain_shared = !h->bias_per_instance;
         P.d_out = d_out;
     }
-    const size_t one = P.est ? bias_image_bytes(P.nx, P.nu, P.gain_dense) : (size_t)plant_lds(P.nx, P.nu, 1, 0, 1).total * sizeof(double);
+    const size_t one = P.est ? bias_image_bytes(P.nx, P.nu, P.gain_dense) : plant_image_bytes(P.nx, P.nu); // (the geometry: plant_step.hpp)
     if (one > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's plant does not fit the LDS (xDim beyond about 130)");
     const int group = plant_group(one);
     P.group = group;

@@ -466,6 +466,39 @@ COPRA_DEV PlantObsLds plant_obs_lds(const PlantObsArgs& Q)
         Q.gain_shared, plant_obs_has_yv<kNoise>(Q));
 }
 
+// ---- the launch geometry (host): what copra_hip_plant.hip sizes every build's grid and image with, and what tests/emu asks ----
+constexpr size_t kPlantLdsTarget = 24 * 1024; // a group's image: small enough for several workgroups per CU
+constexpr size_t kPlantLdsMax = 160 * 1024; // one instance's image at most (the CU's LDS)
+constexpr int kPlantGroupMax = 32;
+
+// instances per workgroup: an image of about kPlantLdsTarget bytes, an even number of instances so that every group starts on 16 bytes;
+// `one` is one instance's image in bytes
+inline int plant_group(size_t one)
+{
+    int group = (int)(kPlantLdsTarget / one);
+    group = group > kPlantGroupMax ? kPlantGroupMax : group < 1 ? 1 : group;
+    if (group > 1) group &= ~1;
+    return group;
+}
+
+// one instance's image of the plain tick, in bytes: the widest the tick can ask for (a plant of its own, w, ages)
+inline size_t plant_image_bytes(int nx, int nu)
+{
+    return (size_t)plant_lds(nx, nu, 1, 0, 1, 1).total * sizeof(double);
+}
+
+// ... with the disturbance estimator: the widest the tick can ask for with this gain (a plant of its own, w, ages)
+inline size_t bias_image_bytes(int nx, int nu, int dense)
+{
+    return (size_t)plant_est_lds(nx, nu, 1, 0, 1, 1, 0, dense, 0).total * sizeof(double);
+}
+
+// ... and with the observer: the widest the tick can ask for at this ny (a plant of its own, w, ages, Ld, per-instance gains, v)
+inline size_t observer_image_bytes(int nx, int nu, int ny)
+{
+    return (size_t)plant_obs_lds(nx, nu, ny, 1, 0, 1, 1, 0, 0, 1, 0, 1).total * sizeof(double);
+}
+
 // phase 1: the image of the tick, then what the observer reads beside it
 template <bool kNoise = false>
 COPRA_DEV void plant_obs_stage(const PlantObsArgs& Q, int wg, int tid, int T, double* lds)

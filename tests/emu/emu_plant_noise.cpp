@@ -4,43 +4,44 @@
 // phases, over an image filled with NaN.  Beside it the body of the fill kernel, and the generator itself.  Compiled by
 // tests/test_noise_abi.py: g++ -shared for ctypes, and with tests/emu/emu_plant_noise_main.cpp as a stand-alone program.
 #include "emu_plant_noise.h"
-
-#include <cstdlib>
-#include <limits>
+#include "emu_walk.h"
 
 using namespace copra_hip;
 
 namespace {
 
 template <bool kNoise>
-void walk(const EmuNoiseTick& t, const PlantStepArgs& P, const PlantObsArgs& Q, double* lds, size_t total)
+int walk(const EmuNoiseTick& t, const PlantStepArgs& P, const PlantObsArgs& Q, emu::Image& img, int order, unsigned long long seed)
 {
     const int grid = (P.batch + P.group - 1) / P.group, T = t.threads;
-    for (int wg = 0; wg < grid; ++wg) {
-        for (size_t i = 0; i < total; ++i) lds[i] = std::numeric_limits<double>::quiet_NaN(); // (LDS is not initialised: whatever is read must have been staged)
-        if (t.build == 0) {
-            for (int tid = 0; tid < T; ++tid) plant_stage<kNoise>(P, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_apply<kNoise>(P, wg, tid, T, lds);
-        } else if (t.build == 1) {
-            for (int tid = 0; tid < T; ++tid) plant_stage_est<kNoise>(P, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_apply_est<kNoise>(P, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_estimate<kNoise>(P, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_estimate_store<kNoise>(P, wg, tid, T, lds);
-        } else {
-            for (int tid = 0; tid < T; ++tid) plant_obs_stage<kNoise>(Q, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_obs_apply<kNoise>(Q, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_obs_innovate<kNoise>(Q, wg, tid, T, lds);
-            for (int tid = 0; tid < T; ++tid) plant_obs_update<kNoise>(Q, wg, tid, T, lds);
-        }
-    }
+    double* const lds = img.lds;
+    if (t.build == 0)
+        return emu::walk(img, grid, 2, T, order, seed, [&](int wg, int ph, int tid) {
+            if (ph == 0) plant_stage<kNoise>(P, wg, tid, T, lds);
+            else plant_apply<kNoise>(P, wg, tid, T, lds);
+        });
+    if (t.build == 1)
+        return emu::walk(img, grid, 4, T, order, seed, [&](int wg, int ph, int tid) {
+            if (ph == 0) plant_stage_est<kNoise>(P, wg, tid, T, lds);
+            else if (ph == 1) plant_apply_est<kNoise>(P, wg, tid, T, lds);
+            else if (ph == 2) plant_estimate<kNoise>(P, wg, tid, T, lds);
+            else plant_estimate_store<kNoise>(P, wg, tid, T, lds);
+        });
+    return emu::walk(img, grid, 4, T, order, seed, [&](int wg, int ph, int tid) {
+        if (ph == 0) plant_obs_stage<kNoise>(Q, wg, tid, T, lds);
+        else if (ph == 1) plant_obs_apply<kNoise>(Q, wg, tid, T, lds);
+        else if (ph == 2) plant_obs_innovate<kNoise>(Q, wg, tid, T, lds);
+        else plant_obs_update<kNoise>(Q, wg, tid, T, lds);
+    });
 }
 
 } // namespace
 
 extern "C" {
 
-// Returns 0; -1: no memory
-int emu_plant_noise_tick(EmuNoiseTick* t)
+// Returns 0; -1: no memory; -2: the guard behind the image was written.  order, seed: the walk order of emu_walk.h; vec2_used (may be null)
+// says whether the walk copied two doubles per lane.
+int emu_plant_noise_tick_walk(EmuNoiseTick* t, int order, unsigned long long seed, int* vec2_used)
 {
     PlantObsArgs Q {};
     PlantStepArgs& P = Q.s;
@@ -78,13 +79,14 @@ int emu_plant_noise_tick(EmuNoiseTick* t)
             Q.gain_shared, plant_obs_has_yv(Q)).total;
     }
     t->lds_doubles = (int)total;
-    double* lds = static_cast<double*>(std::aligned_alloc(16, (total * sizeof(double) + 15) / 16 * 16));
-    if (!lds) return -1;
-    if (t->knoise) walk<true>(*t, P, Q, lds, total);
-    else walk<false>(*t, P, Q, lds, total);
-    std::free(lds);
-    return 0;
+    if (vec2_used) *vec2_used = P.vec2;
+    emu::Image img(total);
+    if (!img.lds) return emu::kEmuNoMemory;
+    return t->knoise ? walk<true>(*t, P, Q, img, order, seed) : walk<false>(*t, P, Q, img, order, seed);
 }
+
+// ... every phase and the grid walked in ascending order
+int emu_plant_noise_tick(EmuNoiseTick* t) { return emu_plant_noise_tick_walk(t, 0, 0, nullptr); }
 
 // the fill kernel's body over its grid: out[batch][rows]
 void emu_noise_fill(int batch, int rows, int stream, int per_instance, int group, int threads, unsigned long long seed, unsigned long long first,

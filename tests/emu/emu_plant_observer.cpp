@@ -3,10 +3,7 @@
 // workgroup's threads one after the other through phase 1, then -- a barrier each -- through phases 2, 3 and 4, over an image filled with
 // NaN.  Compiled by tests/test_observer_abi.py itself: g++ -shared for ctypes, and with tests/emu/emu_plant_observer_main.cpp as a
 // stand-alone program.
-#include "../../copra_amd/csrc/plant_step.hpp"
-
-#include <cstdlib>
-#include <limits>
+#include "emu_walk.h"
 
 using namespace copra_hip;
 
@@ -38,8 +35,8 @@ struct EmuObserverTick {
     int vec2_mode, vec2_used;
 };
 
-// Returns 0; -1: no memory
-int emu_plant_observer_step(EmuObserverTick* t)
+// Returns 0; -1: no memory; -2: the guard behind the image was written.  order, seed: the walk order of emu_walk.h.
+int emu_plant_observer_step_walk(EmuObserverTick* t, int order, unsigned long long seed)
 {
     PlantObsArgs Q {};
     PlantStepArgs& P = Q.s;
@@ -62,19 +59,20 @@ int emu_plant_observer_step(EmuObserverTick* t)
     t->vec2_used = P.vec2;
     const size_t total = (size_t)plant_obs_lds(P.nx, P.nu, Q.ny, P.group, P.shared, P.w != nullptr, P.backup_steps > 0, Q.same_model, Q.meas, Q.Ld != nullptr,
         Q.gain_shared, Q.yv != nullptr).total;
-    double* lds = static_cast<double*>(std::aligned_alloc(16, (total * sizeof(double) + 15) / 16 * 16));
-    if (!lds) return -1;
-    const int grid = (P.batch + P.group - 1) / P.group, T = t->threads;
-    for (int wg = 0; wg < grid; ++wg) {
-        for (size_t i = 0; i < total; ++i) lds[i] = std::numeric_limits<double>::quiet_NaN(); // (LDS is not initialised: whatever is read must have been staged)
-        for (int tid = 0; tid < T; ++tid) plant_obs_stage(Q, wg, tid, T, lds);
-        for (int tid = 0; tid < T; ++tid) plant_obs_apply(Q, wg, tid, T, lds);
-        for (int tid = 0; tid < T; ++tid) plant_obs_innovate(Q, wg, tid, T, lds);
-        for (int tid = 0; tid < T; ++tid) plant_obs_update(Q, wg, tid, T, lds);
-    }
-    std::free(lds);
-    return 0;
+    emu::Image img(total);
+    if (!img.lds) return emu::kEmuNoMemory;
+    double* const lds = img.lds;
+    const int T = t->threads;
+    return emu::walk(img, (P.batch + P.group - 1) / P.group, 4, T, order, seed, [&](int wg, int ph, int tid) {
+        if (ph == 0) plant_obs_stage(Q, wg, tid, T, lds);
+        else if (ph == 1) plant_obs_apply(Q, wg, tid, T, lds);
+        else if (ph == 2) plant_obs_innovate(Q, wg, tid, T, lds);
+        else plant_obs_update(Q, wg, tid, T, lds);
+    });
 }
+
+// ... every phase and the grid walked in ascending order
+int emu_plant_observer_step(EmuObserverTick* t) { return emu_plant_observer_step_walk(t, 0, 0); }
 
 // the image in doubles, as the launch sizes it
 int emu_plant_observer_lds_doubles(int nx, int nu, int ny, int group, int shared, int has_w, int backup, int same_model, int meas, int has_Ld, int gain_shared,

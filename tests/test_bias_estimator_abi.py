@@ -159,7 +159,6 @@ def test_python_binding_has_the_estimator():
 # ---- the kernel bodies on the host ----
 VP, CI = ctypes.c_void_p, ctypes.c_int
 STEP_ARGS = [CI] * 7 + [VP] * 13 + [CI, CI] + [VP] * 3 + [CI] * 3 + [VP] * 5 + [CI]
-LDS_TARGET, GROUP_MAX = 24 * 1024, 32  # kPlantLdsTarget, kPlantGroupMax of copra_hip_plant.hip
 
 
 @pytest.fixture(scope="module")
@@ -171,6 +170,8 @@ def emu(tmp_path_factory):
     lib.emu_plant_bias_step.argtypes = STEP_ARGS
     lib.emu_plant_bias_lds_doubles.restype = CI
     lib.emu_plant_bias_est_doubles.restype = CI
+    lib.emu_plant_launch_group.restype = CI
+    lib.emu_plant_launch_group.argtypes = [CI] * 5
     return lib
 
 
@@ -197,10 +198,8 @@ def emu_abi9(tmp_path_factory):
 
 
 def launch_group(emu, nx, nu, dense):
-    """the group copra_hip_plant.hip launches with: from one instance's widest image with this gain"""
-    one = 8 * emu.emu_plant_bias_est_doubles(nx, nu, 1, 0, 1, 1, 0, int(dense), 0)
-    g = min(GROUP_MAX, max(1, LDS_TARGET // one))
-    return g & ~1 if g > 1 else g
+    """the group copra_hip_plant.hip launches with: plant_group(bias_image_bytes(nx, nu, dense)) of plant_step.hpp, asked of the emulator"""
+    return emu.emu_plant_launch_group(1, nx, nu, 0, int(dense))
 
 
 def _model(rng, batch, nx, nu, N=5, failed=0):

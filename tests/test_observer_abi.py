@@ -40,7 +40,6 @@ FIELDS = ["ex", "v", "y_meas", "y_out", "xhat_out", "v_seq", "y_hist", "xhat_his
 LD = np.longdouble
 U = 2.0 ** -53
 SHAPES = [(6, 3, 3), (9, 3, 3), (2, 1, 1), (3, 3, 3), (2, 1, 3)]  # (nx, nu, ny): the issue's five cases
-LDS_TARGET, GROUP_MAX = 24 * 1024, 32  # kPlantLdsTarget, kPlantGroupMax of copra_hip_plant.hip
 
 
 def _lib():
@@ -218,14 +217,14 @@ def emu(tmp_path_factory):
     lib.emu_plant_observer_step.argtypes = [ctypes.POINTER(Tick)]
     lib.emu_plant_observer_lds_doubles.restype = CI
     lib.emu_plant_observer_lds_doubles.argtypes = [CI] * 12
+    lib.emu_plant_launch_group.restype = CI
+    lib.emu_plant_launch_group.argtypes = [CI] * 5
     return lib
 
 
 def launch_group(emu, nx, nu, ny):
-    """the group copra_hip_plant.hip launches with: from one instance's widest image at this ny"""
-    one = 8 * emu.emu_plant_observer_lds_doubles(nx, nu, ny, 1, 0, 1, 1, 0, 0, 1, 0, 1)
-    g = min(GROUP_MAX, max(1, LDS_TARGET // one))
-    return g & ~1 if g > 1 else g
+    """the group copra_hip_plant.hip launches with: plant_group(observer_image_bytes(nx, nu, ny)) of plant_step.hpp, asked of the emulator"""
+    return emu.emu_plant_launch_group(2, nx, nu, ny, 0)
 
 
 def _ptr(a):
