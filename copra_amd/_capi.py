@@ -81,6 +81,35 @@ class Noise(C.Structure):
                 ("sigma_v", C.c_void_p), ("per_instance", C.c_int), ("on_device", C.c_int)]
 
 
+class Score(C.Structure):
+    """copra_score_t: the measure copra_batch_set_score scores every tick against"""
+    _fields_ = [("struct_size", C.c_int), ("qx", C.c_void_p), ("ru", C.c_void_p), ("dense", C.c_int), ("x_ref", C.c_void_p),
+                ("ref_steps", C.c_longlong), ("x_lo", C.c_void_p), ("x_hi", C.c_void_p), ("u_lo", C.c_void_p), ("u_hi", C.c_void_p),
+                ("tol", C.c_double), ("per_instance", C.c_int), ("on_device", C.c_int)]
+
+
+class ScoreRecord(C.Structure):
+    """copra_score_record_t: 64 bytes per instance"""
+    _fields_ = ([(n, C.c_double) for n in ("jx", "ju", "viol_sum", "viol_max", "peak")]
+                + [(n, C.c_int) for n in ("ticks", "held", "replayed", "fallback", "violating", "first_violation")])
+
+
+SCORE_RECORD_DTYPE = np.dtype([(n, "f8") for n in ("jx", "ju", "viol_sum", "viol_max", "peak")]
+                              + [(n, "i4") for n in ("ticks", "held", "replayed", "fallback", "violating", "first_violation")])
+
+
+class ScoreStat(C.Structure):
+    """copra_score_stat_t: one double field of the records over the batch"""
+    _fields_ = [("n", C.c_longlong), ("mean", C.c_double), ("m2", C.c_double), ("min", C.c_double), ("max", C.c_double),
+                ("argmin", C.c_longlong), ("argmax", C.c_longlong)]
+
+
+class ScoreSummary(C.Structure):
+    """copra_score_summary_t: what copra_batch_score_summary reduces the records to"""
+    _fields_ = ([(n, ScoreStat) for n in ("jx", "ju", "viol_sum", "viol_max", "peak")]
+                + [(n, C.c_longlong) for n in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")])
+
+
 PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
@@ -411,6 +440,18 @@ def lib():
         L.copra_batch_noise_tick.argtypes = [vp]
         L.copra_batch_draw_noise.restype = C.c_int
         L.copra_batch_draw_noise.argtypes = [vp, C.c_ulonglong, C.c_int, vp, vp]
+        L.copra_score_init.restype = None
+        L.copra_score_init.argtypes = [C.POINTER(Score)]
+        L.copra_batch_set_score.restype = C.c_int
+        L.copra_batch_set_score.argtypes = [vp, C.POINTER(Score)]
+        L.copra_batch_score_reset.restype = C.c_int
+        L.copra_batch_score_reset.argtypes = [vp]
+        L.copra_batch_score_device.restype = vp
+        L.copra_batch_score_device.argtypes = [vp]
+        L.copra_batch_get_score.restype = C.c_int
+        L.copra_batch_get_score.argtypes = [vp, vp]
+        L.copra_batch_score_summary.restype = C.c_int
+        L.copra_batch_score_summary.argtypes = [vp, C.POINTER(ScoreSummary)]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

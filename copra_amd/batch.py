@@ -607,6 +607,124 @@ class BatchLMPC:
         _capi.check(self._lib.copra_batch_draw_noise(self._h, int(tick), 0 if stream == "process" else 1, ptr, C.c_void_p(hip_stream or 0)))
         return t
 
+    # ---- closed-loop scores (copra_batch_set_score, ABI 14): the tick keeps one record per instance on the device ----
+    def set_score(self, state_weights=None, control_weights=None, state_ref=None, state_limits=None, control_limits=None, tol=0.0):
+        """Closed-loop scores (copra_batch_set_score): from now on every advance() / tick of rollout() updates one record per instance on the
+        device -- jx += e' Qx e with e = x - state_ref at the schedule tick, ju += u' Ru u, the violations of the box limits on the true state
+        and the applied control, the ticks held / replayed / on the fallback -- so a closed-loop study needs no x_hist / u_hist.
+        state_weights: (nx,) diagonal or (nx, nx) dense, or with a leading batch axis one per instance (a 2-d array with batch == nx is read
+        as (nx, nx)); control_weights likewise with nu; one of them dense makes both dense.  state_ref: (nx,) a constant goal, (steps, nx) a
+        signal read at min(schedule_tick, steps - 1), (batch, steps, nx) one per instance.  state_limits / control_limits: (lower, upper),
+        each (nx,) / (nu,) or with a leading batch axis, or None; infinite entries are allowed.  tol: a tick counts as violating when its
+        largest violation exceeds it.  A mix of shared and per-instance arrays is written out per instance here.  numpy: natural indexing,
+        copied; torch CUDA float64 tensors (all of them then, all shared or all per instance, dense weights in the ABI's column-major):
+        used in place and kept alive.  Zeroes the records.  Every argument None (set_score(None)): scoring ends."""
+        xl, xh = state_limits if state_limits is not None else (None, None)
+        ul, uh = control_limits if control_limits is not None else (None, None)
+        given = dict(qx=state_weights, ru=control_weights, x_ref=state_ref, x_lo=xl, x_hi=xh, u_lo=ul, u_hi=uh)
+        if all(v is None for v in given.values()):
+            _capi.check(self._lib.copra_batch_set_score(self._h, None))
+            self._score_keep = None
+            return
+        b, nx, nu = self.batch, self.nx, self.nu
+        torch_in = any(_is_torch(v) for v in given.values())
+        if torch_in:
+            for v in given.values():
+                if v is not None and not (_is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float64"):
+                    raise ValueError("set_score: contiguous CUDA float64 tensors are needed (all arrays numpy, or all tensors)")
+            arrs = dict(given)
+        else:
+            arrs = {k: (None if v is None else np.asarray(v, dtype=np.float64)) for k, v in given.items()}
+        rows = dict(qx=nx, ru=nu, x_lo=nx, x_hi=nx, u_lo=nu, u_hi=nu)
+        dense, per, steps = False, False, 1
+        kind = {}  # name -> (dense, per instance)
+        for k, a in arrs.items():
+            if a is None:
+                continue
+            sh = tuple(a.shape)
+            if k == "x_ref":
+                if len(sh) == 1 and sh == (nx,):
+                    kind[k] = (False, False)
+                elif len(sh) == 2 and sh[1] == nx and sh[0] >= 1:
+                    kind[k], steps = (False, False), sh[0]
+                elif len(sh) == 3 and sh[0] == b and sh[2] == nx and sh[1] >= 1:
+                    kind[k], steps = (False, True), sh[1]
+                else:
+                    raise _capi.CopraDomainError("set_score: state_ref of shape (%d,), (steps, %d) or (%d, steps, %d) expected, got %s" % (nx, nx, b, nx, sh))
+                continue
+            r = rows[k]
+            weight = k in ("qx", "ru")
+            if sh == (r,):
+                kind[k] = (False, False)
+            elif weight and sh == (r, r):
+                kind[k] = (True, False)
+            elif sh == (b, r):
+                kind[k] = (False, True)
+            elif weight and sh == (b, r, r):
+                kind[k] = (True, True)
+            else:
+                raise _capi.CopraDomainError("set_score: %s has shape %s" % (k, sh))
+        dense = any(d for d, _ in kind.values())
+        per = any(p for _, p in kind.values())
+        if torch_in:
+            if any(p != per for _, p in kind.values()) or any(d != dense for k, (d, _) in kind.items() if k in ("qx", "ru")):
+                raise ValueError("set_score: tensors are used in place -- all shared or all per instance, both weights diagonal or both dense")
+            ptrs = {k: (None if a is None else a.data_ptr()) for k, a in arrs.items()}
+            keep = [a for a in arrs.values() if a is not None]
+        else:
+            keep = []
+            ptrs = {}
+            for k, a in arrs.items():
+                if a is None:
+                    ptrs[k] = None
+                    continue
+                d, p = kind[k]
+                if k in ("qx", "ru"):
+                    if dense and not d:  # a diagonal beside a dense weight: written out
+                        a = a[..., None] * np.eye(a.shape[-1])
+                    elif dense:
+                        a = np.swapaxes(a, -1, -2)  # natural indexing -> the ABI's column-major blocks
+                elif k == "x_ref" and a.ndim == 1:
+                    a = a[None, :]
+                if per and not p:
+                    a = np.broadcast_to(a, (b,) + a.shape)
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                keep.append(a)
+                ptrs[k] = a.ctypes.data
+        m = _capi.Score()
+        self._lib.copra_score_init(C.byref(m))
+        m.qx, m.ru, m.x_ref, m.x_lo, m.x_hi, m.u_lo, m.u_hi = (ptrs[k] for k in ("qx", "ru", "x_ref", "x_lo", "x_hi", "u_lo", "u_hi"))
+        m.dense, m.per_instance, m.on_device = int(dense), int(per), int(torch_in)
+        m.ref_steps, m.tol = int(steps), float(tol)
+        _capi.check(self._lib.copra_batch_set_score(self._h, C.byref(m)))
+        self._score_keep = keep if torch_in else None
+
+    def reset_score(self):
+        """zero the records, in stream order behind the last tick (copra_batch_score_reset): a new episode"""
+        _capi.check(self._lib.copra_batch_score_reset(self._h))
+
+    def score(self):
+        """the records, one per instance, as a numpy structured array (_capi.SCORE_RECORD_DTYPE: jx, ju, viol_sum, viol_max, peak, ticks, held,
+        replayed, fallback, violating, first_violation); waits for the last tick (copra_batch_get_score)"""
+        out = np.zeros(self.batch, dtype=_capi.SCORE_RECORD_DTYPE)
+        _capi.check(self._lib.copra_batch_get_score(self._h, out.ctypes.data))
+        return out
+
+    @property
+    def score_ptr(self):
+        """device pointer of the records (copra_batch_score_device); 0 while scoring is off"""
+        return int(self._lib.copra_batch_score_device(self._h) or 0)
+
+    def score_summary(self):
+        """the records reduced over the batch on the device (copra_batch_score_summary; waits for the last tick): for jx, ju, viol_sum, viol_max
+        and peak a dict(n, mean, m2, min, max, argmin, argmax) over the finite values (variance = m2 / (n - 1)); the totals ticks, held,
+        replayed, fallback, violating; instances_violating and instances_held.  The same records give the same bits."""
+        s = _capi.ScoreSummary()
+        _capi.check(self._lib.copra_batch_score_summary(self._h, C.byref(s)))
+        out = {f: {k: getattr(getattr(s, f), k) for k, _ in _capi.ScoreStat._fields_} for f in ("jx", "ju", "viol_sum", "viol_max", "peak")}
+        out.update({k: int(getattr(s, k)) for k in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")})
+        return out
+
     def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None, noise=None,
                     y_meas=None, y_out=None, xhat_out=None):
         st = _capi.PlantStepObs()

@@ -10,6 +10,7 @@
 // (d_xp), the controller's x0 is the estimate, which the same launch corrects with the innovation of ny measured outputs.
 // copra_batch_set_noise / _noise_seek / _noise_tick / _draw_noise: Monte-Carlo ticks -- phase 1 of the plant step draws process and sensor
 // noise from a counter-based generator (plant_noise.hpp) at the handle's noise tick; builds of the kernels of their own, no memory.
+// copra_batch_set_score (copra_hip_score.hip): while scoring is on, advance() hands the tick's state, control and age to launch_score.
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
@@ -237,6 +238,10 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     P.u_out = u_out;
     P.status_out = status_out;
     P.age_out = age_out;
+    if (h->score_on) { // the score reads this tick's u_out / age_out: where the caller asked for none, the buffers copra_batch_set_score took
+        if (!P.u_out) P.u_out = h->d_score_u;
+        if (!P.age_out) P.age_out = h->d_score_age;
+    }
     if (h->backup_steps > 0) {
         P.backup_steps = h->backup_steps;
         P.fresh = h->plan_fresh;
@@ -282,6 +287,11 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
     h->noise_tick += 1; // (counted whether noise is drawn or not: a seek or a new copra_batch_set_noise says where the draws stand)
     h->sched_tick += 1; // time moves on for every instance, a failed one included: the next solve reads the next window
+    if (h->score_on) { // the records, against the true state: the plant's own while the observer simulates one, else the new x0 (the estimate
+        const double* const truth = h->obs_on && !io.y_meas ? (const double*)h->d_xp : h->x0; // on a y_meas tick, where no truth exists)
+        const copra_status_t rc = launch_score(h, truth, P.u_out, P.age_out, s, who);
+        if (rc != COPRA_OK) return rc;
+    }
     return write_windows(h, s, who);
 }
 

@@ -11,6 +11,8 @@
 //                          schedules, whose windows the tick moves (copra_batch_set_reference_schedule, ref_window.hpp); limit schedules
 //                          (copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule, limit_window.hpp); noise drawn in
 //                          the plant step and its fill kernel (copra_batch_set_noise, copra_batch_draw_noise, plant_noise.hpp)
+//   copra_hip_score.hip    closed-loop scores: copra_batch_set_score / _score_reset / _get_score / _score_summary and their kernels
+//                          (score_step.hpp); launch_score below is what the tick calls behind its plant step while scoring is on
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -144,6 +146,8 @@ struct LimitSchedule {
     int r = 0, S = 0, row0 = 0, offset = 0, per_instance = 0, preview = 0;
 };
 
+constexpr int kScoreArrays = 7; // the arrays of a score's measure (copra_score_t)
+
 // Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
 // from the caller or a view into an owned block.  Nothing owned refers to anything else owned, so the order of destruction is free.
 struct copra_batch {
@@ -215,6 +219,18 @@ struct copra_batch {
     int noise_per_instance = 0, noise_ny = 0; // (noise_ny: the observer's ny that noise_sv was given for)
     unsigned long long noise_seed = 0, noise_first = 0;
     unsigned long long noise_tick = 0; // plant steps since copra_batch_set_noise, or what copra_batch_noise_seek set
+    // closed-loop scores (copra_batch_set_score; copra_hip_score.hip, score_step.hpp): every buffer is taken by the setter, never by the tick
+    bool score_on = false;
+    int score_dense = 0, score_per_instance = 0;
+    long long score_ref_steps = 0;
+    double score_tol = 0.0;
+    const double* score_arr[kScoreArrays] = {}; // qx, ru, x_ref, x_lo, x_hi, u_lo, u_hi -- device: the caller's, or the copies below; null: not given
+    Dev<double> own_score_arr[kScoreArrays]; // the library's copies of host arrays
+    Dev<unsigned char> d_score; // [batch] records of 64 bytes
+    Dev<double> d_score_u; // [batch][nu]: the tick's u_out where the caller gave none ...
+    Dev<int> d_score_age; // ... and [batch] its age_out
+    Dev<unsigned char> d_score_part; // the partials of the summary's first stage, then its result
+    PinnedBuf<unsigned char> h_score_sum; // the result's way to the host
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -320,5 +336,8 @@ copra_status_t prepare_riccati(copra_batch* h);
 bool use_riccati(copra_batch* h);
 fused_kernel_t select_fused_kernel(const FusedPlan& P);
 fused_kernel_t select_tier2_kernel(const FusedPlan& P);
+// ---- copra_hip_score.hip: one tick's update of the records, on `s` behind the plant step -- x [batch][nx] the true state after the tick, u
+// [batch][nu] and age [batch] what the tick wrote as u_out / age_out; called only while h->score_on; no synchronisation, no allocation ----
+copra_status_t launch_score(copra_batch* h, const double* x, const double* u, const int* age, hipStream_t s, const char* who);
 // ---- copra_hip_jit.hip: dense-QP kernels compiled at run time for one problem size (copra_qp_dense_specialise) ----
 hipFunction_t dense_jit_lookup(int n, int lanes);

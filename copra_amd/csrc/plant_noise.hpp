@@ -135,7 +135,7 @@ COPRA_DEV void noise_fill_body(const NoiseFillArgs& F, int wg, int tid, int T)
     noise_stage(F.gen, F.stream, F.sigma, F.per_instance, nullptr, b0, cnt, F.rows, F.out + b0 * F.rows, tid, T);
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(COPRA_PLANT_PHASES_ONLY) // (a unit that wants the phase bodies alone defines it: the kernels have ONE home, copra_hip_plant.hip)
 constexpr int kNoiseFillThreads = 256;
 __global__ __launch_bounds__(kNoiseFillThreads) void copra_noise_fill_kernel(const NoiseFillArgs F)
 {

@@ -612,7 +612,7 @@ COPRA_DEV void plant_obs_update(const PlantObsArgs& Q, int wg, int tid, int T, c
     }
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(COPRA_PLANT_PHASES_ONLY) // (copra_hip_score.hip takes the phase bodies alone: the kernels have ONE home, copra_hip_plant.hip)
 constexpr int kPlantThreads = 256;
 // (kNoise: phase 1 draws the process noise -- builds of their own, so that the builds without it hold none of the generator's code)
 template <bool kEst, bool kNoise = false>

@@ -23,6 +23,55 @@ def set_shard_noise(controller, total, rank, world, seed, process=None, sensor=N
     return lo, hi
 
 
+SCORE_FIELDS = ("jx", "ju", "viol_sum", "viol_max", "peak")
+SCORE_TOTALS = ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")
+
+
+def _merge_score_stat(a, b):
+    """the pairwise update of copra_batch_score_summary (include/copra_hip.h), on the host: a, then b; args are global indices already"""
+    import numpy as np
+    if b["n"] == 0:
+        return dict(a)
+    if a["n"] == 0:
+        return dict(b)
+    na, nb, n = np.float64(a["n"]), np.float64(b["n"]), np.float64(a["n"] + b["n"])
+    delta = np.float64(b["mean"]) - np.float64(a["mean"])
+    bmin = b["min"] < a["min"] or (b["min"] == a["min"] and b["argmin"] < a["argmin"])
+    bmax = b["max"] > a["max"] or (b["max"] == a["max"] and b["argmax"] < a["argmax"])
+    return dict(n=a["n"] + b["n"], mean=float(np.float64(a["mean"]) + delta * nb / n),
+                m2=float(np.float64(a["m2"]) + np.float64(b["m2"]) + delta * delta * na * nb / n),
+                min=b["min"] if bmin else a["min"], max=b["max"] if bmax else a["max"],
+                argmin=b["argmin"] if bmin else a["argmin"], argmax=b["argmax"] if bmax else a["argmax"])
+
+
+def merge_score_summaries(summaries, first_instances):
+    """The summary of a batch spread over handles from the handles' own BatchLMPC.score_summary() dicts: the same merge rule as on the device,
+    applied in the order given; first_instances[k] is the global index of handle k's instance 0 and is added to its argmin / argmax (-1, no
+    finite value, stays).  Counts, min, max and args are those of one summary over the whole batch; mean and m2 agree with it to rounding."""
+    if len(summaries) != len(first_instances):
+        raise ValueError("merge_score_summaries: one first instance per summary")
+    out = None
+    for s, first in zip(summaries, first_instances):
+        cur = {k: int(s[k]) for k in SCORE_TOTALS}
+        for f in SCORE_FIELDS:
+            st = dict(s[f])
+            for arg in ("argmin", "argmax"):
+                st[arg] = int(st[arg]) + int(first) if st[arg] >= 0 else -1
+            cur[f] = st
+        if out is None:
+            out = cur
+            continue
+        merged = {k: out[k] + cur[k] for k in SCORE_TOTALS}
+        for f in SCORE_FIELDS:
+            merged[f] = _merge_score_stat(out[f], cur[f])
+        out = merged
+    if out is None:
+        inf = float("inf")
+        out = {k: 0 for k in SCORE_TOTALS}
+        out.update({f: dict(n=0, mean=0.0, m2=0.0, min=inf, max=-inf, argmin=-1, argmax=-1) for f in SCORE_FIELDS})
+    return out
+
+
 def slab_layout(batch, n, X):
     """byte offsets of the four result arrays inside one flat slab (all 8-byte aligned): [U | status | iter | X].  The
     trajectory comes LAST so that the head of the slab -- controls, status, iteration counts: 492 of the 1500 bytes per instance at

@@ -566,6 +566,102 @@ copra_status_t copra_batch_noise_seek(copra_batch_t* h, unsigned long long tick)
 unsigned long long copra_batch_noise_tick(const copra_batch_t* h);
 copra_status_t copra_batch_draw_noise(copra_batch_t* h, unsigned long long tick, int stream, double* out_device, void* hip_stream);
 
+/* ---- closed-loop scores: the tick keeps score (ABI 14).  A closed-loop study wants a few numbers per instance -- the accumulated stage
+ *      cost, how often and how badly limits were violated on the TRUE state, how many ticks were held or ran on a backup plan -- and their
+ *      distribution over the batch; taken from x_hist / u_hist they cost [ticks][batch][nx + nu] doubles and a caller without an array
+ *      library a loop on the host.  Here the caller hands the measure over once (copra_batch_set_score); every copra_batch_advance and every
+ *      tick of copra_batch_rollout then updates one 64-byte record per instance on the device, in a kernel of its own behind the plant step
+ *      on the same stream, and copra_batch_score_summary reduces the records to a few hundred bytes, reproducibly.  No history is needed.
+ *      The measure, copra_score_t (append-only, struct_size set by copra_score_init):
+ *        qx       weights of the state term: [nx] with dense == 0, [nx x nx] column-major with dense != 0; NULL: no state term
+ *        ru       weights of the control term: [nu] or [nu x nu] likewise (dense is one flag for both); NULL: none
+ *        x_ref    the reference signal of the state term, [per_instance ? batch : 1][ref_steps][nx]; NULL: zero.  ref_steps == 1: a constant
+ *                 goal.  The row read for the state after a tick is min(tau, ref_steps - 1), tau the handle's schedule tick AFTER that
+ *                 tick's tau += 1 (copra_batch_schedule_tick; copra_batch_schedule_seek moves it with the other schedules): a state at
+ *                 schedule time tau is compared with the block a reference trajectory's window shows at its step 0 at that tau.
+ *        x_lo, x_hi [nx], u_lo, u_hi [nu]   box limits, each may be NULL; infinite entries are allowed as in copra_batch_set_control_bounds
+ *        tol >= 0   a tick counts as violating when its largest violation exceeds tol
+ *        per_instance   one flag for every array: each is then given [batch] times
+ *        on_device      the arrays are used in place and must stay valid; otherwise they are copied and the stream of the last solve /
+ *                       tick is synchronised once
+ *      The update, after the plant step of a tick, for instance b.  x is the true state after the tick: the plant's xp+ while the observer
+ *      simulates a plant; the estimate xhat+ on a y_meas tick, where no truth exists; otherwise the new x0.  u is the control the tick
+ *      applied, age what age_out reports.  Rows within an instance are taken in ASCENDING order, every sum starts from 0.0:
+ *        e_r  = x_r - x_ref_r
+ *        lx   = sum_r (qx_r e_r) e_r   |   sum_r e_r (sum_j Qx[r,j] e_j)            (diagonal | dense)
+ *        lu   = sum_c (ru_c u_c) u_c   |   sum_c u_c (sum_j Ru[c,j] u_j)            where a control was applied, else 0
+ *        v_r  = max(0, lo_r - z_r, z_r - hi_r) over the rows of x, then of u (a held instance has no u rows); comparisons with `>`: a NaN
+ *               row counts 0;   vmax = max_r v_r
+ *        jx += lx;  ju += lu;  viol_sum += sum_r v_r;  viol_max = max(viol_max, vmax);  peak = max(peak, lx + lu);  ticks += 1
+ *        held += (age == COPRA_PLAN_HELD);  replayed += (age >= 1);  fallback += (age == COPRA_PLAN_FALLBACK)
+ *        if vmax > tol:  violating += 1;  if first_violation == 0: first_violation = ticks    (the 1-based tick of the first violation
+ *                                                                                               since the last reset; 0: none)
+ *      A held instance is scored on its unchanged state -- time passes and the robot sits there -- and its ju keeps its bits: the NaN its
+ *      u_out row holds is never added, by the discipline the tick has for a failed instance's control.  A NaN state or reference makes that
+ *      instance's jx NaN: defined behaviour, the summary counts it out.  peak and viol_max ignore a NaN (`>` again).
+ *      The record, copra_score_record_t: 64 bytes per instance, all-zero bytes are the initial state.
+ *      Lifetime: copra_batch_set_score takes the record buffer and zeroes it (on the stream of the last solve / tick); a call while scoring is on
+ *      replaces the measure and zeroes the records; copra_batch_set_score(h, NULL) ends scoring and releases the buffers;
+ *      copra_batch_score_reset zeroes the records in stream order -- a new episode.  copra_batch_set_x0, copra_batch_set_system, the
+ *      schedule calls, copra_batch_set_noise and copra_batch_set_backup_steps leave the records alone.  copra_batch_score_device returns the
+ *      records on the device (NULL while scoring is off); copra_batch_get_score waits for the last tick and copies [batch] records.
+ *      Scoring works with backup plans, solve_every, the estimator, the observer, noise and every schedule: they decide x, u and age, the
+ *      score only reads them.  u and age are the tick's own u_out / age_out (u_hist[t] / age_hist[t] of a rollout); where the caller gives
+ *      none the tick writes them to buffers the setter took.  The tick neither synchronises nor allocates for the score; while scoring was
+ *      never enabled the tick launches exactly what it launched in ABI 13.
+ *      The summary: copra_batch_score_summary waits for the last tick and reduces the records on the device.  For each of the five double
+ *      fields a copra_score_stat_t over the records whose field is FINITE: n, mean, m2 (the sum of squared deviations from the mean;
+ *      variance = m2 / (n - 1)), min, max, argmin, argmax (ties: the lowest index); with n == 0: mean = m2 = 0, min = +inf, max = -inf,
+ *      arg = -1.  Then the batch totals of ticks, held, replayed, fallback, violating, and instances_violating / instances_held: the number
+ *      of records whose counter is not zero -- the first is the Monte-Carlo estimate of the probability of a violation.
+ *      No floating-point atomics: partial statistics a, b are merged with the pairwise update
+ *        delta = mean_b - mean_a;  n = n_a + n_b;  mean = mean_a + delta n_b / n;  m2 = m2_a + m2_b + delta^2 n_a n_b / n
+ *      (an empty side returns the other unchanged) in an order that depends on the batch size alone, never on the grid, the occupancy or
+ *      the run, so that two summaries of the same records are equal bit for bit:
+ *        stage 1: chunk c is records [1024 c, 1024 (c + 1)), one workgroup of 256 threads each.  Thread t merges, from the empty statistic,
+ *                 records 1024 c + t, + 256, + 512, + 768 in ascending order; inside each wave of 64 lanes, for off = 32, 16, 8, 4, 2, 1,
+ *                 lane l <- merge(lane l, lane l + off); thread 0 merges the four waves in ascending order, (((w0, w1), w2), w3).
+ *        stage 2: one workgroup over the chunks' partials: thread t merges partials t, t + 256, ... in ascending order, then the same lane
+ *                 tree and fold of the waves.
+ *      COPRA_ERR_ARG: a NULL handle; ref_steps < 1 with an x_ref; a negative or NaN tol; a NaN weight or lo > hi in a host array; a NULL
+ *      destination.  COPRA_ERR_RUNTIME: reset, get or summary while scoring is not on.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC
+ *      controller, as for the tick itself; an instance whose image does not fit the LDS. ---- */
+typedef struct {
+    int struct_size; /* append-only, set by copra_score_init */
+    const double* qx; /* [nx] or [nx x nx]; NULL: no state term */
+    const double* ru; /* [nu] or [nu x nu]; NULL: no control term */
+    int dense; /* one flag for both weights */
+    const double* x_ref; /* [per_instance ? batch : 1][ref_steps][nx]; NULL: zero */
+    long long ref_steps;
+    const double* x_lo; /* [nx]; NULL: none */
+    const double* x_hi;
+    const double* u_lo; /* [nu]; NULL: none */
+    const double* u_hi;
+    double tol;
+    int per_instance; /* one flag for every array */
+    int on_device; /* used in place, must stay valid; else copied */
+} copra_score_t;
+typedef struct {
+    double jx, ju, viol_sum, viol_max, peak;
+    int ticks, held, replayed, fallback, violating, first_violation;
+} copra_score_record_t;
+typedef struct {
+    long long n;
+    double mean, m2, min, max;
+    long long argmin, argmax;
+} copra_score_stat_t;
+typedef struct {
+    copra_score_stat_t jx, ju, viol_sum, viol_max, peak;
+    long long ticks, held, replayed, fallback, violating;
+    long long instances_violating, instances_held;
+} copra_score_summary_t;
+void copra_score_init(copra_score_t* score);
+copra_status_t copra_batch_set_score(copra_batch_t* h, const copra_score_t* score);
+copra_status_t copra_batch_score_reset(copra_batch_t* h);
+const copra_score_record_t* copra_batch_score_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_score(copra_batch_t* h, copra_score_record_t* host);
+copra_status_t copra_batch_score_summary(copra_batch_t* h, copra_score_summary_t* out);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
