@@ -110,6 +110,13 @@ class ScoreSummary(C.Structure):
                 + [(n, C.c_longlong) for n in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")])
 
 
+class Target(C.Structure):
+    """copra_target_t: the controlled outputs, the setpoint signal and the driven costs of copra_batch_set_target"""
+    _fields_ = [("struct_size", C.c_int), ("nr", C.c_int), ("H", C.c_void_p), ("r", C.c_void_p), ("steps", C.c_longlong), ("offset", C.c_int),
+                ("per_instance", C.c_int), ("n_costs", C.c_int), ("cost_index", C.POINTER(C.c_int)), ("cost_rows", C.POINTER(C.c_int)),
+                ("cost_map", C.POINTER(C.c_void_p)), ("on_device", C.c_int)]
+
+
 PLAN_FALLBACK, PLAN_HELD = -1, -2  # COPRA_PLAN_FALLBACK, COPRA_PLAN_HELD: what age_out holds where no control of a plan was applied
 
 
@@ -452,6 +459,18 @@ def lib():
         L.copra_batch_get_score.argtypes = [vp, vp]
         L.copra_batch_score_summary.restype = C.c_int
         L.copra_batch_score_summary.argtypes = [vp, C.POINTER(ScoreSummary)]
+        L.copra_target_init.restype = None
+        L.copra_target_init.argtypes = [C.POINTER(Target)]
+        L.copra_batch_set_target.restype = C.c_int
+        L.copra_batch_set_target.argtypes = [vp, C.POINTER(Target)]
+        L.copra_batch_target_device.restype = vp
+        L.copra_batch_target_device.argtypes = [vp]
+        L.copra_batch_target_status_device.restype = vp
+        L.copra_batch_target_status_device.argtypes = [vp]
+        L.copra_batch_get_target.restype = C.c_int
+        L.copra_batch_get_target.argtypes = [vp, vp, vp]
+        L.copra_batch_get_cost_reference.restype = C.c_int
+        L.copra_batch_get_cost_reference.argtypes = [vp, C.c_int, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -46,6 +46,8 @@ class BatchLMPC:
         self._obs_keep, self._ny = None, 0  # ... and as the observer's C and gains (set_observer); its number of outputs, 0: off
         self._noise_keep = None  # ... and as the standard deviations of the noise drawn on the device (set_noise)
         self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
+        self._target_keep = None  # ... and as the outputs, the setpoint and the maps of the steady-state targets (set_target)
+        self._costs = list(costs)  # the cost dicts as given: set_target builds the maps [M N] of the driven costs from them
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
         self._cost_rows = [None if cc[i].kind == _capi.COST_KINDS["dense"] else int(cc[i].rows) for i in range(len(costs))]
@@ -171,13 +173,14 @@ class BatchLMPC:
         dc = np.ascontiguousarray(d, dtype=np.float64)
         _capi.check(self._lib.copra_batch_set_shared_system(self._h, Ac.ctypes.data, Bc.ctypes.data, dc.ctypes.data, 0))
         self._obs_keep, self._ny = None, 0  # (the library ends the observer)
+        self._target_keep = None  # ... and the steady-state targets
 
     def set_cost_reference(self, cost_index, p):
         """per-instance reference of cost `cost_index`: p of shape (batch, rows) (numpy, or a torch CUDA tensor used in
         place); p of shape (rows,): ONE new reference for every instance (copra_batch_set_cost_reference_all: copied); None
         restores the controller-wide reference given at creation"""
         self._ref_keep.pop(int(cost_index), None)  # one slot per cost: the previous tensor is released
-        self._sched_keep.pop(int(cost_index), None)  # (the library ends the cost's schedule)
+        self._sched_keep.pop(int(cost_index), None)  # (the library ends the cost's schedule, and takes the cost off the targets' list)
         if p is not None and getattr(p, "ndim", np.ndim(p)) == 1:
             if _is_torch(p):
                 assert p.is_cuda and p.is_contiguous() and str(p.dtype) == "torch.float64"
@@ -195,6 +198,17 @@ class BatchLMPC:
             pb = np.ascontiguousarray(p, dtype=np.float64)
             assert pb.shape[0] == self.batch
             _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), pb.ctypes.data, 0))
+
+    def cost_reference(self, cost_index):
+        """the per-instance reference of cost `cost_index` in force, (batch, rows of the cost), as a numpy copy (copra_batch_get_cost_reference:
+        waits for the last tick): what set_target, a schedule's window or set_cost_reference wrote; raises while the controller-wide
+        reference given at creation is in force"""
+        rows = self._cost_rows[int(cost_index)]
+        if rows is None:
+            raise _capi.CopraUnsupported("cost_reference: a dense (host-evaluated) cost has no reference p")
+        out = np.empty((self.batch, rows))
+        _capi.check(self._lib.copra_batch_get_cost_reference(self._h, int(cost_index), out.ctypes.data))
+        return out
 
     def set_reference_schedule(self, cost_index, schedule, rows_per_step, offset=0):
         """The reference of cost `cost_index` follows a signal (copra_batch_set_reference_schedule): schedule of shape (steps, r) -- one for the
@@ -724,6 +738,120 @@ class BatchLMPC:
         out = {f: {k: getattr(getattr(s, f), k) for k, _ in _capi.ScoreStat._fields_} for f in ("jx", "ju", "viol_sum", "viol_max", "peak")}
         out.update({k: int(getattr(s, k)) for k in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")})
         return out
+
+    # ---- steady-state targets (copra_batch_set_target, ABI 15): the references of the driven costs follow d and a setpoint ----
+    def _step_map(self, cost_index):
+        """T_c = [M_c N_c] of the step form of cost `cost_index` (natural indexing) and its rows r_c, from the dict the constructor received: a
+        per-step entry as it is; of a full-size entry (a reference trajectory: blkdiag of one block) its first block"""
+        c = self._costs[cost_index]
+        nx, nu, N = self.nx, self.nu, self.N
+        if c["kind"] == "dense":  # (no step form: the library refuses it)
+            return np.zeros((1, nx + nu)), 1
+        M = None if c.get("M") is None else np.atleast_2d(np.asarray(c["M"], dtype=np.float64))
+        Nm = None if c.get("N") is None else np.atleast_2d(np.asarray(c["N"], dtype=np.float64))
+        R = (M if M is not None else Nm).shape[0]
+        r = R
+        if M is not None and M.shape[1] != nx:
+            steps = N + 1 if c["kind"] == "trajectory" else N
+            r = R // steps if R % steps == 0 else R
+        elif Nm is not None and Nm.shape[1] != nu:
+            r = R // N if R % N == 0 else R
+        T = np.zeros((r, nx + nu))
+        if M is not None:
+            T[:, :nx] = M[:r, :nx]
+        if Nm is not None:
+            T[:, nx:] = Nm[:r, :nu]
+        return T, r
+
+    def set_target(self, outputs, setpoint=None, costs=None, offset=0):
+        """Steady-state targets (copra_batch_set_target): from now on every advance() / tick of rollout(), and set_system, set_bias and
+        schedule_seek, recompute on the device, per instance, the steady state z = [xs; us] with (A - I) xs + B us = -d and
+        outputs @ xs = setpoint, and write M xs + N us into the references of the costs in `costs` -- the references follow the model's d
+        (the estimates while the estimator or the observer's Ld is on) and the setpoint, so a constant load leaves no offset.
+        outputs: (nu, nx), the controlled outputs H, natural indexing.  setpoint: (nu,) a constant, (steps, nu) a signal read at
+        min(schedule_tick + offset, steps - 1), (batch, steps, nu) one per instance.  costs: a list of cost indices; their maps [M N] are
+        built from the cost dicts the constructor received.  numpy: copied; torch CUDA float64 tensors (outputs then in the ABI's
+        column-major, i.e. outputs.T contiguous, and the setpoint): used in place and kept alive.  An instance whose system is singular
+        keeps its references and its z (target_status() == 1).  set_cost_reference / set_reference_schedule on a driven cost takes it off
+        the list.  outputs None (set_target(None)) ends the targets and keeps the last references."""
+        if outputs is None:
+            _capi.check(self._lib.copra_batch_set_target(self._h, None))
+            self._target_keep = None
+            return
+        b, nx, nu = self.batch, self.nx, self.nu
+        if setpoint is None or costs is None:
+            raise ValueError("set_target: outputs, setpoint and costs are needed")
+        idx = [int(k) for k in costs]
+        if not 1 <= len(idx) <= 8:
+            raise ValueError("set_target: 1 .. 8 driven costs")
+        if any(k < 0 or k >= len(self._costs) for k in idx):
+            raise ValueError("set_target: no such cost")
+        torch_in = _is_torch(outputs) or _is_torch(setpoint)
+        if torch_in:
+            for v in (outputs, setpoint):
+                if not (_is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float64"):
+                    raise ValueError("set_target: contiguous CUDA float64 tensors are needed (outputs and setpoint numpy, or both tensors)")
+            Hc, sp = outputs, setpoint
+            hshape = tuple(Hc.shape)[::-1]  # (the ABI's column-major: the tensor holds outputs.T)
+        else:
+            Hn = np.asarray(outputs, dtype=np.float64)
+            hshape = tuple(Hn.shape)
+            Hc = np.ascontiguousarray(Hn.T) if Hn.ndim == 2 else Hn
+            sp = np.ascontiguousarray(setpoint, dtype=np.float64)
+        if hshape != (nu, nx):
+            raise _capi.CopraDomainError("set_target: outputs of shape (%d, %d) expected, got %s" % (nu, nx, hshape))
+        sh = tuple(sp.shape)
+        if sh == (nu,):
+            steps, per = 1, 0
+        elif len(sh) == 2 and sh[1] == nu and sh[0] >= 1:
+            steps, per = sh[0], 0
+        elif len(sh) == 3 and sh[0] == b and sh[2] == nu and sh[1] >= 1:
+            steps, per = sh[1], 1
+        else:
+            raise _capi.CopraDomainError("set_target: setpoint of shape (%d,), (steps, %d) or (%d, steps, %d) expected, got %s" % (nu, nu, b, nu, sh))
+        if int(offset) < 0:
+            raise ValueError("set_target: offset < 0")
+        maps, rows = [], []
+        for k in idx:
+            T, r = self._step_map(k)
+            maps.append(np.ascontiguousarray(T.T))  # column-major [r x n]
+            rows.append(r)
+        keep = [Hc, sp]
+        if torch_in:
+            import torch
+            maps = [torch.from_numpy(m).cuda() for m in maps]
+            mptr = [m.data_ptr() for m in maps]
+            hptr, rptr = Hc.data_ptr(), sp.data_ptr()
+        else:
+            mptr = [m.ctypes.data for m in maps]
+            hptr, rptr = Hc.ctypes.data, sp.ctypes.data
+        keep += maps
+        t = _capi.Target()
+        self._lib.copra_target_init(C.byref(t))
+        ci, cr, cm = (C.c_int * len(idx))(*idx), (C.c_int * len(idx))(*rows), (C.c_void_p * len(idx))(*mptr)
+        t.nr, t.H, t.r, t.steps, t.offset, t.per_instance = nu, hptr, rptr, int(steps), int(offset), per
+        t.n_costs, t.cost_index, t.cost_rows, t.cost_map, t.on_device = len(idx), ci, cr, cm, int(torch_in)
+        for k in idx:  # (the costs' references are the library's now)
+            self._ref_keep.pop(k, None)
+        _capi.check(self._lib.copra_batch_set_target(self._h, C.byref(t)))
+        self._target_keep = keep if torch_in else None
+
+    def target(self):
+        """the steady states z = [xs; us], (batch, nx + nu), as a numpy copy (copra_batch_get_target: waits for the last tick)"""
+        out = np.empty((self.batch, self.nx + self.nu))
+        _capi.check(self._lib.copra_batch_get_target(self._h, out.ctypes.data, None))
+        return out
+
+    def target_status(self):
+        """(batch,) int32: 1 where the last target calculation found the instance's system singular -- its references and its z kept"""
+        out = np.empty(self.batch, dtype=np.int32)
+        _capi.check(self._lib.copra_batch_get_target(self._h, None, out.ctypes.data))
+        return out
+
+    @property
+    def target_ptr(self):
+        """device pointer of the steady states (copra_batch_target_device); 0 while targets are off"""
+        return int(self._lib.copra_batch_target_device(self._h) or 0)
 
     def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None, noise=None,
                     y_meas=None, y_out=None, xhat_out=None):

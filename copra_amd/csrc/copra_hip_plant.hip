@@ -11,6 +11,8 @@
 // copra_batch_set_noise / _noise_seek / _noise_tick / _draw_noise: Monte-Carlo ticks -- phase 1 of the plant step draws process and sensor
 // noise from a counter-based generator (plant_noise.hpp) at the handle's noise tick; builds of the kernels of their own, no memory.
 // copra_batch_set_score (copra_hip_score.hip): while scoring is on, advance() hands the tick's state, control and age to launch_score.
+// copra_batch_set_target (copra_hip_target.hip): while targets are on, advance(), copra_batch_schedule_seek and copra_batch_set_bias call
+// launch_target behind what they did -- the steady states and the driven costs' references follow d and the setpoint.
 #include "engine.hpp"
 #include "limit_window.hpp"
 #include "plant_step.hpp"
@@ -292,7 +294,8 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
         const copra_status_t rc = launch_score(h, truth, P.u_out, P.age_out, s, who);
         if (rc != COPRA_OK) return rc;
     }
-    return write_windows(h, s, who);
+    const copra_status_t rc = write_windows(h, s, who);
+    return rc != COPRA_OK ? rc : launch_target(h, s, who); // (behind the plant step, which moved d, at the new tick's block of the setpoint)
 }
 
 } // namespace
@@ -455,7 +458,7 @@ copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_de
         HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a tick that still writes the estimates)
         HIP_TRY(hipMemcpy(h->d_bias, d, bytes, hipMemcpyHostToDevice));
     }
-    return COPRA_OK;
+    return launch_target(h, h->last_stream, who);
 }
 
 copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* C, const double* Lx, const double* Ld, int per_instance, int on_device)
@@ -706,6 +709,7 @@ copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_ind
     rs.r = r, rs.S = ct.prows / r, rs.offset = offset, rs.per_instance = per_instance != 0;
     if (!h->cost_p[t]) h->model_dirty = true; // shared model: c0 / C2 change
     h->cost_p[t] = h->d_cost_p[t];
+    target_drop_cost(h, t); // (a schedule on a cost the target calculation drives takes it off that list)
     return write_windows(h, h->last_stream, who);
 }
 
@@ -714,7 +718,8 @@ copra_status_t copra_batch_schedule_seek(copra_batch_t* h, long long tick)
     if (!h) return fail(COPRA_ERR_ARG, "copra_batch_schedule_seek: null handle");
     if (tick < 0) return fail(COPRA_ERR_ARG, "copra_batch_schedule_seek: negative tick");
     h->sched_tick = tick;
-    return write_windows(h, h->last_stream, "copra_batch_schedule_seek");
+    const copra_status_t rc = write_windows(h, h->last_stream, "copra_batch_schedule_seek");
+    return rc != COPRA_OK ? rc : launch_target(h, h->last_stream, "copra_batch_schedule_seek");
 }
 
 copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_index, const double* sched, long long steps, int r, int offset, int preview,

@@ -178,7 +178,8 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
         h->B = B;
         h->d = d;
         h->x0 = x0;
-        return bias_restart(h, h->last_stream); // (estimator on: the caller's d is copied, not adopted)
+        const copra_status_t rc = bias_restart(h, h->last_stream); // (estimator on: the caller's d is copied, not adopted)
+        return rc != COPRA_OK ? rc : launch_target(h, h->last_stream, "copra_batch_set_system");
     }
     const size_t nA = b * P.nx * P.nx, nB = b * P.nx * P.nu, nd = b * P.nx;
     if (!h->own_A) {
@@ -195,7 +196,8 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
     h->B = h->own_B;
     h->d = h->own_d;
     h->x0 = h->own_x0;
-    return bias_restart(h, h->last_stream);
+    const copra_status_t rc = bias_restart(h, h->last_stream);
+    return rc != COPRA_OK ? rc : launch_target(h, h->last_stream, "copra_batch_set_system"); // (targets on: the steady states of the new model)
 }
 
 } // extern "C"
@@ -251,7 +253,8 @@ copra_status_t copra_batch_set_system_rowmajor_async(copra_batch_t* h, const dou
     h->B = h->own_B;
     h->d = d; // (vectors have no layout: used in place)
     h->x0 = x0;
-    return bias_restart(h, s); // (estimator on: d is read once more, on `s`, for the copy the estimates restart from)
+    const copra_status_t rc = bias_restart(h, s); // (estimator on: d is read once more, on `s`, for the copy the estimates restart from)
+    return rc != COPRA_OK ? rc : launch_target(h, s, "copra_batch_set_system_rowmajor_async"); // (targets on: behind the transposes, on `s`)
 }
 
 int copra_batch_lanes_per_instance(const copra_batch_t* h)
@@ -270,6 +273,7 @@ copra_status_t copra_batch_set_cost_reference(copra_batch_t* h, int cost_index, 
     cost_index = h->hp.cost_slot[(size_t)cost_index]; // (dense costs are not among the kernel-evaluated terms)
     if (cost_index < 0) return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_reference: a dense (host-evaluated) cost has no reference p");
     h->ref_sched[cost_index].sched = nullptr; // (a reference given by hand ends the cost's schedule)
+    target_drop_cost(h, cost_index); // ... and takes the cost off the target calculation's list
     if ((p != nullptr) != (h->cost_p[cost_index] != nullptr)) h->model_dirty = true; // shared model: c0 / C2 change
     if (!p) { // back to the controller-wide reference given at creation
         h->cost_p[cost_index] = nullptr;
@@ -335,6 +339,7 @@ copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_ind
     double* const out = h->d_cost_p[t];
     if (p == out) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference_all: p aliases the library's buffer");
     h->ref_sched[t].sched = nullptr; // (a reference given by hand ends the cost's schedule)
+    target_drop_cost(h, t); // ... and takes the cost off the target calculation's list
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a solve that still reads the buffer)
     const double* src = p;
     if (!on_device) {

@@ -13,6 +13,9 @@
 //                          the plant step and its fill kernel (copra_batch_set_noise, copra_batch_draw_noise, plant_noise.hpp)
 //   copra_hip_score.hip    closed-loop scores: copra_batch_set_score / _score_reset / _get_score / _score_summary and their kernels
 //                          (score_step.hpp); launch_score below is what the tick calls behind its plant step while scoring is on
+//   copra_hip_target.hip   steady-state targets: copra_batch_set_target / _target_device / _target_status_device / _get_target and their
+//                          kernel (target_step.hpp); launch_target below is what the tick and the setters that move d, the setpoint's
+//                          block or the model call while targets are on
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -147,6 +150,7 @@ struct LimitSchedule {
 };
 
 constexpr int kScoreArrays = 7; // the arrays of a score's measure (copra_score_t)
+constexpr int kTargetCosts = 8; // the costs one target calculation drives (copra_target_t; kTargetMaxCosts of target_step.hpp)
 
 // Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
 // from the caller or a view into an owned block.  Nothing owned refers to anything else owned, so the order of destruction is free.
@@ -231,6 +235,18 @@ struct copra_batch {
     Dev<int> d_score_age; // ... and [batch] its age_out
     Dev<unsigned char> d_score_part; // the partials of the summary's first stage, then its result
     PinnedBuf<unsigned char> h_score_sum; // the result's way to the host
+    // steady-state targets (copra_batch_set_target; copra_hip_target.hip, target_step.hpp): every buffer is taken by the setter, never by the tick
+    bool target_on = false;
+    int target_offset = 0, target_per_instance = 0;
+    long long target_steps = 0;
+    const double *target_H = nullptr, *target_r = nullptr; // device: the caller's, or the copies below
+    Dev<double> own_target_H, own_target_r; // the library's copies of host arrays
+    int target_ncost = 0; // the driven costs: their slot among the kernel-evaluated terms, the rows of one block, the map T_c
+    int target_cost[kTargetCosts] = {}, target_rows[kTargetCosts] = {};
+    const double* target_map[kTargetCosts] = {};
+    Dev<double> own_target_map[kTargetCosts];
+    Dev<double> d_target; // [batch][nx + nu]: z = [xs ; us]
+    Dev<int> d_target_status; // [batch]: 1 where the last calculation found the instance singular
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -328,6 +344,18 @@ inline copra_status_t bias_restart(copra_batch* h, hipStream_t s)
     return COPRA_OK;
 }
 
+// A reference of cost term t given by hand or by a schedule: the cost leaves the target calculation's list, as those setters end a schedule
+inline void target_drop_cost(copra_batch* h, int t)
+{
+    for (int k = 0; k < h->target_ncost; ++k) {
+        if (h->target_cost[k] != t) continue;
+        for (int q = k + 1; q < h->target_ncost; ++q)
+            h->target_cost[q - 1] = h->target_cost[q], h->target_rows[q - 1] = h->target_rows[q], h->target_map[q - 1] = h->target_map[q];
+        h->target_ncost -= 1;
+        return;
+    }
+}
+
 // ---- copra_hip.hip ----
 typedef void (*fused_kernel_t)(const FusedPlan);
 FusedPlan device_plan(const copra_batch* h);
@@ -339,5 +367,8 @@ fused_kernel_t select_tier2_kernel(const FusedPlan& P);
 // ---- copra_hip_score.hip: one tick's update of the records, on `s` behind the plant step -- x [batch][nx] the true state after the tick, u
 // [batch][nu] and age [batch] what the tick wrote as u_out / age_out; called only while h->score_on; no synchronisation, no allocation ----
 copra_status_t launch_score(copra_batch* h, const double* x, const double* u, const int* age, hipStream_t s, const char* who);
+// ---- copra_hip_target.hip: the steady states and the driven costs' references from the model, the d and the setpoint's block in force, on
+// `s` (behind the handle's last stream where that is another one); returns at once while targets are off; no synchronisation, no allocation ----
+copra_status_t launch_target(copra_batch* h, hipStream_t s, const char* who);
 // ---- copra_hip_jit.hip: dense-QP kernels compiled at run time for one problem size (copra_qp_dense_specialise) ----
 hipFunction_t dense_jit_lookup(int n, int lanes);

@@ -662,6 +662,66 @@ const copra_score_record_t* copra_batch_score_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_score(copra_batch_t* h, copra_score_record_t* host);
 copra_status_t copra_batch_score_summary(copra_batch_t* h, copra_score_summary_t* out);
 
+/* ---- steady-state targets: the references follow d and a setpoint (ABI 15).  The estimator and the observer make the model's d right; an
+ *      offset-free loop also needs the target calculator, which recomputes the steady state (xs, us) that is consistent with the model, its
+ *      current d and the setpoint, and makes it the reference of the costs: a TrajectoryCost towards a goal beside a ControlCost whose
+ *      reference is zero pull against each other under a constant load, because the equilibrium control is not zero.  Here the caller hands
+ *      the controlled outputs, the setpoint signal and the driven costs over once (copra_batch_set_target) and a kernel of its own keeps the
+ *      references right on the device, in stream order.  Per instance b, with n = nx + nu and nr == nu:
+ *        M = [ A - I   B ]      rhs = [ -d ]        M z = rhs,   z = [xs ; us]
+ *            [   H     0 ]            [  r ]
+ *        p_c[s r_c + i] = (T_c z)[i]      for every driven cost c, every block s = 0 .. S_c - 1, every row i = 0 .. r_c - 1
+ *      A, B, d are the controller's model in force -- d the estimates while the estimator or the observer's Ld is on.  r is block
+ *      min(tau + offset, steps - 1) of the setpoint signal, tau the schedule tick (copra_batch_schedule_tick).  T_c = cost_map[c] is
+ *      [cost_rows[c] x n] column-major and shared by the batch; for the step forms of the four cost kinds it is [M_c N_c] (a missing M or N:
+ *      zeros), so that p = M xs + N us.  S_c = (rows of the cost as created) / cost_rows[c], the rule of copra_batch_set_reference_schedule.
+ *      The blocks are written into the per-instance references the solve reads: the driven costs go into per-instance-reference mode, as
+ *      copra_batch_set_cost_reference_all puts them there, every instance starting from the reference in force.
+ *      The solve: Gaussian elimination with partial pivoting on [M | rhs] -- the pivot of column k is the entry of largest magnitude among
+ *      rows k .. n - 1, ties to the LOWEST row (for a double integrator A - I has a zero diagonal: without pivoting the first pivot is 0);
+ *      f = M_ik / M_kk, M_ij = M_ij - f M_kj for j = k + 1 .. n ASCENDING; back substitution acc = rhs_i, acc = acc - M_ij z_j for
+ *      j = i + 1 .. n - 1 ASCENDING, z_i = acc / M_ii; a reference row is ((0.0 + T[i,0] z_0) + T[i,1] z_1) + ...  (target_step.hpp).
+ *      An instance is SINGULAR when a pivot has |pivot| <= n 2^-52 max|M_ij| or M or rhs holds a non-finite value: target_status[b] = 1,
+ *      its references and its stored z keep their bits, nothing of its neighbours changes.  Otherwise target_status[b] = 0.
+ *      The kernel is stateless -- it factorises from A, B, H every time, nothing cached can go stale -- and is launched, stream-ordered,
+ *      without a synchronisation or an allocation, by: every copra_batch_advance and every tick of copra_batch_rollout, behind the plant
+ *      step (which moves d), the tick counter's += 1, the score and the schedule windows; copra_batch_set_target itself, on the stream of
+ *      the last solve / tick, so that the first solve is right; copra_batch_schedule_seek; copra_batch_set_bias; copra_batch_set_system
+ *      and copra_batch_set_system_rowmajor_async.  Held instances are computed like any other: their r may move.  While targets were never
+ *      enabled every one of these launches exactly what it launched in ABI 14.
+ *      A driven cost cannot also follow a reference schedule: copra_batch_set_target on a cost with a live schedule is COPRA_ERR_RUNTIME; a
+ *      later copra_batch_set_reference_schedule or copra_batch_set_cost_reference[_all] on a driven cost takes it off the target's list.
+ *      copra_batch_set_target(h, NULL) ends the targets and keeps the last references; copra_batch_set_shared_system ends them too.
+ *      copra_batch_target_device / _target_status_device: z [batch][nx + nu] and the status [batch] on the device (NULL while off);
+ *      copra_batch_get_target waits for the last tick and copies; z or status may be NULL.  copra_batch_get_cost_reference waits likewise and
+ *      copies the per-instance reference of cost `cost_index` in force, [batch][rows of the cost as created] -- what this kernel, a
+ *      schedule's window or copra_batch_set_cost_reference[_all] wrote; COPRA_ERR_RUNTIME while the controller-wide reference is in force.
+ *      COPRA_ERR_ARG: a NULL handle, steps < 1, offset < 0, n_costs outside 1 .. 8, no such cost (or one cost twice), a NULL array.
+ *      COPRA_ERR_DOMAIN: nr != uDim; cost_rows[c] does not divide the cost's rows.  COPRA_ERR_RUNTIME: no system set yet; a driven cost
+ *      with a live schedule; copra_batch_get_target while targets are off.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller; a model
+ *      from copra_batch_set_shared_system, which has one d; a dense (host-evaluated) cost, or a full-size cost the controller does not
+ *      evaluate step by step; systems of one wave (64 instances) that do not fit the LDS (xDim + uDim beyond about 16). ---- */
+typedef struct {
+    int struct_size; /* append-only, set by copra_target_init */
+    int nr; /* must equal uDim */
+    const double* H; /* [nr x nx] column-major, one for the batch */
+    const double* r; /* [per_instance ? batch : 1][steps][nr] */
+    long long steps;
+    int offset;
+    int per_instance;
+    int n_costs; /* 1 .. 8 driven costs */
+    const int* cost_index;
+    const int* cost_rows;
+    const double* const* cost_map; /* T_c [cost_rows[c] x (nx + nu)] column-major */
+    int on_device; /* H, r, cost_map[*] are device arrays used in place; else copied (one synchronisation) */
+} copra_target_t;
+void copra_target_init(copra_target_t* target);
+copra_status_t copra_batch_set_target(copra_batch_t* h, const copra_target_t* target);
+const double* copra_batch_target_device(const copra_batch_t* h);
+const int* copra_batch_target_status_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_target(copra_batch_t* h, double* z, int* status);
+copra_status_t copra_batch_get_cost_reference(copra_batch_t* h, int cost_index, double* p);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
