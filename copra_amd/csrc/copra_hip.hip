@@ -400,13 +400,9 @@ static bool axis_solver_wanted(const copra_batch* h, const FusedPlan& P)
     const copra_options_t& opt = h->hp.opt;
     if (h->ad.axis_off || P.prof_fine || h->packed || h->shared) return false;
     if (opt.lane_min_batch > 0 && P.batch < opt.lane_min_batch) return false;
-    if (h->limit_sched_seen) { // limits written by a schedule (live, or ended with its last window kept): only the builds that read an instance's own
-        // limits (CT: lmpc_axis.hpp) -- the others read the controller's
-        const bool weights = plan_has_weights(P);
-        const AxisBuild* const first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, false);
-        const AxisBuild* const list = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, true);
-        if (!first || !first->ct || !list || !list->ct) return false;
-    }
+    // (limits written by a schedule -- live, or ended with its last window kept -- are per-instance limits like those set by hand: a schedule
+    //  allocates d_row_f_inst, or d_lb_inst and d_ub_inst, before its first window, and the handle keeps them for its life, so the plan carries
+    //  them and axis_solver_covers asks for the builds that read an instance's own limits)
     return axis_solver_covers(h->hp, P);
 }
 static size_t lane_lds_bytes(const FusedPlan& P)

@@ -775,7 +775,6 @@ copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_in
     ls.sched = sched;
     ls.steps = steps;
     ls.r = r, ls.S = S, ls.row0 = row0, ls.offset = offset, ls.per_instance = per_instance != 0, ls.preview = preview != 0;
-    h->limit_sched_seen = true;
     return write_limit_windows(h, h->last_stream, who);
 }
 
@@ -818,7 +817,6 @@ copra_status_t copra_batch_set_control_bound_schedule(copra_batch_t* h, const do
         ls->steps = steps;
         ls->r = P.nu, ls->S = P.N, ls->row0 = 0, ls->offset = offset, ls->per_instance = per_instance != 0, ls->preview = preview != 0;
     }
-    h->limit_sched_seen = true;
     return write_limit_windows(h, h->last_stream, who);
 }
 

@@ -199,7 +199,6 @@ struct copra_batch {
     long long sched_tick = 0; // at the controller's tick counter tau: the advances so far, or what copra_batch_schedule_seek set
     std::map<int, LimitSchedule> cstr_sched; // limit schedules by constraint (position in the user's array) ...
     LimitSchedule lb_sched, ub_sched; // ... and of the control bounds (both live or neither)
-    bool limit_sched_seen = false; // a limit schedule has written per-instance limits of this controller: its last window stays in force when it ends
     // backup plans of the tick (copra_batch_set_backup_steps; copra_hip_plant.hip, plant_step.hpp)
     int backup_steps = 0; // K: 0 is off
     Dev<double> d_plan; // [batch][K][nu]: controls of steps 1 .. K of every instance's last successful solve

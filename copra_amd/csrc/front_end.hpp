@@ -36,9 +36,15 @@ inline bool axis_solver_covers(const HostPlan& hp, const FusedPlan& P)
         }
     }
     if (hp.opt.no_axis_solver || hp.opt.no_lane_pass || P.axis_tab < 0 || hp.large || P.initial_state) return false;
-    // (per-instance limits: the builds that keep bounds and right-hand sides in registers take this lane's own -- where they are the same
-    //  along the horizon, else the instance goes to the tier: lmpc_axis.hpp)
-    if ((P.row_f_inst || P.lb_inst || P.ub_inst) && (!P.axis_const || (P.lb_inst == nullptr) != (P.ub_inst == nullptr))) return false;
+    // (per-instance limits: the builds that keep bounds and right-hand sides in registers, CT, take this lane's own -- where they are the same
+    //  along the horizon, else the instance goes to the tier: lmpc_axis.hpp.  The other builds read the controller's, so BOTH launches must
+    //  be CT ones: the second chance re-solves what the first lists, with the same limits)
+    if (P.row_f_inst || P.lb_inst || P.ub_inst) {
+        if (!P.axis_const || (P.lb_inst == nullptr) != (P.ub_inst == nullptr)) return false;
+        const AxisBuild* const first = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, false);
+        const AxisBuild* const list = pick_axis_build(P.nx, P.nu, P.N, P.axis_const, P.axis_rpa, P.stage_refs, weights, true);
+        if (!first || !first->ct || !list || !list->ct) return false;
+    }
     for (int t = 0; t < kMaxCosts; ++t) // (per-instance references: a lane rebuilds the affine terms of its axis from them -- FusedPlan::axis_cref)
         if (P.cost_p[t] && (P.axis_cref < 0 || t >= P.ncost)) return false;
     if (P.stage_refs) { // reference trajectories: the stages' h wait in the lane's sparse array for the sweep (lmpc_axis.hpp)

@@ -2,8 +2,10 @@
 preview control) with a goal and velocity / jerk limits PER ROBOT, entirely on the device.
 
 Every robot has its own sampling period, goal (copra_batch_set_cost_reference) and limits (copra_batch_set_constraint_rhs,
-copra_batch_set_control_bounds); every tick x0 <- the state predicted for step 1 plus a disturbance.  The controller's axes are decoupled, so
-the engine solves it with one (robot, axis) per lane -- nothing to declare.
+copra_batch_set_control_bounds); every tick x0 <- the state predicted for step 1 plus a disturbance.  The controller's axes are decoupled, and
+without the limits per robot the engine would solve it with one (robot, axis) per lane.  Only the builds of that solver that
+keep their tables in registers read a robot's own limits, and for chains of three states the second launch has none: with limits per robot
+this controller runs the lane pass and the wave-per-instance tiers (`axis_solver` in the output says which ran) -- nothing to declare.
 
     python examples/jerk_fleet.py [batch] [ticks]
 """

@@ -226,6 +226,10 @@ def _lmpc_solve(A, B, d, x0, N, costs, cstrs, dump_instance, specialised, initia
         raise _capi.CopraUnsupported("emu")
     n, neq, nineq = sizes[0], sizes[1], sizes[2]  # n = number of decision variables of the QP
     mgen = neq + nineq
+    if rr is not None and rr.shape != (batch, mgen):  # (the kernels index [instance][stacked row]: a wrong shape would read past the array)
+        raise ValueError("row_rhs: shape %r, expected %r" % (rr.shape, (batch, mgen)))
+    if lo is not None and (lo.shape != (batch, nu * N) or up.shape != (batch, nu * N)):
+        raise ValueError("bounds: shapes %r and %r, expected %r" % (lo.shape, up.shape, (batch, nu * N)))
     X = nx * (N + 1)
     u = np.full((batch, nu * N), np.nan)
     tr = np.full((batch, X), np.nan)

@@ -1,6 +1,8 @@
 """Random controllers on the shapes of the (instance, axis)-per-lane solver (tests/random_controllers.py: make_integrator, make_chain3, make_chain1; now and then
 in axis-major state order, with a goal per instance, with cost weights per instance) through the CPU wave emulator of the kernel bodies against the oracle: statuses, iteration
-counters, U and X.   python tests/fuzz/fuzz_axis_emulator.py [first_seed [count [batch]]]"""
+counters, U and X.   python tests/fuzz/fuzz_axis_emulator.py [--limits] [first_seed [count [batch]]]
+--limits: every instance its own right-hand sides and control bounds as well (random_controllers.draw_limits: the solver keeps the controller only where
+both its builds read them, pyemu.last_axis_run() says whether it did)"""
 import os
 import sys
 
@@ -20,9 +22,11 @@ def rel(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-3))) if a.size else 0.0
 
 
-first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-count = int(sys.argv[2]) if len(sys.argv) > 2 else 60
-b = int(sys.argv[3]) if len(sys.argv) > 3 else 24
+argv = [a for a in sys.argv[1:] if a != "--limits"]
+with_limits = "--limits" in sys.argv[1:]
+first = int(argv[0]) if len(argv) > 0 else 0
+count = int(argv[1]) if len(argv) > 1 else 60
+b = int(argv[2]) if len(argv) > 2 else 24
 nbad = ntie = naxis = 0
 for seed in range(first, first + count):
     rng = np.random.default_rng([seed, 5])
@@ -43,8 +47,15 @@ for seed in range(first, first + count):
                for t, cs in enumerate(c["costs"]) if cs.get("weights") is not None and cs["kind"] != "dense"
                and np.size(cs["weights"]) == np.size(cs["p"]) and np.size(cs["p"]) in (c["nx"], c["nu"])}
         what.append("own weights on %s" % sorted(wts))
-    re = pyemu.lmpc_solve(c["A"], c["B"], c["d"], c["x0"], c["N"], c["costs"], c["cstrs"], cost_refs=refs, cost_weights=wts)
+    lim = RC.draw_limits(c, seed) if with_limits else dict(rhs={}, bounds=None, row_rhs=None)
+    re = pyemu.lmpc_solve(c["A"], c["B"], c["d"], c["x0"], c["N"], c["costs"], c["cstrs"], cost_refs=refs, cost_weights=wts, row_rhs=lim["row_rhs"],
+                          bounds=lim["bounds"])
     run = pyemu.last_axis_run()
+    if with_limits:
+        what.append("own limits (%s%s), %s" % ("rhs " if lim["rhs"] else "", "bounds" if lim["bounds"] else "", "solver" if run else "tiers"))
+        if run and (lim["rhs"] or lim["bounds"]) and not (run["first"][6] and run["second"][6]):
+            what.append("A BUILD THAT DOES NOT READ THEM")
+            nbad += 1
     if wts:
         what.append("builds %s" % (run["first"][0] if run else "generic"))
     bad = tie = 0
@@ -53,7 +64,7 @@ for seed in range(first, first + count):
         costs = c["costs"] if refs is None else [dict(c["costs"][0], p=refs[0][k])] + c["costs"][1:]
         if wts:
             costs = [dict(cs, weights=wts[t][k]) if t in wts else cs for t, cs in enumerate(costs)]
-        ro = pyoracle.lmpc_solve(c["A"][k], c["B"][k], c["d"][k], c["x0"][k], c["N"], costs, c["cstrs"])
+        ro = pyoracle.lmpc_solve(c["A"][k], c["B"][k], c["d"][k], c["x0"][k], c["N"], costs, RC.instance_cstrs(c, lim, k))
         if re["status"][k] != ro["status"]:
             bad += 1
             continue

@@ -367,3 +367,59 @@ def com_preview_with_general_rows(seed, batch):
     else:
         cstrs.append(dict(kind="control", G=rng.standard_normal((1, 3)), f=[1.0]))
     return wl, cstrs
+
+
+def draw_limits(c, seed, batch=None):
+    """Per-instance limits for a controller of this module (copra_batch_set_constraint_rhs, copra_batch_set_control_bounds): a right-hand side
+    for every constraint that has an f and control bounds where the controller has a ControlBoundConstraint, each the controller's own scaled
+    by U(0.6, 1.0) per instance and the same along the horizon; now and then only one of the two.  A generator of its own: no controller above
+    depends on it.  -> dict(rhs: {constraint index: (batch, size of its f)}, bounds: (lower, upper) each (batch, nu N), or None, row_rhs: the
+    right-hand sides of ALL rows in the stacked order (batch, rows) -- equalities first, then inequalities, each in the order given, a per-step
+    entry step by step, the finite sides of a TrajectoryBoundConstraint among them at the controller's values --, or None where rhs is empty)"""
+    rng = np.random.default_rng([seed, 60606])
+    b = c["x0"].shape[0] if batch is None else batch
+    nx, nu, N = c["nx"], c["nu"], c["N"]
+    which = rng.choice(["both", "rhs", "bounds"], p=[0.7, 0.15, 0.15])
+    rhs, bounds = {}, None
+    for t, cs in enumerate(c["cstrs"]):
+        if "f" in cs:
+            rhs[t] = rng.uniform(0.6, 1.0, b)[:, None] * np.asarray(cs["f"], dtype=float)[None, :]
+        elif cs["kind"] == "control_bound":
+            s = rng.uniform(0.6, 1.0, b)[:, None]
+            lo, hi = np.asarray(cs["lower"], dtype=float), np.asarray(cs["upper"], dtype=float)
+            if lo.size == nu:
+                lo, hi = np.tile(lo, N), np.tile(hi, N)
+            bounds = (s * lo[None, :], s * hi[None, :])
+    if which == "bounds" and bounds is not None:  # (only one of the two, where the controller has it)
+        rhs = {}
+    if which == "rhs" and rhs:
+        bounds = None
+    row_rhs = None
+    if rhs:
+        eq, ineq = [], []
+        for t, cs in enumerate(c["cstrs"]):
+            if cs["kind"] == "control_bound":
+                continue
+            if cs["kind"] == "trajectory_bound":
+                lo, hi = np.asarray(cs["lower"], dtype=float), np.asarray(cs["upper"], dtype=float)
+                assert np.isneginf(lo).all() and hi.size == nx  # (what this module draws: upper limits per step)
+                ineq.append(np.tile(hi[np.isfinite(hi)], (b, N + 1)))
+                continue
+            f = rhs[t]
+            per_step = cs["kind"] == "trajectory" and np.shape(cs["E"])[1] == nx or cs["kind"] == "control" and np.shape(cs["G"])[1] == nu \
+                or cs["kind"] == "mixed" and np.shape(cs["E"])[1] == nx
+            (ineq if cs.get("ineq", True) else eq).append(np.tile(f, (1, N + 1 if cs["kind"] == "trajectory" else N)) if per_step else f)
+        row_rhs = np.ascontiguousarray(np.hstack(eq + ineq))
+    return dict(rhs=rhs, bounds=bounds, row_rhs=row_rhs)
+
+
+def instance_cstrs(c, lim, k):
+    """the controller's constraints with instance k's limits of draw_limits, for a solver that takes controller-wide constraints"""
+    out = []
+    for t, cs in enumerate(c["cstrs"]):
+        if t in lim["rhs"]:
+            cs = dict(cs, f=lim["rhs"][t][k])
+        elif cs["kind"] == "control_bound" and lim["bounds"] is not None:
+            cs = dict(kind="control_bound", lower=lim["bounds"][0][k], upper=lim["bounds"][1][k])
+        out.append(cs)
+    return out

@@ -69,6 +69,11 @@ def _initial_state():
     return dict(A=np.tile(pb["A"], (2, 1, 1)), B=np.tile(pb["B"], (2, 1, 1)), x0=np.zeros((2, 2)), N=12, costs=pb["costs"], cstrs=pb["cstrs"])
 
 
+def _limits(rows, nu, N):
+    """per-instance right-hand sides of `rows` rows at every step and control bounds, for 4 instances"""
+    return dict(row_rhs=np.full((4, rows * (N + 1)), 0.4), bounds=(np.full((4, nu * N), -1.0), np.full((4, nu * N), 1.0)))
+
+
 COM_W = {0: np.ones((4, 6)), 1: np.ones((4, 3))}
 IS = dict(R=10.0 * np.eye(2), r=np.array([0.1, -0.2]))
 # name: (line of axis_solver_wanted | lane_pass_wanted, controller, options, inputs, axis covers, lane covers)
@@ -99,6 +104,12 @@ CASES = {
     # (four cost terms: neither FusedPlan::lane_cref nor axis_cref -- also the second half of line 497's condition)
     "lane_531_stage_references_without_coefficients": (531, lambda: _four_costs(_tracking()), {}, {}, False, False),
     "stage_references_with_coefficients": (None, _tracking, {}, {}, True, True),
+    # per-instance limits: only where BOTH builds the solver picks keep their tables in registers -- the others read the controller's limits
+    # (front_end.hpp; line None: the rule is younger than the text the other lines are from)
+    "limits_kinematic_second_chance_reads_lds": (None, _kinematic, {}, _limits(3, 3, 20), False, True),
+    "limits_jerk_second_chance_reads_lds": (None, _jerk, {}, _limits(3, 3, 20), False, False),
+    "limits_com_21_second_chance_reads_lds": (None, lambda: _com(N=21), {}, _limits(3, 3, 21), False, True),
+    "limits_com_20_both_builds_in_registers": (None, _com, {}, _limits(3, 3, 20), True, True),
 }
 
 
