@@ -600,52 +600,113 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
         }
 #pragma unroll
         for (int j = 0; j < RPA; ++j) nrow[j] = 0.0;
+        // The row norms depend on (A, B, E) alone and are read only where a row is violated -- the exception: their recurrences do not run with
+        // the stages but are caught up, stage by stage and in the stages' order, where some lane of the wave has a violated row (kdone: the
+        // stages they have been advanced by, wave-uniform).  A scan without a violated row does no norm work at all.
+        int kdone = 0;
+        constexpr bool ONE_TEST = RPA == 1;
+        auto norm_stage = [&]() __attribute__((always_inline)) { // nrow (CT) or W takes the term of G = A^t B, then G <- A G
+            if (CT) {
+#pragma unroll
+                for (int j = 0; j < RPA; ++j) {
+                    if (j < rpa) {
+                        double pg = 0.0;
+#pragma unroll
+                        for (int i = 0; i < NXA; ++i) pg += re[j][i] * G[i];
+                        nrow[j] += pg * pg;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NXA; ++i) {
+#pragma unroll
+                    for (int j = 0; j < NXA; ++j) W[i][j] += G[i] * G[j];
+                }
+            }
+            double gn[NXA];
+#pragma unroll
+            for (int i = 0; i < NXA; ++i) {
+                double ag = 0.0;
+#pragma unroll
+                for (int j = 0; j < NXA; ++j) ag += A[i][j] * G[j];
+                gn[i] = ag;
+            }
+#pragma unroll
+            for (int i = 0; i < NXA; ++i) G[i] = gn[i];
+        };
+        // row j of step k on the new iterate: its slack (an empty slot has f = inf: its slack is not below thr) and, !CT, what the tables say of it
+        struct RowAt {
+            double s, e[NXA], gq, cidd;
+        };
+        auto row_at = [&](int k, int j, double uk, bool with_u) __attribute__((always_inline)) -> RowAt {
+            RowAt r;
+            double ax = 0.0, f;
+            r.gq = r.cidd = 0.0;
+            if (CT) {
+#pragma unroll
+                for (int i = 0; i < NXA; ++i) r.e[i] = re[j][i];
+                f = rf[j];
+            } else {
+                const double* const rw = T + oRows + (k * rpa + j) * RW;
+#pragma unroll
+                for (int i = 0; i < NXA; ++i) r.e[i] = rw[i];
+                r.gq = with_u ? rw[NXA] : 0.0;
+                f = rw[NXA + 1];
+                r.cidd = rw[NXA + 2]; // (a whole number, -1: the slot is empty)
+            }
+#pragma unroll
+            for (int i = 0; i < NXA; ++i) ax += r.e[i] * x[i];
+            if (!CT) ax += r.gq * uk;
+            r.s = f - ax;
+            return r;
+        };
+        // The bookkeeping of row j of step k.  A violated row is the exception: this runs where some lane of the wave has one, behind a
+        // wave-uniform test -- the norms are brought up to step k first; whether the slot holds a row is looked at here as well.
+        auto row_pick = [&](int k, int j, const RowAt& row) __attribute__((always_inline)) {
+            for (; kdone < k; ++kdone) norm_stage();
+            const double s = row.s;
+            double n2 = 0.0;
+            if (CT) {
+                n2 = nrow[j];
+            } else {
+#pragma unroll
+                for (int i = 0; i < NXA; ++i)
+#pragma unroll
+                    for (int i2 = 0; i2 < NXA; ++i2) n2 += (row.e[i] * row.e[i2]) * W[i][i2];
+                n2 += row.gq * row.gq;
+            }
+            const bool neg = (s < thr) & (CT ? rowon[j] : (row.cidd >= 0.0));
+            if (FIRST && count_viol) nviol += neg ? 1 : 0;
+            const bool v = neg & ((mact[2 + j] & (1u << k)) == 0u);
+            const int cid = CT ? ridx0[j] + k * ridxd[j] : (int)row.cidd;
+            const double l = s * s * nR, r = sR * sR * n2;
+            const bool better = v & ((cR < 0) | (l > r) | ((l == r) & (cid < cR)));
+            sR = better ? s : sR;
+            nR = better ? n2 : nR;
+            cR = better ? cid : cR;
+            lR = better ? ((NH + k * rpa + j) | (k << 8) | ((2 + j) << 13)) : lR;
+        };
+        // the rows of step k, slot by slot, each behind its own test
         auto rows_of = [&](int k, double uk, bool with_u) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < RPA; ++j) {
                 if (j < rpa) {
-                    double e[NXA], gq = 0.0, f, ax = 0.0, n2 = 0.0, cidd = 0.0;
-                    if (CT) {
-#pragma unroll
-                        for (int i = 0; i < NXA; ++i) e[i] = re[j][i];
-                        f = rf[j];
-                    } else {
-                        const double* const rw = T + oRows + (k * rpa + j) * RW;
-#pragma unroll
-                        for (int i = 0; i < NXA; ++i) e[i] = rw[i];
-                        gq = with_u ? rw[NXA] : 0.0;
-                        f = rw[NXA + 1];
-                        cidd = rw[NXA + 2]; // (a whole number, -1: the slot is empty)
-                    }
-#pragma unroll
-                    for (int i = 0; i < NXA; ++i) ax += e[i] * x[i];
-                    if (CT) {
-                        n2 = nrow[j];
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < NXA; ++i)
-#pragma unroll
-                            for (int i2 = 0; i2 < NXA; ++i2) n2 += (e[i] * e[i2]) * W[i][i2];
-                        ax += gq * uk;
-                        n2 += gq * gq;
-                    }
-                    const double s = f - ax;
-                    // (a violated row is the exception: nothing below runs where no lane has one at this step -- an empty slot has f = inf, its
-                    //  slack is not below thr: whether the slot holds a row is looked at behind the test as well)
-                    if (wave_any(s < thr)) {
-                        const bool neg = (s < thr) & (CT ? rowon[j] : (cidd >= 0.0));
-                        if (FIRST && count_viol) nviol += neg ? 1 : 0;
-                        const bool v = neg & ((mact[2 + j] & (1u << k)) == 0u);
-                        const int cid = CT ? ridx0[j] + k * ridxd[j] : (int)cidd;
-                        const double l = s * s * nR, r = sR * sR * n2;
-                        const bool better = v & ((cR < 0) | (l > r) | ((l == r) & (cid < cR)));
-                        sR = better ? s : sR;
-                        nR = better ? n2 : nR;
-                        cR = better ? cid : cR;
-                        lR = better ? ((NH + k * rpa + j) | (k << 8) | ((2 + j) << 13)) : lR;
-                    }
+                    const RowAt row = row_at(k, j, uk, with_u);
+                    if (wave_any(row.s < thr)) row_pick(k, j, row);
                 }
             }
+        };
+        // The bookkeeping of the bounds of u_k (sU, sL <= thr: a candidate is a violated bound -- the exception, like a violated row): whether it
+        // is free to be picked, whether it beats the worst so far, the first solve's count of violated constraints
+        auto bound_pick = [&](int k, double su, double sl) __attribute__((always_inline)) {
+            const bool vu = su < thr, vl = sl < thr;
+            const bool free_k = (mb & (1u << k)) == 0u;
+            if (FIRST && count_viol) nviol += (vu ? 1 : 0) + (vl ? 1 : 0);
+            const bool tu = free_k & (su < sU), tl = free_k & (sl < sL);
+            sU = tu ? su : sU;
+            kU = tu ? k : kU;
+            sL = tl ? sl : sL;
+            kL = tl ? k : kL;
         };
 #pragma unroll
         for (int k = 0; k < NMAX; ++k) {
@@ -674,56 +735,33 @@ COPRA_DEV void lmpc_axis_body(const FusedPlan& P, int group)
                     for (int i = 0; i < NXA; ++i) xi[i] = xn[i];
                 }
                 U[k] = u;
-                rows_of(k, u, true);
-                {
+                if (ONE_TEST) {
+                    // one row per axis and step: ONE wave-uniform test per stage -- a violated row or bound on some lane is the exception, and
+                    // everything about a candidate sits behind it; the row and the bounds keep their own tests there, on the rare path
+                    RowAt row {};
+                    if (rpa > 0) row = row_at(k, 0, u, true);
                     const double su = (CT ? ubc : UB[k]) - u, sl = u - (CT ? lbc : UB[NH + k]);
-                    // (sU, sL <= thr: a candidate is a violated bound -- the exception, like a violated row; whether it is free to be picked, whether
-                    //  it beats the worst so far and the first solve's count of violated constraints are looked at behind that test only)
-                    const bool vu = su < thr, vl = sl < thr;
-                    if (wave_any(vu | vl)) {
-                        const bool free_k = (mb & (1u << k)) == 0u;
-                        if (FIRST && count_viol) nviol += (vu ? 1 : 0) + (vl ? 1 : 0);
-                        const bool tu = free_k & (su < sU), tl = free_k & (sl < sL);
-                        sU = tu ? su : sU;
-                        kU = tu ? k : kU;
-                        sL = tl ? sl : sL;
-                        kL = tl ? k : kL;
-                    }
-                }
-                double xn[NXA], gn[NXA];
-#pragma unroll
-                for (int i = 0; i < NXA; ++i) {
-                    double acc = d[i] + B[i] * u, ag = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NXA; ++j) {
-                        acc += A[i][j] * x[j];
-                        ag += A[i][j] * G[j];
-                    }
-                    xn[i] = acc;
-                    gn[i] = ag;
-                }
-                if (CT) {
-#pragma unroll
-                    for (int j = 0; j < RPA; ++j) {
-                        if (j < rpa) {
-                            double pg = 0.0;
-#pragma unroll
-                            for (int i = 0; i < NXA; ++i) pg += re[j][i] * G[i];
-                            nrow[j] += pg * pg;
-                        }
+                    const bool vr = row.s < thr, vb = (su < thr) | (sl < thr);
+                    if (wave_any(vr | vb)) {
+                        if (wave_any(vr)) row_pick(k, 0, row);
+                        if (wave_any(vb)) bound_pick(k, su, sl);
                     }
                 } else {
-#pragma unroll
-                    for (int i = 0; i < NXA; ++i) {
-#pragma unroll
-                        for (int j = 0; j < NXA; ++j) W[i][j] += G[i] * G[j];
-                    }
+                    // (two rows: the slacks held across one test cost these builds registers they do not have -- a test per row, one for the bounds)
+                    rows_of(k, u, true);
+                    const double su = (CT ? ubc : UB[k]) - u, sl = u - (CT ? lbc : UB[NH + k]);
+                    if (wave_any((su < thr) | (sl < thr))) bound_pick(k, su, sl);
                 }
+                double xn[NXA];
 #pragma unroll
                 for (int i = 0; i < NXA; ++i) {
-                    x[i] = xn[i];
-                    G[i] = gn[i];
+                    double acc = d[i] + B[i] * u;
+#pragma unroll
+                    for (int j = 0; j < NXA; ++j) acc += A[i][j] * x[j];
+                    xn[i] = acc;
                 }
+#pragma unroll
+                for (int i = 0; i < NXA; ++i) x[i] = xn[i];
                 sched_fence();
             }
         }
