@@ -27,13 +27,9 @@ namespace {
 // (copra_plant_step_t) or ABI 11 (copra_plant_step_ex_t) passes: fields beyond the caller's struct_size keep their defaults (all zero)
 copra_status_t read_step(const copra_plant_step_t* step, copra_plant_step_obs_t& wide, const char* who)
 {
-    std::memset(&wide, 0, sizeof wide);
+    const copra_status_t rc = read_sized(wide, step, who, "copra_plant_step_t", "copra_plant_step_init");
+    if (rc != COPRA_OK) return rc;
     copra_plant_step_ex_t& out = wide.ex;
-    out.step.struct_size = (int)sizeof wide;
-    if (!step) return COPRA_OK;
-    if (step->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_plant_step_t::struct_size is not set (copra_plant_step_init)");
-    const size_t known = (size_t)step->struct_size < sizeof wide ? (size_t)step->struct_size : sizeof wide;
-    std::memcpy(&wide, step, known);
     out.step.struct_size = (int)sizeof wide;
     const int given = (out.step.A != nullptr) + (out.step.B != nullptr) + (out.step.d != nullptr);
     if (given != 0 && given != 3) return fail(COPRA_ERR_ARG, std::string(who) + ": a plant needs all of A, B and d (or none of them: the controller's model)");
@@ -129,17 +125,6 @@ copra_status_t write_windows(copra_batch* h, hipStream_t s, const char* who)
 {
     const copra_status_t rc = write_ref_windows(h, s, who);
     return rc != COPRA_OK ? rc : write_limit_windows(h, s, who);
-}
-
-// the library's copy of a host schedule (the caller has waited for the window launch that may still read the old one)
-copra_status_t own_schedule(LimitSchedule& ls, const double* sched, size_t count)
-{
-    if (ls.own.count() < count) {
-        ls.sched = nullptr; // (it may be the copy that goes)
-        OWN_TRY(ls.own.alloc(count));
-    }
-    HIP_TRY(hipMemcpy(ls.own, sched, count * sizeof(double), hipMemcpyHostToDevice));
-    return COPRA_OK;
 }
 
 // what one tick reads and writes beside the step's plant: the step's own pointers, or a rollout's rows of tick t
@@ -271,11 +256,8 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     void (*const kernel)(const PlantStepArgs) = P.sigma_w ? (P.est ? copra_plant_step_kernel<true, true> : copra_plant_step_kernel<false, true>)
                                                           : (P.est ? copra_plant_step_kernel<true> : copra_plant_step_kernel<false>);
     if (lds_bytes > 48 * 1024 && !h->obs_on) LDS_OPT_IN(kernel, lds_bytes);
-    if (s != h->last_stream) { // behind the solve, whichever stream that was launched on
-        if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
-    }
+    const copra_status_t behind = order_behind_last(h, s); // behind the solve, whichever stream that was launched on
+    if (behind != COPRA_OK) return behind;
     if (h->obs_on) { // the observer: its own build of the kernel, with a group and an image of its own
         const copra_status_t rc = launch_observer(h, P, st, io, s, who);
         if (rc != COPRA_OK) return rc;
@@ -409,7 +391,7 @@ copra_status_t copra_batch_set_bias_estimator(copra_batch_t* h, const double* ga
     if (rc != COPRA_OK) return rc;
     if (!gain) { // the estimator ends; the last estimates stay the model's d (h->d keeps pointing at them)
         h->bias_on = false;
-        h->bias_gain = nullptr;
+        h->bias_gain.unset();
         return COPRA_OK;
     }
     if (h->obs_on) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the observer is on (copra_batch_set_observer): its gain Ld estimates d");
@@ -419,23 +401,15 @@ copra_status_t copra_batch_set_bias_estimator(copra_batch_t* h, const double* ga
     const FusedPlan& P = h->hp.plan;
     if (bias_image_bytes(P.nx, P.nu, dense != 0) > kPlantLdsMax)
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one instance's model, plant and gain do not fit the LDS");
-    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), nd = (size_t)P.batch * P.nx;
     if (!on_device) { // the library's copy: a tick that still reads the old one first
-        const size_t count = (per_instance ? b : 1) * (size_t)P.nx * (dense ? P.nx : 1);
+        const size_t count = (per_instance ? (size_t)(P.batch > 0 ? P.batch : 1) : 1) * (size_t)P.nx * (dense ? P.nx : 1);
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        if (h->own_bias_gain.count() < count) {
-            h->bias_on = false; // (it may be the copy that goes)
-            OWN_TRY(h->own_bias_gain.alloc(count));
-        }
-        HIP_TRY(hipMemcpy(h->own_bias_gain, gain, count * sizeof(double), hipMemcpyHostToDevice));
-        gain = h->own_bias_gain;
+        h->bias_on = false; // (a failed attempt leaves the estimator off, never a gain half replaced)
+        OWN_TRY(h->bias_gain.copy_in(gain, count));
     }
-    if (!h->d_bias) OWN_TRY(h->d_bias.alloc(b * (size_t)P.nx));
-    if (h->d != h->d_bias) { // the d in force seeds the estimates, behind the last solve / tick; a caller's buffer is read, never written
-        if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
-        h->d = h->d_bias;
-    }
-    h->bias_gain = gain;
+    const copra_status_t rc_d = adopt_bias_buffer(h, h->last_stream); // the d in force seeds the estimates, behind the last solve / tick
+    if (rc_d != COPRA_OK) return rc_d;
+    if (on_device) h->bias_gain.borrow(gain);
     h->bias_dense = dense != 0, h->bias_per_instance = per_instance != 0;
     h->bias_on = true;
     return COPRA_OK;
@@ -469,7 +443,7 @@ copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* 
     if (rc != COPRA_OK) return rc;
     if (!C) { // the observer ends; x0 and d stay as the last tick left them
         h->obs_on = false;
-        h->obs_C = h->obs_Lx = h->obs_Ld = nullptr;
+        h->obs_C.unset(), h->obs_Lx.unset(), h->obs_Ld.unset();
         return COPRA_OK;
     }
     if (ny < 1) return fail(COPRA_ERR_ARG, std::string(who) + ": ny < 1");
@@ -489,38 +463,22 @@ copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* 
     if (!on_device) { // the library's copies: a tick that still reads the old ones first
         const size_t count = (per_instance ? b : 1) * (size_t)P.nx * ny;
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        copra_status_t err = COPRA_OK;
-        const auto own = [&](Dev<double>& buf, const double*& src) {
-            if (!src || err != COPRA_OK) return;
-            if (buf.count() < count) {
-                h->obs_on = false; // (it may be the copy that goes)
-                if (buf.alloc(count) != 0) {
-                    err = fail(COPRA_ERR_HIP, std::string(who) + ": no device memory for the observer's matrices");
-                    return;
-                }
-            }
-            if (hipMemcpy(buf, src, count * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-                err = fail(COPRA_ERR_HIP, std::string(who) + ": copying the observer's matrices failed");
-                return;
-            }
-            src = buf;
-        };
-        own(h->own_obs_C, C), own(h->own_obs_Lx, Lx), own(h->own_obs_Ld, Ld);
-        if (err != COPRA_OK) return err;
+        h->obs_on = false; // (a failed attempt leaves the observer off, never its matrices half replaced)
+        OWN_TRY(h->obs_C.copy_in(C, count));
+        OWN_TRY(h->obs_Lx.copy_in(Lx, count));
+        if (Ld) OWN_TRY(h->obs_Ld.copy_in(Ld, count));
+        else h->obs_Ld.unset();
     }
     if (Ld) { // the estimates of d: the buffer and the seed of copra_batch_set_bias_estimator
-        if (!h->d_bias) OWN_TRY(h->d_bias.alloc(b * (size_t)P.nx));
-        if (h->d != h->d_bias) {
-            if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
-            h->d = h->d_bias;
-        }
+        const copra_status_t rc_d = adopt_bias_buffer(h, h->last_stream);
+        if (rc_d != COPRA_OK) return rc_d;
     }
     if (!was_on) { // turned on: the plant starts from the x0 in force, behind the last solve / tick
         if (!h->d_xp) OWN_TRY(h->d_xp.alloc(b * (size_t)P.nx));
         if (nd) HIP_TRY(hipMemcpyAsync(h->d_xp, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
     }
     h->obs_ny = ny, h->obs_per_instance = per_instance != 0;
-    h->obs_C = C, h->obs_Lx = Lx, h->obs_Ld = Ld;
+    if (on_device) h->obs_C.borrow(C), h->obs_Lx.borrow(Lx), h->obs_Ld.borrow(Ld);
     h->obs_on = true;
     return COPRA_OK;
 }
@@ -570,13 +528,10 @@ copra_status_t copra_batch_set_noise(copra_batch_t* h, const copra_noise_t* nois
     const copra_status_t rc = check_handle(h, who);
     if (rc != COPRA_OK) return rc;
     copra_noise_t n;
-    std::memset(&n, 0, sizeof n);
-    if (noise) { // (fields beyond the caller's struct_size keep their defaults: all zero)
-        if (noise->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_noise_t::struct_size is not set (copra_noise_init)");
-        std::memcpy(&n, noise, (size_t)noise->struct_size < sizeof n ? (size_t)noise->struct_size : sizeof n);
-    }
+    const copra_status_t rc_n = read_sized(n, noise, who, "copra_noise_t", "copra_noise_init");
+    if (rc_n != COPRA_OK) return rc_n;
     if (!n.sigma_w && !n.sigma_v) { // off: nothing is drawn; the library's copies stay for the next time
-        h->noise_sw = h->noise_sv = nullptr;
+        h->noise_sw.unset(), h->noise_sv.unset();
         h->noise_tick = 0;
         return COPRA_OK;
     }
@@ -595,24 +550,12 @@ copra_status_t copra_batch_set_noise(copra_batch_t* h, const copra_noise_t* nois
         };
         if (bad(n.sigma_w, cw) || bad(n.sigma_v, cv)) return fail(COPRA_ERR_ARG, std::string(who) + ": a negative or NaN sigma");
         HIP_TRY(hipStreamSynchronize(h->last_stream)); // the library's copies: a tick that still reads the old ones first
-        if (n.sigma_w) {
-            if (h->own_noise_sw.count() < cw) {
-                h->noise_sw = nullptr; // (it may be the copy that goes)
-                OWN_TRY(h->own_noise_sw.alloc(cw));
-            }
-            HIP_TRY(hipMemcpy(h->own_noise_sw, n.sigma_w, cw * sizeof(double), hipMemcpyHostToDevice));
-            n.sigma_w = h->own_noise_sw;
-        }
-        if (n.sigma_v) {
-            if (h->own_noise_sv.count() < cv) {
-                h->noise_sv = nullptr;
-                OWN_TRY(h->own_noise_sv.alloc(cv));
-            }
-            HIP_TRY(hipMemcpy(h->own_noise_sv, n.sigma_v, cv * sizeof(double), hipMemcpyHostToDevice));
-            n.sigma_v = h->own_noise_sv;
-        }
+        h->noise_sw.unset(), h->noise_sv.unset(); // (a failed attempt leaves both streams off, never one with the other's layout)
+        if (n.sigma_w) OWN_TRY(h->noise_sw.copy_in(n.sigma_w, cw));
+        if (n.sigma_v) OWN_TRY(h->noise_sv.copy_in(n.sigma_v, cv));
+    } else {
+        h->noise_sw.borrow(n.sigma_w), h->noise_sv.borrow(n.sigma_v);
     }
-    h->noise_sw = n.sigma_w, h->noise_sv = n.sigma_v;
     h->noise_per_instance = n.per_instance != 0;
     h->noise_ny = n.sigma_v ? h->obs_ny : 0;
     h->noise_seed = n.seed, h->noise_first = n.first_instance;
@@ -684,7 +627,7 @@ copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_ind
     if (t < 0) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": a dense (host-evaluated) cost has no reference p");
     RefSchedule& rs = h->ref_sched[t];
     if (!sched) { // the schedule ends, the window stays (cost_p keeps pointing at it)
-        rs.sched = nullptr;
+        rs.sched.unset();
         return COPRA_OK;
     }
     if (steps < 1 || offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
@@ -697,14 +640,10 @@ copra_status_t copra_batch_set_reference_schedule(copra_batch_t* h, int cost_ind
     if (!on_device) { // the library's copy: a window launch that still reads the old one first
         const size_t count = (per_instance ? b : 1) * (size_t)steps * r;
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        if (rs.own.count() < count) {
-            rs.sched = nullptr; // (it may be the copy that goes)
-            OWN_TRY(rs.own.alloc(count));
-        }
-        HIP_TRY(hipMemcpy(rs.own, sched, count * sizeof(double), hipMemcpyHostToDevice));
-        sched = rs.own;
+        OWN_TRY(rs.sched.copy_in(sched, count));
+    } else {
+        rs.sched.borrow(sched);
     }
-    rs.sched = sched;
     rs.steps = steps;
     rs.r = r, rs.S = ct.prows / r, rs.offset = offset, rs.per_instance = per_instance != 0;
     if (!h->cost_p[t]) h->model_dirty = true; // shared model: c0 / C2 change
@@ -740,7 +679,7 @@ copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_in
             // (its last window launch may be in flight: it reads the schedule, which the caller may free now, and a right-hand side set by
             //  hand next must not be overtaken by it)
             HIP_TRY(hipStreamSynchronize(h->last_stream));
-            it->second.sched = nullptr;
+            it->second.sched.unset();
         }
         return COPRA_OK;
     }
@@ -759,20 +698,15 @@ copra_status_t copra_batch_set_constraint_schedule(copra_batch_t* h, int cstr_in
     if (!was_live && live_limit_windows(h) + 1 > kLimitWindowMax)
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": more live limit windows than one launch serves (8; lower and upper bounds count as one each)");
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
-    if (!h->d_row_f_inst) { // first use: every instance starts from the controller-wide right-hand sides
-        OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
-        std::vector<double> rep(b * (size_t)P.mgen);
-        for (size_t i = 0; i < b; ++i) std::copy(h->hp.row_f.begin(), h->hp.row_f.begin() + P.mgen, rep.begin() + i * P.mgen);
-        HIP_TRY(hipMemcpy(h->d_row_f_inst, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    const copra_status_t rc_f = ensure_row_f_inst(h);
+    if (rc_f != COPRA_OK) return rc_f;
     LimitSchedule& ls = h->cstr_sched[cstr_index];
     if (!on_device) { // the library's copy: a window launch that still reads the old one first
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        const copra_status_t rc = own_schedule(ls, sched, (per_instance ? b : 1) * (size_t)steps * r);
-        if (rc != COPRA_OK) return rc;
-        sched = ls.own;
+        OWN_TRY(ls.sched.copy_in(sched, (per_instance ? b : 1) * (size_t)steps * r));
+    } else {
+        ls.sched.borrow(sched);
     }
-    ls.sched = sched;
     ls.steps = steps;
     ls.r = r, ls.S = S, ls.row0 = row0, ls.offset = offset, ls.per_instance = per_instance != 0, ls.preview = preview != 0;
     return write_limit_windows(h, h->last_stream, who);
@@ -789,7 +723,7 @@ copra_status_t copra_batch_set_control_bound_schedule(copra_batch_t* h, const do
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": the controller has no ControlBoundConstraint (or is an InitialStateLMPC controller)");
     if (!lower) { // the schedule ends, the window stays in the per-instance bounds
         if (h->lb_sched.sched || h->ub_sched.sched) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (as for a constraint's schedule)
-        h->lb_sched.sched = h->ub_sched.sched = nullptr;
+        h->lb_sched.sched.unset(), h->ub_sched.sched.unset();
         return COPRA_OK;
     }
     if (steps < 1 || offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
@@ -804,16 +738,14 @@ copra_status_t copra_batch_set_control_bound_schedule(copra_batch_t* h, const do
     if (!on_device) {
         HIP_TRY(hipStreamSynchronize(h->last_stream));
         const size_t count = (per_instance ? b : 1) * (size_t)steps * P.nu;
-        copra_status_t rc = own_schedule(h->lb_sched, lower, count);
-        if (rc == COPRA_OK) rc = own_schedule(h->ub_sched, upper, count);
-        if (rc != COPRA_OK) {
-            h->lb_sched.sched = h->ub_sched.sched = nullptr;
-            return rc;
-        }
-        lower = h->lb_sched.own, upper = h->ub_sched.own;
+        int e = h->lb_sched.sched.copy_in(lower, count);
+        if (e == 0) e = h->ub_sched.sched.copy_in(upper, count);
+        if (e != 0) h->lb_sched.sched.unset(), h->ub_sched.sched.unset(); // (both live or neither)
+        OWN_TRY(e);
+    } else {
+        h->lb_sched.sched.borrow(lower), h->ub_sched.sched.borrow(upper);
     }
     for (LimitSchedule* ls : { &h->lb_sched, &h->ub_sched }) {
-        ls->sched = ls == &h->lb_sched ? lower : upper;
         ls->steps = steps;
         ls->r = P.nu, ls->S = P.N, ls->row0 = 0, ls->offset = offset, ls->per_instance = per_instance != 0, ls->preview = preview != 0;
     }

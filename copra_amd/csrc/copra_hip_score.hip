@@ -29,10 +29,7 @@ copra_status_t check_handle(const copra_batch* h, const char* who)
 void score_off(copra_batch* h) // (a release waits for a tick that still uses the buffer)
 {
     h->score_on = false;
-    for (int k = 0; k < kScoreArrays; ++k) {
-        h->score_arr[k] = nullptr;
-        h->own_score_arr[k].reset();
-    }
+    for (int k = 0; k < kScoreArrays; ++k) h->score_arr[k].reset();
     h->d_score.reset();
     h->d_score_u.reset();
     h->d_score_age.reset();
@@ -87,10 +84,9 @@ copra_status_t copra_batch_set_score(copra_batch_t* h, const copra_score_t* scor
         score_off(h);
         return COPRA_OK;
     }
-    if (score->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_score_t::struct_size is not set (copra_score_init)");
-    copra_score_t m; // (fields beyond the caller's struct_size keep their defaults: all zero)
-    std::memset(&m, 0, sizeof m);
-    std::memcpy(&m, score, (size_t)score->struct_size < sizeof m ? (size_t)score->struct_size : sizeof m);
+    copra_score_t m;
+    const copra_status_t rc_m = read_sized(m, score, who, "copra_score_t", "copra_score_init");
+    if (rc_m != COPRA_OK) return rc_m;
     if (m.x_ref && m.ref_steps < 1) return fail(COPRA_ERR_ARG, std::string(who) + ": ref_steps < 1");
     if (!(m.tol >= 0.0)) return fail(COPRA_ERR_ARG, std::string(who) + ": a negative or NaN tol");
     const FusedPlan& P = h->hp.plan;
@@ -114,14 +110,10 @@ copra_status_t copra_batch_set_score(copra_batch_t* h, const copra_score_t* scor
                 if (std::isnan(arr[k][i])) return fail(COPRA_ERR_ARG, std::string(who) + ": a NaN limit");
     }
     h->score_on = false; // (a failed attempt leaves the feature off, never a measure half replaced)
-    if (!m.on_device) { // the library's copies: a tick that still reads the old ones first
-        HIP_TRY(hipStreamSynchronize(h->last_stream));
-        for (int k = 0; k < kScoreArrays; ++k) {
-            if (!arr[k]) continue;
-            if (h->own_score_arr[k].count() < count[k] || !h->own_score_arr[k]) OWN_TRY(h->own_score_arr[k].alloc(count[k] ? count[k] : 1));
-            if (count[k]) HIP_TRY(hipMemcpy(h->own_score_arr[k], arr[k], count[k] * sizeof(double), hipMemcpyHostToDevice));
-            arr[k] = h->own_score_arr[k];
-        }
+    if (!m.on_device) HIP_TRY(hipStreamSynchronize(h->last_stream)); // the library's copies: a tick that still reads the old ones first
+    for (int k = 0; k < kScoreArrays; ++k) {
+        if (m.on_device || !arr[k]) h->score_arr[k].borrow(arr[k]);
+        else OWN_TRY(h->score_arr[k].copy_in(arr[k], count[k]));
     }
     const size_t chunks = (size_t)score_chunks((long long)b);
     if (!h->d_score) OWN_TRY(h->d_score.alloc(b * sizeof(ScoreRecord)));
@@ -130,7 +122,6 @@ copra_status_t copra_batch_set_score(copra_batch_t* h, const copra_score_t* scor
     if (!h->d_score_part) OWN_TRY(h->d_score_part.alloc((chunks + 1) * sizeof(ScoreSummary)));
     if (!h->h_score_sum) OWN_TRY(h->h_score_sum.alloc(sizeof(ScoreSummary)));
     HIP_TRY(hipMemsetAsync(h->d_score, 0, b * sizeof(ScoreRecord), h->last_stream)); // behind the last solve / tick
-    for (int k = 0; k < kScoreArrays; ++k) h->score_arr[k] = arr[k];
     h->score_dense = dense, h->score_per_instance = per;
     h->score_ref_steps = m.x_ref ? m.ref_steps : 1;
     h->score_tol = m.tol;

@@ -272,7 +272,7 @@ copra_status_t copra_batch_set_cost_reference(copra_batch_t* h, int cost_index, 
     if (cost_index < 0 || cost_index >= (int)h->hp.cost_slot.size()) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference: no such cost");
     cost_index = h->hp.cost_slot[(size_t)cost_index]; // (dense costs are not among the kernel-evaluated terms)
     if (cost_index < 0) return fail(COPRA_ERR_UNSUPPORTED, "copra_batch_set_cost_reference: a dense (host-evaluated) cost has no reference p");
-    h->ref_sched[cost_index].sched = nullptr; // (a reference given by hand ends the cost's schedule)
+    h->ref_sched[cost_index].sched.unset(); // (a reference given by hand ends the cost's schedule)
     target_drop_cost(h, cost_index); // ... and takes the cost off the target calculation's list
     if ((p != nullptr) != (h->cost_p[cost_index] != nullptr)) h->model_dirty = true; // shared model: c0 / C2 change
     if (!p) { // back to the controller-wide reference given at creation
@@ -338,7 +338,7 @@ copra_status_t copra_batch_set_cost_reference_all(copra_batch_t* h, int cost_ind
     if (!h->d_cost_p[t]) OWN_TRY(h->d_cost_p[t].alloc(b * rows));
     double* const out = h->d_cost_p[t];
     if (p == out) return fail(COPRA_ERR_ARG, "copra_batch_set_cost_reference_all: p aliases the library's buffer");
-    h->ref_sched[t].sched = nullptr; // (a reference given by hand ends the cost's schedule)
+    h->ref_sched[t].sched.unset(); // (a reference given by hand ends the cost's schedule)
     target_drop_cost(h, t); // ... and takes the cost off the target calculation's list
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a solve that still reads the buffer)
     const double* src = p;
@@ -373,15 +373,11 @@ copra_status_t copra_batch_set_constraint_rhs(copra_batch_t* h, int cstr_index, 
         auto it = h->cstr_sched.find(cstr_index);
         if (it != h->cstr_sched.end() && it->second.sched) {
             HIP_TRY(hipStreamSynchronize(h->last_stream));
-            it->second.sched = nullptr;
+            it->second.sched.unset();
         }
     }
-    if (!h->d_row_f_inst) { // first use: every instance starts from the controller-wide right-hand sides
-        OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
-        std::vector<double> rep(b * (size_t)P.mgen);
-        for (size_t i = 0; i < b; ++i) std::copy(h->hp.row_f.begin(), h->hp.row_f.begin() + P.mgen, rep.begin() + i * P.mgen);
-        HIP_TRY(hipMemcpy(h->d_row_f_inst, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    const copra_status_t rc_f = ensure_row_f_inst(h);
+    if (rc_f != COPRA_OK) return rc_f;
     const double* src = f;
     Dev<double> tmp; // freed at the return, after the launch that reads it: the free is the wait when the synchronisation was not reached
     if (!on_device) {
@@ -409,7 +405,7 @@ copra_status_t copra_batch_set_control_bounds(copra_batch_t* h, const double* lo
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (h->lb_sched.sched || h->ub_sched.sched) { // bounds given by hand end the bound schedule: a window launch in flight must not land after these copies
         HIP_TRY(hipStreamSynchronize(h->last_stream));
-        h->lb_sched.sched = h->ub_sched.sched = nullptr;
+        h->lb_sched.sched.unset(), h->ub_sched.sched.unset();
     }
     if (!h->d_lb_inst) OWN_TRY(h->d_lb_inst.alloc(count));
     if (!h->d_ub_inst) OWN_TRY(h->d_ub_inst.alloc(count));
@@ -521,18 +517,11 @@ copra_status_t copra_batch_set_initial_state_bounds(copra_batch_t* h, const doub
     if (!h->hp.plan.initial_state) return fail(COPRA_ERR_RUNTIME, "not an InitialStateLMPC controller");
     const size_t nd = (size_t)h->hp.plan.batch * h->hp.plan.nx;
     if (on_device) {
-        h->x0lb = x0lb;
-        h->x0ub = x0ub;
+        h->x0lb.borrow(x0lb), h->x0ub.borrow(x0ub);
         return COPRA_OK;
     }
-    if (!h->own_x0lb) {
-        OWN_TRY(h->own_x0lb.alloc((nd ? nd : 1)));
-        OWN_TRY(h->own_x0ub.alloc((nd ? nd : 1)));
-    }
-    HIP_TRY(hipMemcpy(h->own_x0lb, x0lb, nd * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->own_x0ub, x0ub, nd * sizeof(double), hipMemcpyHostToDevice));
-    h->x0lb = h->own_x0lb;
-    h->x0ub = h->own_x0ub;
+    OWN_TRY(h->x0lb.copy_in(x0lb, nd));
+    OWN_TRY(h->x0ub.copy_in(x0ub, nd));
     return COPRA_OK;
 }
 

@@ -53,11 +53,8 @@ copra_status_t launch_target(copra_batch* h, hipStream_t s, const char* who)
     if (lds_bytes > kPlantLdsMax) return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": one wave's target systems do not fit the LDS");
     if (lds_bytes > 48 * 1024) LDS_OPT_IN(copra_target_kernel, lds_bytes);
     const bool other = s != h->last_stream;
-    if (other) { // a solve or a tick that still reads the references or writes d: behind it ...
-        if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
-    }
+    const copra_status_t behind = order_behind_last(h, s); // a solve or a tick that still reads the references or writes d: behind it ...
+    if (behind != COPRA_OK) return behind;
     const unsigned grid = (unsigned)((S.batch + S.group - 1) / S.group);
     hipLaunchKernelGGL(copra_target_kernel, dim3(grid), dim3(kTargetThreads), lds_bytes, s, S);
     HIP_TRY(hipGetLastError());
@@ -85,10 +82,9 @@ copra_status_t copra_batch_set_target(copra_batch_t* h, const copra_target_t* ta
         target_off(h);
         return COPRA_OK;
     }
-    if (target->struct_size < (int)sizeof(int)) return fail(COPRA_ERR_ARG, std::string(who) + ": copra_target_t::struct_size is not set (copra_target_init)");
-    copra_target_t m; // (fields beyond the caller's struct_size keep their defaults: all zero)
-    std::memset(&m, 0, sizeof m);
-    std::memcpy(&m, target, (size_t)target->struct_size < sizeof m ? (size_t)target->struct_size : sizeof m);
+    copra_target_t m;
+    const copra_status_t rc_m = read_sized(m, target, who, "copra_target_t", "copra_target_init");
+    if (rc_m != COPRA_OK) return rc_m;
     if (m.steps < 1 || m.offset < 0) return fail(COPRA_ERR_ARG, std::string(who) + ": steps < 1 or offset < 0");
     if (m.n_costs < 1 || m.n_costs > kTargetMaxCosts) return fail(COPRA_ERR_ARG, std::string(who) + ": n_costs outside 1 .. 8");
     if (!m.H || !m.r || !m.cost_index || !m.cost_rows || !m.cost_map) return fail(COPRA_ERR_ARG, std::string(who) + ": a null array");
@@ -128,24 +124,14 @@ copra_status_t copra_batch_set_target(copra_batch_t* h, const copra_target_t* ta
     const size_t b = (size_t)(P.batch > 0 ? P.batch : 1), lead = m.per_instance ? b : 1;
     const size_t nH = (size_t)P.nu * P.nx, nr = lead * (size_t)m.steps * P.nu;
     target_off(h); // (a failed attempt leaves the feature off, never a setpoint half replaced)
-    const double* H = m.H;
-    const double* r = m.r;
-    const double* map[kTargetMaxCosts];
-    for (int k = 0; k < m.n_costs; ++k) map[k] = m.cost_map[k];
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // the one synchronisation: a launch that still reads the old copies, a solve that reads the references
-    if (!m.on_device) { // the library's copies
-        if (h->own_target_H.count() < nH) OWN_TRY(h->own_target_H.alloc(nH));
-        HIP_TRY(hipMemcpy(h->own_target_H, H, nH * sizeof(double), hipMemcpyHostToDevice));
-        H = h->own_target_H;
-        if (h->own_target_r.count() < nr) OWN_TRY(h->own_target_r.alloc(nr));
-        HIP_TRY(hipMemcpy(h->own_target_r, r, nr * sizeof(double), hipMemcpyHostToDevice));
-        r = h->own_target_r;
-        for (int k = 0; k < m.n_costs; ++k) {
-            const size_t count = (size_t)m.cost_rows[k] * n;
-            if (h->own_target_map[k].count() < count) OWN_TRY(h->own_target_map[k].alloc(count));
-            HIP_TRY(hipMemcpy(h->own_target_map[k], map[k], count * sizeof(double), hipMemcpyHostToDevice));
-            map[k] = h->own_target_map[k];
-        }
+    if (m.on_device) {
+        h->target_H.borrow(m.H), h->target_r.borrow(m.r);
+        for (int k = 0; k < m.n_costs; ++k) h->target_map[k].borrow(m.cost_map[k]);
+    } else { // the library's copies
+        OWN_TRY(h->target_H.copy_in(m.H, nH));
+        OWN_TRY(h->target_r.copy_in(m.r, nr));
+        for (int k = 0; k < m.n_costs; ++k) OWN_TRY(h->target_map[k].copy_in(m.cost_map[k], (size_t)m.cost_rows[k] * n));
     }
     if (!h->d_target) {
         OWN_TRY(h->d_target.alloc(b * (size_t)n));
@@ -173,10 +159,9 @@ copra_status_t copra_batch_set_target(copra_batch_t* h, const copra_target_t* ta
         }
         h->cost_p[t] = h->d_cost_p[t];
     }
-    h->target_H = H, h->target_r = r;
     h->target_steps = m.steps, h->target_offset = m.offset, h->target_per_instance = m.per_instance != 0;
     h->target_ncost = m.n_costs;
-    for (int k = 0; k < m.n_costs; ++k) h->target_cost[k] = slot[k], h->target_rows[k] = m.cost_rows[k], h->target_map[k] = map[k];
+    for (int k = 0; k < m.n_costs; ++k) h->target_cost[k] = slot[k], h->target_rows[k] = m.cost_rows[k];
     h->target_on = true;
     const copra_status_t rc = launch_target(h, h->last_stream, who); // so that the first solve is right
     if (rc != COPRA_OK) target_off(h);

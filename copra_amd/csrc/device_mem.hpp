@@ -3,7 +3,8 @@
 //   static void release(void* p);
 //   static int  copy_in(void* dst, const void* src, size_t bytes);  (DevBag only) host -> block
 // The HIP policies are in engine.hpp; tests/cpp/test_device_mem.cpp has a counting one.
-// A member that OWNS memory is a DevBuf / DevBag; a raw pointer next to it is borrowed or a view.  All-or-none groups need no helper:
+// A member that OWNS memory is a DevBuf / DevBag; a raw pointer next to it is borrowed or a view.  An array that a setter takes either on
+// the device (borrowed) or from the host (copied) is ONE member, a DevArg: the view in force and the copy behind it.  All-or-none groups need no helper:
 // allocate into locals and move them into the members once every one has succeeded -- a failed attempt then leaves the members as they were.
 #pragma once
 #include <cstddef>
@@ -57,6 +58,54 @@ public:
 private:
     T* p_ = nullptr;
     size_t n_ = 0;
+};
+
+// An input array that is the caller's device array or the library's copy of a host array: the `const T*` in force (null: unset) and the
+// copy, which outlives a borrow() and an unset() "for the next time".  Reads as the view (if (x), Q.C = h->obs_C).  Nothing here waits for
+// the device -- Mem has no stream: whoever calls copy_in() has waited for what may still read the old copy.
+template <class T, class Mem>
+class DevArg {
+public:
+    DevArg() = default;
+    DevArg(const DevArg&) = delete;
+    DevArg& operator=(const DevArg&) = delete;
+    DevArg(DevArg&& o) noexcept : view_(o.view_), copy_(std::move(o.copy_)) { o.view_ = nullptr; }
+    DevArg& operator=(DevArg&& o) noexcept // (a view of o's copy follows it: a block's address does not change with its owner)
+    {
+        if (this != std::addressof(o)) {
+            view_ = o.view_, o.view_ = nullptr;
+            copy_ = std::move(o.copy_);
+        }
+        return *this;
+    }
+
+    // the caller's device array; the copy is kept
+    void borrow(const T* device_ptr) { view_ = device_ptr; }
+    // the library's copy of `count` host elements (a block of one element when count is 0), grown only when it is too small.  The view is
+    // null from the first step on and stays null when the allocation or the copy fails, whose error code is returned
+    int copy_in(const T* host, size_t count)
+    {
+        view_ = nullptr;
+        int rc = copy_.grow(count ? count : 1);
+        if (rc == 0 && count) rc = Mem::copy_in(copy_.get(), host, count * sizeof(T));
+        if (rc != 0) return rc;
+        view_ = copy_.get();
+        return 0;
+    }
+    void unset() { view_ = nullptr; } // the copy is kept
+    void reset() // ... and here it goes
+    {
+        view_ = nullptr;
+        copy_.reset();
+    }
+    const T* get() const { return view_; }
+    const DevBuf<T, Mem>& copy() const { return copy_; }
+    operator const T*() const { return view_; }
+    explicit operator bool() const { return view_ != nullptr; }
+
+private:
+    const T* view_ = nullptr;
+    DevBuf<T, Mem> copy_;
 };
 
 // Move-only list of untyped blocks, all released with it.  The first error of any add() stays in error(); add() after an error still

@@ -28,9 +28,12 @@
 #include "plan_builder.hpp"
 #include "stage_plan.hpp"
 
+#include <algorithm>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace copra_hip;
@@ -68,8 +71,10 @@ using Dev = DevBuf<T, DeviceMem>;
 template <class T>
 using PinnedBuf = DevBuf<T, PinnedMem>;
 using Bag = DevBag<DeviceMem>;
+template <class T>
+using DevIn = DevArg<T, DeviceMem>;
 
-// HIP_TRY for what an owner returns: OWN_TRY(h->d_x.alloc(n)), OWN_TRY(h->d_x.grow(n))
+// HIP_TRY for what an owner returns: OWN_TRY(h->d_x.alloc(n)), OWN_TRY(h->d_x.grow(n)), OWN_TRY(h->x_in.copy_in(x, n))
 #define OWN_TRY(expr) HIP_TRY((hipError_t)(expr))
 
 // a plan table on the device (at least one element, so that an empty table still has an address)
@@ -133,8 +138,7 @@ struct AdaptState {
 
 // A cost whose reference follows a schedule (copra_batch_set_reference_schedule): the tick writes its window into d_cost_p (copra_hip_plant.hip)
 struct RefSchedule {
-    const double* sched = nullptr; // device: the caller's, or `own`; null: the cost has no schedule
-    Dev<double> own; // the library's copy of a host schedule
+    DevIn<double> sched; // null: the cost has no schedule
     long long steps = 0;
     int r = 0, S = 0, offset = 0, per_instance = 0;
 };
@@ -143,8 +147,7 @@ struct RefSchedule {
 // stacked rows; copra_batch_set_control_bound_schedule: the lower / upper control bounds, into d_lb_inst / d_ub_inst): the tick writes its window
 // behind the reference windows (copra_hip_plant.hip, limit_window.hpp)
 struct LimitSchedule {
-    const double* sched = nullptr; // device: the caller's, or `own`; null: no schedule
-    Dev<double> own; // the library's copy of a host schedule
+    DevIn<double> sched; // null: no schedule
     long long steps = 0;
     int r = 0, S = 0, row0 = 0, offset = 0, per_instance = 0, preview = 0;
 };
@@ -153,7 +156,13 @@ constexpr int kScoreArrays = 7; // the arrays of a score's measure (copra_score_
 constexpr int kTargetCosts = 8; // the costs one target calculation drives (copra_target_t; kTargetMaxCosts of target_step.hpp)
 
 // Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
-// from the caller or a view into an owned block.  Nothing owned refers to anything else owned, so the order of destruction is free.
+// from the caller or a view into an owned block.  An array that a setter accepts on the device (borrowed) or from the host (copied) is ONE
+// DevIn<T> member: it reads as the pointer in force and holds the library's copy, which a borrow or an unset keeps for the next time.  Its
+// setter waits for the handle's last stream once (a launch may still read the old copy), calls copy_in() per array and leaves its feature off
+// when one fails.  Nothing owned refers to anything else owned, so the order of destruction is free.
+// Deliberately NOT DevIn, because pointer and buffer mean more there than "theirs or our copy": A / B / d / x0 beside own_A / own_B / own_d /
+// own_x0 (own_x0 is also the tick's write buffer, d also aliases d_bias, own_A / own_B are the targets of the row-major transposes) and
+// cost_p / d_cost_p, cost_w / d_cost_w (the window and target kernels write d_cost_p, and equality with it is tested in several places).
 struct copra_batch {
     HostPlan hp;
     AdaptState ad;
@@ -161,7 +170,7 @@ struct copra_batch {
     Dev<int> d_row_step, d_row_ekind, d_row_eoff, d_row_gkind, d_row_goff;
     Dev<double> d_row_f, d_params, d_lb, d_ub;
     Dev<int> d_row_prev, d_warm; // warm start of the shared-model path (copra_batch_set_warm_start)
-    // system (owned copies, or borrowed device pointers)
+    // system (owned copies, or borrowed device pointers; not DevIn: see above)
     Dev<double> own_A, own_B, own_d, own_x0;
     int axis_order = 0; // the state order of this controller's systems as the (instance, axis)-per-lane solver sees it (FusedPlan::axis_order) ...
     bool axis_order_seen = false; // ... looked at when the first systems were set (see_axis_order, copra_hip.hip)
@@ -193,7 +202,7 @@ struct copra_batch {
     std::vector<double> shA, shB, shd;
     bool sh_dev_stale = true; // d_shA / d_shB / d_shd (the shared model as a plant, copra_hip_plant.hip) are older than shA / shB / shd
     Dev<double> d_row_f_inst, d_lb_inst, d_ub_inst; // per-instance rhs / control bounds
-    Dev<double> d_cost_p[kMaxCosts]; // per-instance cost references (owned copies) ...
+    Dev<double> d_cost_p[kMaxCosts]; // per-instance cost references (owned copies; with cost_p and the weights below not DevIn: see above) ...
     const double* cost_p[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_reference)
     RefSchedule ref_sched[kMaxCosts]; // ... which the tick rewrites for the costs that follow a schedule,
     long long sched_tick = 0; // at the controller's tick counter tau: the advances so far, or what copra_batch_schedule_seek set
@@ -207,18 +216,15 @@ struct copra_batch {
     // disturbance estimator of the tick (copra_batch_set_bias_estimator; copra_hip_plant.hip, plant_step.hpp)
     bool bias_on = false;
     int bias_dense = 0, bias_per_instance = 0;
-    const double* bias_gain = nullptr; // device: the caller's, or own_bias_gain
-    Dev<double> own_bias_gain; // the library's copy of a host gain
+    DevIn<double> bias_gain;
     Dev<double> d_bias; // [batch][nx]: the estimates; the controller's d (h->d) from the moment the estimator is turned on -- never own_d
     // state observer of the tick (copra_batch_set_observer; copra_hip_plant.hip, plant_step.hpp): x0 is the estimate while it is on
     bool obs_on = false;
     int obs_ny = 0, obs_per_instance = 0;
-    const double *obs_C = nullptr, *obs_Lx = nullptr, *obs_Ld = nullptr; // device: the caller's, or the copies below; obs_Ld null: d is not estimated
-    Dev<double> own_obs_C, own_obs_Lx, own_obs_Ld; // the library's copies of host arrays
+    DevIn<double> obs_C, obs_Lx, obs_Ld; // obs_Ld null: d is not estimated
     Dev<double> d_xp; // [batch][nx]: the plant's own state, from the first time the observer is turned on
     // noise drawn on the device (copra_batch_set_noise; copra_hip_plant.hip, plant_noise.hpp)
-    const double *noise_sw = nullptr, *noise_sv = nullptr; // device: the caller's, or the copies below; null: that stream is off
-    Dev<double> own_noise_sw, own_noise_sv; // the library's copies of host arrays
+    DevIn<double> noise_sw, noise_sv; // null: that stream is off
     int noise_per_instance = 0, noise_ny = 0; // (noise_ny: the observer's ny that noise_sv was given for)
     unsigned long long noise_seed = 0, noise_first = 0;
     unsigned long long noise_tick = 0; // plant steps since copra_batch_set_noise, or what copra_batch_noise_seek set
@@ -227,8 +233,7 @@ struct copra_batch {
     int score_dense = 0, score_per_instance = 0;
     long long score_ref_steps = 0;
     double score_tol = 0.0;
-    const double* score_arr[kScoreArrays] = {}; // qx, ru, x_ref, x_lo, x_hi, u_lo, u_hi -- device: the caller's, or the copies below; null: not given
-    Dev<double> own_score_arr[kScoreArrays]; // the library's copies of host arrays
+    DevIn<double> score_arr[kScoreArrays]; // qx, ru, x_ref, x_lo, x_hi, u_lo, u_hi; null: not given
     Dev<unsigned char> d_score; // [batch] records of 64 bytes
     Dev<double> d_score_u; // [batch][nu]: the tick's u_out where the caller gave none ...
     Dev<int> d_score_age; // ... and [batch] its age_out
@@ -238,12 +243,10 @@ struct copra_batch {
     bool target_on = false;
     int target_offset = 0, target_per_instance = 0;
     long long target_steps = 0;
-    const double *target_H = nullptr, *target_r = nullptr; // device: the caller's, or the copies below
-    Dev<double> own_target_H, own_target_r; // the library's copies of host arrays
+    DevIn<double> target_H, target_r;
     int target_ncost = 0; // the driven costs: their slot among the kernel-evaluated terms, the rows of one block, the map T_c
     int target_cost[kTargetCosts] = {}, target_rows[kTargetCosts] = {};
-    const double* target_map[kTargetCosts] = {};
-    Dev<double> own_target_map[kTargetCosts];
+    DevIn<double> target_map[kTargetCosts];
     Dev<double> d_target; // [batch][nx + nu]: z = [xs ; us]
     Dev<int> d_target_status; // [batch]: 1 where the last calculation found the instance singular
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
@@ -278,8 +281,8 @@ struct copra_batch {
     Dev<double> d_ws; // workgroup-per-instance kernel: [large_grid][ws_total] doubles (J, factor, Phi, ...)
     int large_grid = 0;
     // InitialStateLMPC variant
-    Dev<double> d_isR, d_isr, d_x0opt, own_x0lb, own_x0ub;
-    const double *x0lb = nullptr, *x0ub = nullptr;
+    Dev<double> d_isR, d_isr, d_x0opt;
+    DevIn<double> x0lb, x0ub;
     // stage-wise Riccati interior-point path (copra_batch_select_solver; lmpc_riccati.hpp)
     int solver = COPRA_SOLVER_DEFAULT;
     HostStagePlan hs;
@@ -326,20 +329,64 @@ inline int live_limit_windows(const copra_batch* h)
     return n;
 }
 
-// A new system (h->d) while the disturbance estimator is on: the estimates restart from its d -- copied on `s`, behind the last tick, into
-// the library's buffer, which stays the controller's d; the new d itself is only read.  The observer with a gain Ld estimates d the same way
+// What is launched on `s` next stands behind the handle's last stream, where that is another one (ev_plant is the event of this alone)
+inline copra_status_t order_behind_last(copra_batch* h, hipStream_t s)
+{
+    if (s == h->last_stream) return COPRA_OK;
+    if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
+    HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
+    return COPRA_OK;
+}
+
+// The library's estimates become the controller's d: d_bias, allocated on first use, is seeded on `s` from the d in force -- a caller's
+// buffer is read, never written
+inline copra_status_t adopt_bias_buffer(copra_batch* h, hipStream_t s)
+{
+    const FusedPlan& P = h->hp.plan;
+    if (!h->d_bias) OWN_TRY(h->d_bias.alloc((size_t)(P.batch > 0 ? P.batch : 1) * P.nx));
+    if (h->d == h->d_bias) return COPRA_OK;
+    const size_t nd = (size_t)P.batch * P.nx;
+    if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
+    h->d = h->d_bias;
+    return COPRA_OK;
+}
+
+// A new system (h->d) while the disturbance estimator is on: the estimates restart from its d -- copied on `s`, behind the last tick (which
+// may still write them), into the library's buffer, which stays the controller's d; the new d itself is only read.  The observer with a
+// gain Ld estimates d the same way
 inline copra_status_t bias_restart(copra_batch* h, hipStream_t s)
 {
     const bool estimates = h->bias_on || (h->obs_on && h->obs_Ld);
     if (!estimates || !h->d_bias || h->d == h->d_bias) return COPRA_OK;
-    const size_t nd = (size_t)h->hp.plan.batch * h->hp.plan.nx;
-    if (s != h->last_stream) { // (a tick that still writes the estimates)
-        if (!h->ev_plant) HIP_TRY(hipEventCreateWithFlags(&h->ev_plant, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(h->ev_plant, h->last_stream));
-        HIP_TRY(hipStreamWaitEvent(s, h->ev_plant, 0));
-    }
-    if (nd) HIP_TRY(hipMemcpyAsync(h->d_bias, h->d, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
-    h->d = h->d_bias;
+    const copra_status_t rc = order_behind_last(h, s);
+    return rc != COPRA_OK ? rc : adopt_bias_buffer(h, s);
+}
+
+// A caller's struct up to its struct_size, zero beyond it: fields the caller's version of the header does not know keep their defaults.
+// A null `src` reads as all zero
+template <class D, class S>
+copra_status_t read_sized(D& dst, const S* src, const char* who, const char* type_name, const char* init_name)
+{
+    static_assert(sizeof(D) >= sizeof(S), "the widest form of the struct");
+    std::memset(&dst, 0, sizeof dst);
+    if (!src) return COPRA_OK;
+    if (src->struct_size < (int)sizeof(int))
+        return fail(COPRA_ERR_ARG, std::string(who) + ": " + type_name + "::struct_size is not set (" + init_name + ")");
+    std::memcpy(&dst, src, (size_t)src->struct_size < sizeof dst ? (size_t)src->struct_size : sizeof dst);
+    return COPRA_OK;
+}
+
+// First use of the per-instance right-hand sides: every instance starts from the controller-wide ones
+inline copra_status_t ensure_row_f_inst(copra_batch* h)
+{
+    if (h->d_row_f_inst) return COPRA_OK;
+    const FusedPlan& P = h->hp.plan;
+    const size_t b = (size_t)(P.batch > 0 ? P.batch : 1);
+    OWN_TRY(h->d_row_f_inst.alloc(b * (size_t)P.mgen));
+    std::vector<double> rep(b * (size_t)P.mgen);
+    for (size_t i = 0; i < b; ++i) std::copy(h->hp.row_f.begin(), h->hp.row_f.begin() + P.mgen, rep.begin() + i * P.mgen);
+    HIP_TRY(hipMemcpy(h->d_row_f_inst, rep.data(), rep.size() * sizeof(double), hipMemcpyHostToDevice));
     return COPRA_OK;
 }
 
@@ -348,8 +395,11 @@ inline void target_drop_cost(copra_batch* h, int t)
 {
     for (int k = 0; k < h->target_ncost; ++k) {
         if (h->target_cost[k] != t) continue;
-        for (int q = k + 1; q < h->target_ncost; ++q)
-            h->target_cost[q - 1] = h->target_cost[q], h->target_rows[q - 1] = h->target_rows[q], h->target_map[q - 1] = h->target_map[q];
+        h->target_map[k].unset(); // (its copy goes to the end of the list, kept: a launch in flight may still read it)
+        for (int q = k + 1; q < h->target_ncost; ++q) {
+            h->target_cost[q - 1] = h->target_cost[q], h->target_rows[q - 1] = h->target_rows[q];
+            std::swap(h->target_map[q - 1], h->target_map[q]); // (the view and the copy travel together)
+        }
         h->target_ncost -= 1;
         return;
     }

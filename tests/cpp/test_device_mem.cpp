@@ -1,4 +1,5 @@
-// The owners of copra_amd/csrc/device_mem.hpp against a counting allocator: what they release, when, and what a failed attempt leaves.
+// The owners of copra_amd/csrc/device_mem.hpp against a counting allocator: what they release, when, and what a failed attempt leaves;
+// and DevArg, the borrowed-or-owned input array: which pointer is in force, when its copy grows, what a failed allocation or copy leaves.
 // Stand-alone (g++ -std=c++17 -fsanitize=address,undefined, no HIP): tests/test_device_mem.py builds and runs it.
 #include "../../copra_amd/csrc/device_mem.hpp"
 
@@ -8,10 +9,10 @@
 #include <map>
 #include <type_traits>
 
-struct Fake { // live blocks and bytes; the fail_at-th alloc from now on fails (1-based; 0: none)
+struct Fake { // live blocks and bytes; the fail_at-th alloc from now on fails (1-based; 0: none), and so does the copy_fail_at-th copy_in
     static std::map<void*, size_t> live;
     static size_t bytes;
-    static int allocs, releases, fail_at, copies;
+    static int allocs, releases, fail_at, copies, copy_fail_at;
     static int alloc(void** p, size_t n)
     {
         ++allocs;
@@ -35,6 +36,7 @@ struct Fake { // live blocks and bytes; the fail_at-th alloc from now on fails (
     static int copy_in(void* dst, const void* src, size_t n)
     {
         ++copies;
+        if (copy_fail_at > 0 && --copy_fail_at == 0) return 9;
         auto it = live.find(dst);
         if (it == live.end() || it->second < n) return 7;
         std::memcpy(dst, src, n);
@@ -43,7 +45,7 @@ struct Fake { // live blocks and bytes; the fail_at-th alloc from now on fails (
 };
 std::map<void*, size_t> Fake::live;
 size_t Fake::bytes = 0;
-int Fake::allocs = 0, Fake::releases = 0, Fake::fail_at = 0, Fake::copies = 0;
+int Fake::allocs = 0, Fake::releases = 0, Fake::fail_at = 0, Fake::copies = 0, Fake::copy_fail_at = 0;
 
 #define CHECK(c)                                                             \
     do {                                                                     \
@@ -58,6 +60,10 @@ using Buf = DevBuf<T, Fake>;
 static_assert(!std::is_copy_constructible<Buf<int>>::value && !std::is_copy_assignable<Buf<int>>::value, "move-only");
 static_assert(!std::is_copy_constructible<DevBag<Fake>>::value && !std::is_copy_assignable<DevBag<Fake>>::value, "move-only");
 static_assert(std::is_nothrow_move_constructible<Buf<int>>::value && std::is_nothrow_move_assignable<Buf<int>>::value, "cheap moves");
+template <class T>
+using Arg = DevArg<T, Fake>;
+static_assert(!std::is_copy_constructible<Arg<int>>::value && !std::is_copy_assignable<Arg<int>>::value, "move-only");
+static_assert(std::is_nothrow_move_constructible<Arg<int>>::value && std::is_nothrow_move_assignable<Arg<int>>::value, "cheap moves");
 
 static size_t nlive() { return Fake::live.size(); }
 
@@ -186,6 +192,122 @@ static void test_group()
     }
 }
 
+// A borrowed-or-owned input array: the view in force and the copy behind it
+static void test_arg_borrow_and_copy()
+{
+    const int r0 = Fake::releases;
+    {
+        Arg<double> a;
+        const double* p = a; // reads as the pointer in force
+        CHECK(!a && p == nullptr && a.get() == nullptr && !a.copy() && nlive() == 0); // default: unset, nothing held
+        a.unset(), a.reset();
+        CHECK(Fake::releases == r0);
+        const double host[6] = { 1.0, 2.0, 3.0, 4.0, 5.0, 6.0 };
+        const int a0 = Fake::allocs, c0 = Fake::copies;
+        CHECK(a.copy_in(host, 4) == 0 && a && a.get() == a.copy().get() && a.copy().count() == 4 && nlive() == 1);
+        CHECK(Fake::allocs == a0 + 1 && Fake::copies == c0 + 1 && a[0] == 1.0 && a[3] == 4.0);
+        const double* const block = a.copy().get();
+        double theirs[2] = { 7.0, 8.0 };
+        a.borrow(theirs); // the caller's array: the copy is kept for the next time
+        CHECK(a.get() == theirs && a[1] == 8.0 && a.copy().get() == block && a.copy().count() == 4 && nlive() == 1 && Fake::releases == r0);
+        CHECK(a.copy_in(host + 1, 3) == 0 && Fake::allocs == a0 + 1 && a.get() == block && a[0] == 2.0); // no larger: no allocation
+        CHECK(a.copy_in(host, 4) == 0 && Fake::allocs == a0 + 1 && a.get() == block);
+        CHECK(a.copy_in(host, 5) == 0 && Fake::allocs == a0 + 2 && Fake::releases == r0 + 1 && nlive() == 1); // too small: replaced
+        CHECK(a.get() == a.copy().get() && a.copy().count() == 5 && a[4] == 5.0 && Fake::bytes == 5 * sizeof(double));
+        a.borrow(nullptr); // (a null array borrowed is an array unset)
+        CHECK(!a && a.copy().count() == 5 && nlive() == 1);
+    }
+    CHECK(nlive() == 0 && Fake::releases == r0 + 2);
+}
+
+static void test_arg_empty_copy()
+{
+    Arg<double> a;
+    const int c0 = Fake::copies;
+    CHECK(a.copy_in(nullptr, 0) == 0 && a && a.copy().count() == 1 && nlive() == 1 && Fake::copies == c0); // an address, no copy call
+    const double* const block = a.get();
+    const int a0 = Fake::allocs;
+    CHECK(a.copy_in(nullptr, 0) == 0 && a.get() == block && Fake::allocs == a0 && Fake::copies == c0);
+    const double one = 4.0;
+    CHECK(a.copy_in(&one, 1) == 0 && a.get() == block && Fake::allocs == a0 && Fake::copies == c0 + 1 && a[0] == 4.0); // max(count, 1) is held
+}
+
+static void test_arg_failures()
+{
+    const double host[8] = { 1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 7.0, 8.0 };
+    double theirs[1] = { 0.0 };
+    for (int held = 0; held < 2; ++held) { // from nothing held, and from a copy in force that has to grow
+        Arg<double> a;
+        if (held) CHECK(a.copy_in(host, 2) == 0 && a && nlive() == 1);
+        Fake::fail_at = 1;
+        CHECK(a.copy_in(host, 8) == 2 && Fake::fail_at == 0); // the allocation fails: the view is null, the old block went first
+        CHECK(!a && a.get() == nullptr && !a.copy() && a.copy().count() == 0 && nlive() == 0 && Fake::bytes == 0);
+        CHECK(a.copy_in(host, 8) == 0 && a && a.get() == a.copy().get() && a[7] == 8.0 && nlive() == 1); // ... and the next attempt succeeds
+        a.borrow(theirs);
+        Fake::copy_fail_at = 1;
+        CHECK(a.copy_in(host, 8) == 9 && Fake::copy_fail_at == 0); // the copy fails: the view is null -- not the caller's array, not the
+        CHECK(!a && a.copy().count() == 8 && nlive() == 1 && Fake::bytes == 8 * sizeof(double)); // block half written --, the block is held
+        CHECK(a.copy_in(host, 3) == 0 && a.get() == a.copy().get() && a[2] == 3.0 && nlive() == 1);
+    }
+    CHECK(nlive() == 0);
+}
+
+static void test_arg_unset_and_reset()
+{
+    const double host[3] = { 1.0, 2.0, 3.0 };
+    Arg<double> a;
+    CHECK(a.copy_in(host, 3) == 0);
+    const double* const block = a.get();
+    const int r0 = Fake::releases, a0 = Fake::allocs;
+    a.unset(); // off: the copy stays
+    CHECK(!a && a.copy().get() == block && nlive() == 1 && Fake::releases == r0);
+    CHECK(a.copy_in(host, 3) == 0 && a.get() == block && Fake::allocs == a0);
+    a.reset(); // off: the copy goes
+    CHECK(!a && !a.copy() && nlive() == 0 && Fake::releases == r0 + 1);
+    a.reset();
+    CHECK(Fake::releases == r0 + 1);
+    CHECK(a.copy_in(host, 1) == 0 && a && Fake::allocs == a0 + 1);
+}
+
+// An entry of a list dropped as the engine drops a driven cost (target_drop_cost): the entries behind it move down by one, each view with
+// its own copy
+static void test_arg_moves()
+{
+    const double h0[2] = { 10.0, 11.0 }, h1[3] = { 20.0, 21.0, 22.0 }, h2[1] = { 30.0 };
+    double theirs[1] = { 40.0 };
+    {
+        Arg<double> m[3];
+        CHECK(m[0].copy_in(h0, 2) == 0 && m[1].copy_in(h1, 3) == 0 && m[2].copy_in(h2, 1) == 0 && nlive() == 3);
+        const double *const b1 = m[1].get(), *const b2 = m[2].get();
+        const int r0 = Fake::releases;
+        m[0] = std::move(m[1]); // by assignment: the target's copy goes, exactly once
+        CHECK(Fake::releases == r0 + 1 && nlive() == 2);
+        CHECK(m[0].get() == b1 && m[0].get() == m[0].copy().get() && m[0].copy().count() == 3 && m[0][2] == 22.0);
+        CHECK(!m[1] && !m[1].copy() && m[1].copy().count() == 0); // what was moved from is unset and holds nothing
+        m[1] = std::move(m[2]);
+        CHECK(Fake::releases == r0 + 1 && m[1].get() == b2 && m[1].get() == m[1].copy().get() && !m[2] && !m[2].copy());
+        Arg<double>& self = m[1];
+        m[1] = std::move(self); // self-move: harmless
+        CHECK(m[1].get() == b2 && m[1].copy().get() == b2 && nlive() == 2);
+        Arg<double> c(std::move(m[0]));
+        CHECK(c.get() == b1 && c.copy().get() == b1 && !m[0] && !m[0].copy() && nlive() == 2 && Fake::releases == r0 + 1);
+    }
+    CHECK(nlive() == 0);
+    {
+        Arg<double> m[3]; // ... and by swaps, as the engine does it: the dropped entry's copy ends up behind the list, kept
+        CHECK(m[0].copy_in(h0, 2) == 0 && m[1].copy_in(h1, 3) == 0 && m[2].copy_in(h2, 1) == 0);
+        const double *const b0 = m[0].get(), *const b1 = m[1].get();
+        m[2].borrow(theirs); // (a borrowed view travels too, with the copy it bypasses)
+        const double* const b2 = m[2].copy().get();
+        const int r0 = Fake::releases;
+        m[0].unset();
+        std::swap(m[0], m[1]), std::swap(m[1], m[2]);
+        CHECK(Fake::releases == r0 && nlive() == 3);
+        CHECK(m[0].get() == b1 && m[0].copy().get() == b1 && m[1].get() == theirs && m[1].copy().get() == b2 && !m[2] && m[2].copy().get() == b0);
+    }
+    CHECK(nlive() == 0); // every block once: a second release aborts in Fake::release
+}
+
 int main()
 {
     test_empty();
@@ -194,6 +316,13 @@ int main()
     test_moves();
     test_bag();
     test_group();
+    test_arg_borrow_and_copy();
+    test_arg_empty_copy();
+    CHECK(nlive() == 0);
+    test_arg_failures();
+    test_arg_unset_and_reset();
+    CHECK(nlive() == 0);
+    test_arg_moves();
     CHECK(nlive() == 0 && Fake::bytes == 0 && Fake::allocs > 0);
     std::printf("device_mem ok: %d allocations, %d releases, none live\n", Fake::allocs, Fake::releases);
     return 0;

@@ -173,3 +173,76 @@ def test_destroy_then_create_again(oracle):
         eng.solve()
         _against(eng.results(), ref, "a controller created after the others were destroyed")
         eng.close()
+
+
+def test_borrowed_then_copied_inputs_are_the_callers_arrays_bit_for_bit(oracle):
+    """case 7: the inputs a setter takes on the device (borrowed) or from the host (copied: DevIn in copra_amd/csrc/engine.hpp) -- the bias
+    gain, the observer's C / Lx / Ld, the noise sigmas, a control-bound schedule, the score's measure.  Controller X gets each as host arrays
+    given once, then as the caller's device tensors, then as host arrays per instance (the library's copy regrows after it was bypassed);
+    controller Y gets the same values as device tensors every time.  After one solve and one advance per step both hold the same bits --
+    they ran the same kernels on the same numbers -- and every solve of X meets the oracle at the file's bar.  The estimator and the
+    observer exclude each other: the three steps are walked once with each."""
+    import torch
+    from copra_amd import BatchLMPC
+    N, nx, nu, ny = 8, 4, 2, 2
+    wl = planar_integrator(B, N, v_max=2.0)  # (no velocity reaches its limit in six ticks: the noise pushes no state out of the feasible set;
+    rng = np.random.default_rng(7)  # the scheduled control bounds are active at most instances' first control at every step)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+    X, Y = (BatchLMPC(nx, nu, N, B, wl["costs"], wl["cstrs"]) for _ in range(2))
+    for e in (X, Y):
+        e.set_system(wl["A"], wl["B"], wl["d"], wl["x0"])
+    spread = rng.uniform(0.9, 1.1, B)  # what an instance's values differ by at the per-instance step
+    C0 = np.eye(nx)[:ny]
+    Lx0 = np.vstack([0.5 * np.eye(ny), np.eye(ny)])
+    Ld0 = np.vstack([np.zeros((ny, ny)), 0.05 * np.eye(ny)])
+    lo0, hi0 = np.array(wl["cstrs"][1]["lower"]), np.array(wl["cstrs"][1]["upper"])
+    blocks = 5  # (fewer than N: the window's last steps read the last block)
+    step_no = 0
+    for mode in ("estimator", "observer"):
+        for form in ("host", "device", "host per instance"):
+            step_no += 1
+            per = form == "host per instance"
+            s = 1.0 + 0.1 * step_no  # other values at every step: a copy left over from an earlier one would show
+            lead = spread[:, None] if per else 1.0
+            lead3 = spread[:, None, None] if per else 1.0
+            give = (lambda a: a) if form != "device" else dev  # X's form; Y's is dev
+            give_T = lambda f, a: f(np.swapaxes(a, -1, -2)) if f is dev else a  # (matrices: tensors are in the ABI's column-major)
+            fade = (1.0 - 0.04 * np.arange(blocks))[:, None]
+            lo, hi = lead3 * s * 0.6 * fade * lo0, lead3 * s * 0.6 * fade * hi0
+            qx, ru = lead * s * np.array([1.0, 2.0, 0.5, 0.25]), lead * s * np.array([0.1, 0.2])
+            x_lo, x_hi = lead * -0.3 * s * np.ones(nx), lead * 0.3 * s * np.ones(nx)
+            sw = lead * s * np.array([1e-3, 1e-3, 5e-4, 5e-4])
+            sv = lead * s * np.array([1e-3, 2e-3])
+            for e, f in ((X, give), (Y, dev)):
+                if mode == "estimator":
+                    e.set_bias_estimator(f(lead * s * np.full(nx, 0.3)))
+                    e.set_noise(11, process=f(sw))
+                else:
+                    e.set_observer(give_T(f, lead3 * s * C0), give_T(f, lead3 / s * Lx0), give_T(f, lead3 * s * Ld0))
+                    e.set_noise(11, process=f(sw), sensor=f(sv))
+                e.set_control_bound_schedule(f(lo), f(hi))
+                e.set_score(f(qx), f(ru), None, (f(x_lo), f(x_hi)))
+            tau = X.schedule_tick()
+            assert tau == step_no - 1 == Y.schedule_tick()
+            x, d = X.state(), X.bias()
+            X.solve()
+            Y.solve()
+            at = np.minimum(tau + np.arange(N), blocks - 1)
+            lo_w = (lo[:, at] if per else np.broadcast_to(lo[at], (B, N, nu))).reshape(B, N * nu)
+            hi_w = (hi[:, at] if per else np.broadcast_to(hi[at], (B, N, nu))).reshape(B, N * nu)
+            limits = lambda k: [wl["cstrs"][0], dict(kind="control_bound", lower=lo_w[k], upper=hi_w[k])]
+            what = "%s, %s" % (mode, form)
+            _against(X.results(), _one_by_one(oracle, dict(wl, d=d), N, lambda k: wl["costs"], limits, x0=x), what)
+            X.advance()
+            Y.advance()
+            assert X.state().tobytes() == Y.state().tobytes(), what
+            assert X.bias().tobytes() == Y.bias().tobytes(), what
+            assert not np.array_equal(X.bias(), d), what  # (the gain and the noise moved the estimates: the comparison is of something)
+            if mode == "observer":
+                assert X.plant_state().tobytes() == Y.plant_state().tobytes(), what
+            sx, sy = X.score(), Y.score()
+            assert sx.tobytes() == sy.tobytes() and (sx["ticks"] == 1).all(), what
+        for e in (X, Y):
+            e.set_bias_estimator(None)
+    X.close()
+    Y.close()

@@ -1,5 +1,6 @@
 """copra_amd/csrc/device_mem.hpp, the owners of device and pinned memory, on the host: tests/cpp/test_device_mem.cpp drives them with a
-counting allocator (what is released and when, what a failed attempt leaves behind) under AddressSanitizer and UBSan.  The program is an
+counting allocator (what is released and when, what a failed attempt leaves behind; for DevArg, the borrowed-or-copied input array, which
+pointer is in force and when its copy grows) under AddressSanitizer and UBSan.  The program is an
 executable of its own: g++ only, no HIP, no GPU."""
 import os
 import subprocess
