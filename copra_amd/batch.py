@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _args, _capi
 
 
 def to_abi_layout(A, B, d, x0):
@@ -22,10 +22,6 @@ def to_abi_layout(A, B, d, x0):
     Ab = np.ascontiguousarray(np.transpose(A, (0, 2, 1)))
     Bb = np.ascontiguousarray(np.transpose(B, (0, 2, 1)))
     return Ab, Bb, np.ascontiguousarray(d, dtype=np.float64), np.ascontiguousarray(x0, dtype=np.float64)
-
-
-def _is_torch(t):
-    return type(t).__module__.startswith("torch")
 
 
 class BatchLMPC:
@@ -39,14 +35,18 @@ class BatchLMPC:
         self.n = self.nu * self.N
         self.X = self.nx * (self.N + 1)
         self._keep = []
-        self._ref_keep = {}  # torch tensors used in place as per-instance cost references, by cost index
-        self._w_keep = {}  # ... and as per-instance cost weights
-        self._sched_keep = {}  # ... and as reference schedules (set_reference_schedule)
-        self._bias_keep = None  # ... and as the disturbance estimator's gain (set_bias_estimator)
-        self._obs_keep, self._ny = None, 0  # ... and as the observer's C and gains (set_observer); its number of outputs, 0: off
-        self._noise_keep = None  # ... and as the standard deviations of the noise drawn on the device (set_noise)
-        self._limit_keep = {}  # ... and as limit schedules: by constraint index (set_constraint_schedule), "bounds" (set_control_bound_schedule)
-        self._target_keep = None  # ... and as the outputs, the setpoint and the maps of the steady-state targets (set_target)
+        # The tensors the library reads or writes in place, by slot; a setter fills its slot AFTER the library accepted the call (a refused
+        # call leaves the tensors in force alive) and a host copy or None in a tensor's place empties it (_hold).  What else ends a slot:
+        #   "system", "x0", "outputs", "tick"   only their own next call
+        #   "bias", "noise", "score"            X(None)
+        #   "observer", "target"                X(None); set_shared_system (the library ends both)
+        #   ("reference", k)                    set_cost_reference(k, ..); set_reference_schedule(k, ..); set_target(.., costs with k)
+        #   ("weights", k)                      set_cost_weights(k, None)
+        #   ("schedule", k)                     set_reference_schedule(k, None); set_cost_reference(k, ..)
+        #   ("limit", k)                        set_constraint_schedule(k, None); set_constraint_rhs(k, ..)
+        #   ("limit", "bounds")                 set_control_bound_schedule(None, None); set_control_bounds(..)
+        self._held = {}
+        self._ny = 0  # the observer's number of outputs (set_observer), 0: off
         self._costs = list(costs)  # the cost dicts as given: set_target builds the maps [M N] of the driven costs from them
         cc = _capi.pack_costs(costs, self._keep)
         # rows per cost as created: what a per-instance weight vector holds (None: a dense cost, which the library refuses)
@@ -63,8 +63,18 @@ class BatchLMPC:
             isd = C.byref(_capi.InitialStateDesc(_capi.dptr(Rm), _capi.dptr(rv)))
         _capi.check(self._lib.copra_batch_create_with_options(C.byref(self._h), C.byref(dims), len(costs), cc, len(cstrs), kk, isd,
                                                               C.byref(opts)))
-        self._sys = None
-        self._outs = None
+
+    def _hold(self, slot, *args):
+        """slot <- the tensors among the _args.Arg records `args` (one record: its tensor itself); host copies and None only: emptied"""
+        owners = [a.owner for a in args if a is not None and a.on_device]
+        if owners:
+            self._held[slot] = owners[0] if len(args) == 1 else owners
+        else:
+            self._held.pop(slot, None)
+
+    def _release(self, *slots):
+        for slot in slots:
+            self._held.pop(slot, None)
 
     def specialise(self, cache_dir=None, lint=True):
         """compile this controller's shape into its own kernels (hipcc --genco, cached); see copra_batch_specialise.
@@ -141,63 +151,61 @@ class BatchLMPC:
             pass
 
     # PreviewSystem::system for every instance
+    def _system(self, what, A, B, d, x0, matrix):
+        """the four records of a system and their on_device; host arrays must have the system's shapes (a tensor's shape is not checked)"""
+        b, nx, nu = self.batch, self.nx, self.nu
+        args = [_args.marshal(a, what, matrix=matrix and i < 2) for i, a in enumerate((A, B, d, x0))]
+        on_device, _ = _args.same_way(what, args)
+        if not on_device:
+            for a, shape in zip(args, ((b, nx, nx), (b, nx, nu), (b, nx), (b, nx))):
+                _args.expect(a, shape, what)
+        return args, on_device
+
     def set_system(self, A, B, d, x0):
-        if _is_torch(A):
-            self._sys = (A, B, d, x0)  # keep alive; used in place
-            for t in self._sys:
-                assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64"
-            _capi.check(self._lib.copra_batch_set_system(self._h, A.data_ptr(), B.data_ptr(), d.data_ptr(),
-                                                         x0.data_ptr(), 1))
-        else:
-            Ab, Bb, db, xb = to_abi_layout(A, B, d, x0)
-            assert Ab.shape == (self.batch, self.nx, self.nx) and Bb.shape == (self.batch, self.nu, self.nx)
-            assert db.shape == (self.batch, self.nx) and xb.shape == (self.batch, self.nx)
-            _capi.check(self._lib.copra_batch_set_system(self._h, Ab.ctypes.data, Bb.ctypes.data, db.ctypes.data,
-                                                         xb.ctypes.data, 0))
+        args, on_device = self._system("set_system", A, B, d, x0, True)
+        _capi.check(self._lib.copra_batch_set_system(self._h, *[a.ptr for a in args], on_device))
+        self._hold("system", *args)
 
     def set_system_rowmajor_async(self, A, B, d, x0, stream=None):
         """torch CUDA tensors in numpy's natural (row-major) indexing, (b,nx,nx), (b,nx,nu), (b,nx), (b,nx): the library
         transposes A and B on `stream` (an integer hipStream_t handle); nothing blocks the host"""
-        self._sys = (A, B, d, x0)
-        for t in self._sys:
-            assert t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch.float64"
-        _capi.check(self._lib.copra_batch_set_system_rowmajor_async(self._h, A.data_ptr(), B.data_ptr(), d.data_ptr(), x0.data_ptr(),
-                                                                    C.c_void_p(stream or 0)))
+        args, on_device = self._system("set_system_rowmajor_async", A, B, d, x0, False)
+        if not on_device:
+            raise ValueError("set_system_rowmajor_async: contiguous CUDA float64 tensors are needed")
+        _capi.check(self._lib.copra_batch_set_system_rowmajor_async(self._h, *[a.ptr for a in args], C.c_void_p(stream or 0)))
+        self._hold("system", *args)
 
     # PreviewSystem::xInit for every instance
     def set_shared_system(self, A, B, d):
         """Shared-model receding-horizon fast path: ONE system (A (nx,nx), B (nx,nu), d (nx)) for the whole batch;
         the per-instance initial states come from set_x0.  The factorisation is done once, at the next solve()."""
-        Ac = np.ascontiguousarray(np.asarray(A, dtype=np.float64).T)  # column-major
-        Bc = np.ascontiguousarray(np.asarray(B, dtype=np.float64).T)
-        dc = np.ascontiguousarray(d, dtype=np.float64)
-        _capi.check(self._lib.copra_batch_set_shared_system(self._h, Ac.ctypes.data, Bc.ctypes.data, dc.ctypes.data, 0))
-        self._obs_keep, self._ny = None, 0  # (the library ends the observer)
-        self._target_keep = None  # ... and the steady-state targets
+        args = [_args.marshal(np.asarray(a), "set_shared_system", matrix=m) for a, m in ((A, True), (B, True), (d, False))]  # (host only)
+        _capi.check(self._lib.copra_batch_set_shared_system(self._h, *[a.ptr for a in args], 0))
+        self._ny = 0
+        self._release("observer", "target")  # (the library ends the observer and the steady-state targets)
 
     def set_cost_reference(self, cost_index, p):
         """per-instance reference of cost `cost_index`: p of shape (batch, rows) (numpy, or a torch CUDA tensor used in
         place); p of shape (rows,): ONE new reference for every instance (copra_batch_set_cost_reference_all: copied); None
         restores the controller-wide reference given at creation"""
-        self._ref_keep.pop(int(cost_index), None)  # one slot per cost: the previous tensor is released
-        self._sched_keep.pop(int(cost_index), None)  # (the library ends the cost's schedule, and takes the cost off the targets' list)
-        if p is not None and getattr(p, "ndim", np.ndim(p)) == 1:
-            if _is_torch(p):
-                assert p.is_cuda and p.is_contiguous() and str(p.dtype) == "torch.float64"
-                _capi.check(self._lib.copra_batch_set_cost_reference_all(self._h, int(cost_index), p.data_ptr(), 1))
-            else:
-                pb = np.ascontiguousarray(p, dtype=np.float64)
-                _capi.check(self._lib.copra_batch_set_cost_reference_all(self._h, int(cost_index), pb.ctypes.data, 0))
-            return
-        if p is None:
-            _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), None, 0))
-        elif _is_torch(p):
-            self._ref_keep[int(cost_index)] = p
-            _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), p.data_ptr(), 1))
+        k, what = int(cost_index), "set_cost_reference"
+        arg = _args.marshal(p, what)
+        one = arg is not None and len(arg.shape) == 1
+        if arg is not None:
+            rows = self._cost_rows[k] if 0 <= k < len(self._cost_rows) else None  # (None: the library refuses the cost)
+            if arg.on_device and rows is not None:  # (the kernels read that many doubles from the tensor)
+                _args.expect(arg, (rows,) if one else (self.batch, rows), what)
+            elif not one and arg.shape[:1] != (self.batch,):
+                raise _capi.CopraDomainError("%s: expected (%d, rows), got %s" % (what, self.batch, arg.shape))
+        if one:  # (copied also from a tensor: the library waits for its broadcast before it returns)
+            _capi.check(self._lib.copra_batch_set_cost_reference_all(self._h, k, arg.ptr, arg.on_device))
+            arg = None
+        elif arg is None:
+            _capi.check(self._lib.copra_batch_set_cost_reference(self._h, k, None, 0))
         else:
-            pb = np.ascontiguousarray(p, dtype=np.float64)
-            assert pb.shape[0] == self.batch
-            _capi.check(self._lib.copra_batch_set_cost_reference(self._h, int(cost_index), pb.ctypes.data, 0))
+            _capi.check(self._lib.copra_batch_set_cost_reference(self._h, k, arg.ptr, arg.on_device))
+        self._hold(("reference", k), arg)  # one slot per cost: the previous tensor is released
+        self._release(("schedule", k))  # (the library ends the cost's schedule, and takes the cost off the targets' list)
 
     def cost_reference(self, cost_index):
         """the per-instance reference of cost `cost_index` in force, (batch, rows of the cost), as a numpy copy (copra_batch_get_cost_reference:
@@ -220,40 +228,12 @@ class BatchLMPC:
         k, r = int(cost_index), int(rows_per_step)
         if schedule is None:
             _capi.check(self._lib.copra_batch_set_reference_schedule(self._h, k, None, 0, 0, 0, 0, 0))
-            self._sched_keep.pop(k, None)
+            self._release(("schedule", k))
             return
-        torch_in = _is_torch(schedule)
-        if torch_in:
-            if not (schedule.is_cuda and schedule.is_contiguous() and str(schedule.dtype) == "torch.float64"):
-                raise ValueError("set_reference_schedule: a contiguous CUDA float64 tensor is needed")
-            sb, ptr = schedule, schedule.data_ptr()
-        else:
-            sb = np.ascontiguousarray(schedule, dtype=np.float64)
-            ptr = sb.ctypes.data
-        shape = tuple(sb.shape)
-        if len(shape) not in (2, 3) or shape[-1] != r or (len(shape) == 3 and shape[0] != self.batch):
-            raise _capi.CopraDomainError("set_reference_schedule: expected (steps, %d) or (%d, steps, %d), got %s" % (r, self.batch, r, shape))
-        _capi.check(self._lib.copra_batch_set_reference_schedule(self._h, k, ptr, shape[-2], r, int(offset), 1 if len(shape) == 3 else 0,
-                                                                 1 if torch_in else 0))
-        self._ref_keep.pop(k, None)  # (the cost's reference is the library's window now)
-        self._sched_keep.pop(k, None)
-        if torch_in:
-            self._sched_keep[k] = schedule
-
-    def _limit_schedule(self, schedule, r, what):
-        """(pointer, steps, per_instance, on_device, the tensor to keep alive or None) of a limit schedule (steps, r) or (batch, steps, r)"""
-        torch_in = _is_torch(schedule)
-        if torch_in:
-            if not (schedule.is_cuda and schedule.is_contiguous() and str(schedule.dtype) == "torch.float64"):
-                raise ValueError("%s: a contiguous CUDA float64 tensor is needed" % what)
-            sb, ptr = schedule, schedule.data_ptr()
-        else:
-            sb = np.ascontiguousarray(schedule, dtype=np.float64)
-            ptr = sb.ctypes.data
-        shape = tuple(sb.shape)
-        if len(shape) not in (2, 3) or shape[-1] != r or (len(shape) == 3 and shape[0] != self.batch):
-            raise _capi.CopraDomainError("%s: expected (steps, %d) or (%d, steps, %d), got %s" % (what, r, self.batch, r, shape))
-        return ptr, shape[-2], 1 if len(shape) == 3 else 0, 1 if torch_in else 0, sb
+        arg, steps, per = _args.signal(schedule, r, self.batch, False, "set_reference_schedule")
+        _capi.check(self._lib.copra_batch_set_reference_schedule(self._h, k, arg.ptr, steps, r, int(offset), per, arg.on_device))
+        self._release(("reference", k))  # (the cost's reference is the library's window now)
+        self._hold(("schedule", k), arg)
 
     def set_constraint_schedule(self, cstr_index, schedule, rows_per_step, offset=0, preview=True):
         """The right-hand side f of the Trajectory / Control / Mixed constraint `cstr_index` follows a signal (copra_batch_set_constraint_schedule):
@@ -266,13 +246,11 @@ class BatchLMPC:
         k, r = int(cstr_index), int(rows_per_step)
         if schedule is None:
             _capi.check(self._lib.copra_batch_set_constraint_schedule(self._h, k, None, 0, 0, 0, 0, 0, 0))
-            self._limit_keep.pop(k, None)
+            self._release(("limit", k))
             return
-        ptr, steps, per, dev, sb = self._limit_schedule(schedule, r, "set_constraint_schedule")
-        _capi.check(self._lib.copra_batch_set_constraint_schedule(self._h, k, ptr, steps, r, int(offset), 1 if preview else 0, per, dev))
-        self._limit_keep.pop(k, None)
-        if dev:
-            self._limit_keep[k] = sb
+        arg, steps, per = _args.signal(schedule, r, self.batch, False, "set_constraint_schedule")
+        _capi.check(self._lib.copra_batch_set_constraint_schedule(self._h, k, arg.ptr, steps, r, int(offset), 1 if preview else 0, per, arg.on_device))
+        self._hold(("limit", k), arg)
 
     def set_control_bound_schedule(self, lower, upper, offset=0, preview=True):
         """The bounds of the controller's ControlBoundConstraint follow two signals (copra_batch_set_control_bound_schedule): lower and upper of
@@ -281,18 +259,18 @@ class BatchLMPC:
         schedule and keeps the last window; set_control_bounds ends it too."""
         if lower is None and upper is None:
             _capi.check(self._lib.copra_batch_set_control_bound_schedule(self._h, None, None, 0, 0, 0, 0, 0))
-            self._limit_keep.pop("bounds", None)
+            self._release(("limit", "bounds"))
             return
+        what = "set_control_bound_schedule"
         if lower is None or upper is None:
-            raise ValueError("set_control_bound_schedule: both of lower and upper are needed (None, None ends the schedule)")
-        lp, steps, per, dev, lb = self._limit_schedule(lower, self.nu, "set_control_bound_schedule")
-        up, steps_u, per_u, dev_u, ub = self._limit_schedule(upper, self.nu, "set_control_bound_schedule")
-        if (steps, per, dev) != (steps_u, per_u, dev_u):
-            raise _capi.CopraDomainError("set_control_bound_schedule: lower and upper differ in shape or in where they live")
-        _capi.check(self._lib.copra_batch_set_control_bound_schedule(self._h, lp, up, steps, int(offset), 1 if preview else 0, per, dev))
-        self._limit_keep.pop("bounds", None)
-        if dev:
-            self._limit_keep["bounds"] = (lb, ub)
+            raise ValueError("%s: both of lower and upper are needed (None, None ends the schedule)" % what)
+        lo, steps, per = _args.signal(lower, self.nu, self.batch, False, what)
+        up, steps_u, per_u = _args.signal(upper, self.nu, self.batch, False, what)
+        if steps != steps_u or lo.on_device != up.on_device:
+            raise _capi.CopraDomainError("%s: lower and upper differ in shape or in where they live" % what)
+        on_device, per = _args.same_way(what, (lo, up), (per, per_u))
+        _capi.check(self._lib.copra_batch_set_control_bound_schedule(self._h, lo.ptr, up.ptr, steps, int(offset), 1 if preview else 0, per, on_device))
+        self._hold(("limit", "bounds"), lo, up)
 
     def schedule_seek(self, tick):
         """the controller's tick counter <- tick, the windows of all scheduled costs and limits rewritten (copra_batch_schedule_seek; asynchronous)"""
@@ -306,56 +284,44 @@ class BatchLMPC:
         """per-instance weights of cost `cost_index` (copra_batch_set_cost_weights): w of shape (batch, rows) with the rows of that
         cost as created (numpy: copied; a torch CUDA float64 tensor: used in place and kept alive -- changing it changes the next
         solve); w of shape (rows,): the same weights for every instance; None restores the weights given at creation"""
-        self._w_keep.pop(int(cost_index), None)  # one slot per cost: the previous tensor is released
-        if w is None:
-            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), None, 0))
-        elif _is_torch(w):
-            assert w.is_cuda and str(w.dtype) == "torch.float64"
-            if w.ndim == 1:
-                w = w.unsqueeze(0).expand(self.batch, -1)
-            w = w.contiguous()
-            rows = self._cost_rows[int(cost_index)]
-            if rows is not None and tuple(w.shape) != (self.batch, rows):  # (the kernels read batch x rows doubles from it)
-                raise _capi.CopraDomainError("set_cost_weights: expected (%d, %d), got %s" % (self.batch, self._cost_rows[int(cost_index)], tuple(w.shape)))
-            self._w_keep[int(cost_index)] = w
-            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), w.data_ptr(), 1))
-        else:
-            wb = np.asarray(w, dtype=np.float64)
-            if wb.ndim == 1:
-                wb = np.broadcast_to(wb, (self.batch, wb.shape[0]))
-            wb = np.ascontiguousarray(wb)
-            rows = self._cost_rows[int(cost_index)]
-            if rows is not None and wb.shape != (self.batch, rows):
-                raise _capi.CopraDomainError("set_cost_weights: expected (%d, %d), got %s" % (self.batch, self._cost_rows[int(cost_index)], wb.shape))
-            _capi.check(self._lib.copra_batch_set_cost_weights(self._h, int(cost_index), wb.ctypes.data, 0))
+        k, what = int(cost_index), "set_cost_weights"
+        if w is not None and getattr(w, "ndim", np.ndim(w)) == 1:  # the same weights for every instance: written out
+            w = w.unsqueeze(0).expand(self.batch, -1) if _args.is_torch(w) else np.broadcast_to(w, (self.batch, len(w)))
+        if _args.is_torch(w):
+            w = w.contiguous()  # (a copy where it was not: that copy is what the library reads, and what is kept)
+        arg = _args.marshal(w, what)
+        if arg is not None and self._cost_rows[k] is not None:  # (the kernels read batch x rows doubles from it)
+            _args.expect(arg, (self.batch, self._cost_rows[k]), what)
+        _capi.check(self._lib.copra_batch_set_cost_weights(self._h, k, arg and arg.ptr, arg.on_device if arg else 0))
+        self._hold(("weights", k), arg)  # one slot per cost: the previous tensor is released
 
     def set_constraint_rhs(self, cstr_index, f):
         """per-instance right-hand side f (batch, rows) of the Trajectory / Control / Mixed constraint `cstr_index`"""
-        fb = np.ascontiguousarray(f, dtype=np.float64)
-        assert fb.shape[0] == self.batch
-        _capi.check(self._lib.copra_batch_set_constraint_rhs(self._h, int(cstr_index), fb.ctypes.data, 0))
-        self._limit_keep.pop(int(cstr_index), None)  # (the library ends the constraint's schedule)
+        arg = _args.marshal(np.asarray(f), "set_constraint_rhs")  # (host only)
+        if arg.shape[:1] != (self.batch,):
+            raise _capi.CopraDomainError("set_constraint_rhs: expected (%d, rows), got %s" % (self.batch, arg.shape))
+        _capi.check(self._lib.copra_batch_set_constraint_rhs(self._h, int(cstr_index), arg.ptr, 0))
+        self._release(("limit", int(cstr_index)))  # (the library ends the constraint's schedule)
+
+    def _bounds(self, lower, upper, cols):
+        """host copies of lower / upper broadcast to (batch, cols)"""
+        return [_args.marshal(np.broadcast_to(a, (self.batch, cols)), "bounds") for a in (lower, upper)]
 
     def set_control_bounds(self, lower, upper):
         """per-instance ControlBoundConstraint: lower / upper broadcastable to (batch, nu * N)"""
-        lo = np.ascontiguousarray(np.broadcast_to(lower, (self.batch, self.n)), dtype=np.float64)
-        up = np.ascontiguousarray(np.broadcast_to(upper, (self.batch, self.n)), dtype=np.float64)
-        _capi.check(self._lib.copra_batch_set_control_bounds(self._h, lo.ctypes.data, up.ctypes.data, 0))
-        self._limit_keep.pop("bounds", None)  # (the library ends the bound schedule)
+        lo, up = self._bounds(lower, upper, self.n)
+        _capi.check(self._lib.copra_batch_set_control_bounds(self._h, lo.ptr, up.ptr, 0))
+        self._release(("limit", "bounds"))  # (the library ends the bound schedule)
 
     def set_x0(self, x0):
-        if _is_torch(x0):
-            self._x0 = x0
-            _capi.check(self._lib.copra_batch_set_x0(self._h, x0.data_ptr(), 1))
-        else:
-            xb = np.ascontiguousarray(x0, dtype=np.float64)
-            _capi.check(self._lib.copra_batch_set_x0(self._h, xb.ctypes.data, 0))
+        arg = _args.expect(_args.marshal(x0, "set_x0"), (self.batch, self.nx), "set_x0")
+        _capi.check(self._lib.copra_batch_set_x0(self._h, arg.ptr, arg.on_device))
+        self._hold("x0", arg)
 
     # InitialStateLMPC::resetInitialStateBounds, per instance
     def set_initial_state_bounds(self, x0lb, x0ub):
-        lo = np.ascontiguousarray(np.broadcast_to(x0lb, (self.batch, self.nx)), dtype=np.float64)
-        up = np.ascontiguousarray(np.broadcast_to(x0ub, (self.batch, self.nx)), dtype=np.float64)
-        _capi.check(self._lib.copra_batch_set_initial_state_bounds(self._h, lo.ctypes.data, up.ctypes.data, 0))
+        lo, up = self._bounds(x0lb, x0ub, self.nx)
+        _capi.check(self._lib.copra_batch_set_initial_state_bounds(self._h, lo.ptr, up.ptr, 0))
 
     # InitialStateLMPC::initialState()
     def initial_state(self):
@@ -365,7 +331,7 @@ class BatchLMPC:
 
     def set_outputs(self, control, trajectory, status, iters):
         """torch CUDA tensors (float64 [b,n], float64 [b,X], int32 [b], int32 [b,2]) that receive the results"""
-        self._outs = (control, trajectory, status, iters)
+        self._held["outputs"] = (control, trajectory, status, iters)
         _capi.check(self._lib.copra_batch_set_outputs(self._h, control.data_ptr(), trajectory.data_ptr(),
                                                       status.data_ptr(), iters.data_ptr()))
 
@@ -393,29 +359,24 @@ class BatchLMPC:
 
     # ---- the receding-horizon tick (copra_batch_advance / copra_batch_rollout): u = control().head(nu); x = plant(x, u); xInit(x) ----
     def _device(self, a, shape, what, dtype="float64"):
-        """a device pointer for `a`, which must have `shape`: a torch CUDA tensor is used in place, anything else is copied to the device
-        (through torch); (pointer, the object that keeps the memory alive)"""
+        """the _args.Arg of `a` on the device (None: None), which must have `shape`: a torch CUDA tensor is used in place, anything else is
+        copied to the device (through torch) -- the tick's arrays are device-only"""
         if a is None:
-            return None, None
-        if _is_torch(a):
-            if not (a.is_cuda and a.is_contiguous() and str(a.dtype) == "torch." + dtype):
-                raise ValueError("%s: a contiguous CUDA %s tensor is needed" % (what, dtype))
-            t = a
-        else:
+            return None
+        arg = _args.marshal(a, what, dtype)
+        if not arg.on_device:
             import torch
-            t = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-        if tuple(t.shape) != tuple(shape):
-            raise _capi.CopraDomainError("%s: expected %s, got %s" % (what, tuple(shape), tuple(t.shape)))
-        return t.data_ptr(), t
+            arg = _args.marshal(torch.from_numpy(arg.owner).cuda(), what, dtype)
+        return _args.expect(arg, shape, what)
 
     def _output(self, a, shape, what, dtype="float64"):
         """an output of the tick: a torch CUDA tensor written in place; True: one is allocated here"""
         if a is None or a is False:
-            return None, None
+            return None
         if a is True:
             import torch
             a = torch.empty(tuple(shape), dtype=getattr(torch, dtype), device="cuda")
-        elif not _is_torch(a):
+        elif not _args.is_torch(a):
             raise ValueError("%s: outputs stay on the device -- a torch CUDA tensor (or True: allocated for you)" % what)
         return self._device(a, shape, what, dtype)
 
@@ -437,46 +398,17 @@ class BatchLMPC:
         set_shared_system ends the estimator."""
         if gain is None:
             _capi.check(self._lib.copra_batch_set_bias_estimator(self._h, None, 0, 0, 0))
-            self._bias_keep = None
+            self._release("bias")
             return
-        b, nx = self.batch, self.nx
-        torch_in = _is_torch(gain)
-        if torch_in:
-            if not (gain.is_cuda and gain.is_contiguous() and str(gain.dtype) == "torch.float64"):
-                raise ValueError("set_bias_estimator: a contiguous CUDA float64 tensor is needed")
-            g = gain
-        else:
-            g = np.asarray(gain, dtype=np.float64)
-        shape = tuple(g.shape)
-        if shape == (nx,):
-            dense, per = 0, 0
-        elif shape == (nx, nx):
-            dense, per = 1, 0
-        elif shape == (b, nx):
-            dense, per = 0, 1
-        elif shape == (b, nx, nx):
-            dense, per = 1, 1
-        else:
-            raise _capi.CopraDomainError("set_bias_estimator: expected (%d,), (%d, %d), (%d, %d) or (%d, %d, %d), got %s" % (nx, b, nx, nx, nx, b, nx, nx, shape))
-        if torch_in:
-            ptr = g.data_ptr()
-        else:
-            g = np.ascontiguousarray(np.swapaxes(g, -1, -2) if dense else g)
-            ptr = g.ctypes.data
-        _capi.check(self._lib.copra_batch_set_bias_estimator(self._h, ptr, dense, per, 1 if torch_in else 0))
-        self._bias_keep = gain if torch_in else None
+        arg, dense, per = _args.weight(gain, self.nx, self.batch, "set_bias_estimator")
+        _capi.check(self._lib.copra_batch_set_bias_estimator(self._h, arg.ptr, dense, per, arg.on_device))
+        self._hold("bias", arg)
 
     def set_bias(self, d):
         """restart the estimates (copra_batch_set_bias): d of shape (batch, nx), numpy (copied) or a torch CUDA float64 tensor (copied on the
         stream of the last tick)"""
-        if _is_torch(d):
-            ptr, _ = self._device(d, (self.batch, self.nx), "set_bias")
-            _capi.check(self._lib.copra_batch_set_bias(self._h, ptr, 1))
-        else:
-            db = np.ascontiguousarray(d, dtype=np.float64)
-            if db.shape != (self.batch, self.nx):
-                raise _capi.CopraDomainError("set_bias: expected %s, got %s" % ((self.batch, self.nx), db.shape))
-            _capi.check(self._lib.copra_batch_set_bias(self._h, db.ctypes.data, 0))
+        arg = _args.expect(_args.marshal(d, "set_bias"), (self.batch, self.nx), "set_bias")
+        _capi.check(self._lib.copra_batch_set_bias(self._h, arg.ptr, arg.on_device))
 
     def bias(self):
         """the d the next solve reads, (batch, nx), as a numpy copy (copra_batch_get_bias: waits for the last tick): the estimates while the
@@ -500,53 +432,31 @@ class BatchLMPC:
         and keeps every state; C_out None ends the observer.  Excludes set_bias_estimator; set_shared_system ends it."""
         if C_out is None:
             _capi.check(self._lib.copra_batch_set_observer(self._h, 0, None, None, None, 0, 0))
-            self._obs_keep, self._ny = None, 0
+            self._release("observer")
+            self._ny = 0
             return
         if Lx is None:
             raise ValueError("set_observer: C needs a gain Lx")
         b, nx = self.batch, self.nx
-        given = [m for m in (C_out, Lx, Ld) if m is not None]
-        torch_in = _is_torch(given[0])
-        if any(_is_torch(m) != torch_in for m in given):
-            raise ValueError("set_observer: C, Lx and Ld are all numpy or all torch CUDA tensors")
-        if torch_in:
-            for m in given:
-                if not (m.is_cuda and m.is_contiguous() and str(m.dtype) == "torch.float64"):
-                    raise ValueError("set_observer: contiguous CUDA float64 tensors are needed")
-            shapes = [tuple(m.shape) for m in given]
-            shapes[0] = shapes[0][:-2] + (shapes[0][-1], shapes[0][-2])  # (ABI layout: C arrives as (.., nx, ny))
-            shapes[1:] = [sh[:-2] + (sh[-1], sh[-2]) for sh in shapes[1:]]
-        else:
-            given = [np.asarray(m, dtype=np.float64) for m in given]
-            if any(m.ndim == 3 for m in given):  # (one flag covers all three: a matrix given once is written out per instance)
-                given = [np.broadcast_to(m, (b,) + m.shape) if m.ndim == 2 else m for m in given]
-            shapes = [tuple(m.shape) for m in given]
+        args = [_args.marshal(m, "set_observer", matrix=True) for m in (C_out, Lx, Ld) if m is not None]
+        on_device, _ = _args.same_way("set_observer", args)
+        if not on_device and any(len(a.shape) == 3 for a in args):  # (one flag covers all three: a matrix given once is written out per instance)
+            args = [_args.written_out(a, b) if len(a.shape) == 2 else a for a in args]
+        shapes = [a.shape for a in args]
         ny = shapes[0][-2] if len(shapes[0]) >= 2 else 0
-        per = len(shapes[0]) == 3
+        per = int(len(shapes[0]) == 3)
         lead = (b,) if per else ()
-        want = [lead + (ny, nx)] + [lead + (nx, ny)] * (len(given) - 1)
-        if ny < 1 or shapes != want:
+        if ny < 1 or shapes != [lead + (ny, nx)] + [lead + (nx, ny)] * (len(args) - 1):
             raise _capi.CopraDomainError("set_observer: expected C %s and gains %s (or one of each per instance), got %s" % ((ny, nx), (nx, ny), shapes))
-        if torch_in:
-            ptrs = [m.data_ptr() for m in given]
-        else:
-            given = [np.ascontiguousarray(np.swapaxes(m, -1, -2)) for m in given]
-            ptrs = [m.ctypes.data for m in given]
-        ptrs += [None] * (3 - len(ptrs))
-        _capi.check(self._lib.copra_batch_set_observer(self._h, ny, ptrs[0], ptrs[1], ptrs[2], 1 if per else 0, 1 if torch_in else 0))
-        self._obs_keep, self._ny = (given if torch_in else None), ny
+        _capi.check(self._lib.copra_batch_set_observer(self._h, ny, *[a.ptr for a in args], *[None] * (3 - len(args)), per, on_device))
+        self._hold("observer", *args)
+        self._ny = ny
 
     def set_plant_state(self, x):
         """the plant's own state while the observer is or was on (copra_batch_set_plant_state): (batch, nx), numpy (copied) or a torch CUDA
         float64 tensor (copied on the stream of the last tick).  set_x0 sets the estimate; a new episode sets both."""
-        if _is_torch(x):
-            ptr, _ = self._device(x, (self.batch, self.nx), "set_plant_state")
-            _capi.check(self._lib.copra_batch_set_plant_state(self._h, ptr, 1))
-        else:
-            xb = np.ascontiguousarray(x, dtype=np.float64)
-            if xb.shape != (self.batch, self.nx):
-                raise _capi.CopraDomainError("set_plant_state: expected %s, got %s" % ((self.batch, self.nx), xb.shape))
-            _capi.check(self._lib.copra_batch_set_plant_state(self._h, xb.ctypes.data, 0))
+        arg = _args.expect(_args.marshal(x, "set_plant_state"), (self.batch, self.nx), "set_plant_state")
+        _capi.check(self._lib.copra_batch_set_plant_state(self._h, arg.ptr, arg.on_device))
 
     def plant_state(self):
         """the plant's own state, (batch, nx), as a numpy copy (copra_batch_get_plant_state: waits for the last tick)"""
@@ -569,35 +479,21 @@ class BatchLMPC:
         self._lib.copra_noise_init(C.byref(n))
         if process is None and sensor is None:
             _capi.check(self._lib.copra_batch_set_noise(self._h, None))
-            self._noise_keep = None
+            self._release("noise")
             return
-        given = [(a, rows, what) for a, rows, what in ((process, self.nx, "process"), (sensor, self._ny, "sensor")) if a is not None]
-        torch_in = _is_torch(given[0][0])
-        if any(_is_torch(a) != torch_in for a, _, _ in given):
-            raise ValueError("set_noise: process and sensor are both numpy or both torch CUDA tensors")
-        ptrs, keep, pers = {}, [], set()
-        for a, rows, what in given:
-            if torch_in:
-                if not (a.is_cuda and a.is_contiguous() and str(a.dtype) == "torch.float64"):
-                    raise ValueError("set_noise: contiguous CUDA float64 tensors are needed")
-                arr, ptr = a, a.data_ptr()
-            else:
-                arr = np.ascontiguousarray(a, dtype=np.float64)
-                ptr = arr.ctypes.data
+        pw, pv = _args.marshal(process, "set_noise"), _args.marshal(sensor, "set_noise")
+        pers = []
+        for arg, rows, what in ((pw, self.nx, "process"), (pv, self._ny, "sensor")):
+            if arg is None:
+                continue
             if what == "sensor" and rows == 0:
-                rows = arr.shape[-1] if arr.ndim else 0  # (the observer is off: the library says so)
-            if tuple(arr.shape) not in ((rows,), (self.batch, rows)):
-                raise _capi.CopraDomainError("set_noise: %s of shape (%d,) or (%d, %d) expected, got %s" % (what, rows, self.batch, rows, tuple(arr.shape)))
-            pers.add(len(arr.shape) == 2)
-            ptrs[what] = ptr
-            keep.append(arr)
-        if len(pers) != 1:
-            raise _capi.CopraDomainError("set_noise: process and sensor are both given once or both per instance")
+                rows = arg.shape[-1] if arg.shape else 0  # (the observer is off: the library says so)
+            pers.append(_args.weight_form(arg.shape, rows, self.batch, "set_noise: " + what, dense_allowed=False)[1])
+        n.on_device, n.per_instance = _args.same_way("set_noise", (pw, pv), pers)
         n.seed, n.first_instance = int(seed), int(first_instance)
-        n.sigma_w, n.sigma_v = ptrs.get("process"), ptrs.get("sensor")
-        n.per_instance, n.on_device = int(pers.pop()), int(torch_in)
+        n.sigma_w, n.sigma_v = pw and pw.ptr, pv and pv.ptr
         _capi.check(self._lib.copra_batch_set_noise(self._h, C.byref(n)))
-        self._noise_keep = keep if torch_in else None
+        self._hold("noise", pw, pv)
 
     def noise_seek(self, tick):
         """the noise tick the next advance() draws at (copra_batch_noise_seek)"""
@@ -617,9 +513,9 @@ class BatchLMPC:
         if out is None:
             import torch
             out = torch.empty((self.batch, rows), dtype=torch.float64, device="cuda")
-        ptr, t = self._device(out, (self.batch, rows), "draw_noise out")
-        _capi.check(self._lib.copra_batch_draw_noise(self._h, int(tick), 0 if stream == "process" else 1, ptr, C.c_void_p(hip_stream or 0)))
-        return t
+        arg = self._device(out, (self.batch, rows), "draw_noise out")
+        _capi.check(self._lib.copra_batch_draw_noise(self._h, int(tick), 0 if stream == "process" else 1, arg.ptr, C.c_void_p(hip_stream or 0)))
+        return arg.owner
 
     # ---- closed-loop scores (copra_batch_set_score, ABI 14): the tick keeps one record per instance on the device ----
     def set_score(self, state_weights=None, control_weights=None, state_ref=None, state_limits=None, control_limits=None, tol=0.0):
@@ -638,80 +534,39 @@ class BatchLMPC:
         given = dict(qx=state_weights, ru=control_weights, x_ref=state_ref, x_lo=xl, x_hi=xh, u_lo=ul, u_hi=uh)
         if all(v is None for v in given.values()):
             _capi.check(self._lib.copra_batch_set_score(self._h, None))
-            self._score_keep = None
+            self._release("score")
             return
-        b, nx, nu = self.batch, self.nx, self.nu
-        torch_in = any(_is_torch(v) for v in given.values())
-        if torch_in:
-            for v in given.values():
-                if v is not None and not (_is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float64"):
-                    raise ValueError("set_score: contiguous CUDA float64 tensors are needed (all arrays numpy, or all tensors)")
-            arrs = dict(given)
-        else:
-            arrs = {k: (None if v is None else np.asarray(v, dtype=np.float64)) for k, v in given.items()}
+        b, nx, nu, what = self.batch, self.nx, self.nu, "set_score"
         rows = dict(qx=nx, ru=nu, x_lo=nx, x_hi=nx, u_lo=nu, u_hi=nu)
-        dense, per, steps = False, False, 1
-        kind = {}  # name -> (dense, per instance)
-        for k, a in arrs.items():
-            if a is None:
+        args, dense, per, steps = {}, {}, {}, 1
+        for k, v in given.items():
+            if v is None:
                 continue
-            sh = tuple(a.shape)
             if k == "x_ref":
-                if len(sh) == 1 and sh == (nx,):
-                    kind[k] = (False, False)
-                elif len(sh) == 2 and sh[1] == nx and sh[0] >= 1:
-                    kind[k], steps = (False, False), sh[0]
-                elif len(sh) == 3 and sh[0] == b and sh[2] == nx and sh[1] >= 1:
-                    kind[k], steps = (False, True), sh[1]
-                else:
-                    raise _capi.CopraDomainError("set_score: state_ref of shape (%d,), (steps, %d) or (%d, steps, %d) expected, got %s" % (nx, nx, b, nx, sh))
-                continue
-            r = rows[k]
-            weight = k in ("qx", "ru")
-            if sh == (r,):
-                kind[k] = (False, False)
-            elif weight and sh == (r, r):
-                kind[k] = (True, False)
-            elif sh == (b, r):
-                kind[k] = (False, True)
-            elif weight and sh == (b, r, r):
-                kind[k] = (True, True)
+                args[k], steps, per[k] = _args.signal(v, nx, b, True, what + ": state_ref")
             else:
-                raise _capi.CopraDomainError("set_score: %s has shape %s" % (k, sh))
-        dense = any(d for d, _ in kind.values())
-        per = any(p for _, p in kind.values())
-        if torch_in:
-            if any(p != per for _, p in kind.values()) or any(d != dense for k, (d, _) in kind.items() if k in ("qx", "ru")):
-                raise ValueError("set_score: tensors are used in place -- all shared or all per instance, both weights diagonal or both dense")
-            ptrs = {k: (None if a is None else a.data_ptr()) for k, a in arrs.items()}
-            keep = [a for a in arrs.values() if a is not None]
-        else:
-            keep = []
-            ptrs = {}
-            for k, a in arrs.items():
-                if a is None:
-                    ptrs[k] = None
-                    continue
-                d, p = kind[k]
+                args[k], d, per[k] = _args.weight(v, rows[k], b, "%s: %s" % (what, k), dense_allowed=k in ("qx", "ru"))
                 if k in ("qx", "ru"):
-                    if dense and not d:  # a diagonal beside a dense weight: written out
-                        a = a[..., None] * np.eye(a.shape[-1])
-                    elif dense:
-                        a = np.swapaxes(a, -1, -2)  # natural indexing -> the ABI's column-major blocks
-                elif k == "x_ref" and a.ndim == 1:
-                    a = a[None, :]
-                if per and not p:
-                    a = np.broadcast_to(a, (b,) + a.shape)
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                keep.append(a)
-                ptrs[k] = a.ctypes.data
+                    dense[k] = d
+        any_dense, any_per = int(any(dense.values())), int(any(per.values()))
+        on_device, _ = _args.same_way(what, args.values())
+        if on_device:  # used in place: nothing can be written out
+            _args.same_way(what, args.values(), per.values(), ValueError)
+            if len(set(dense.values())) > 1:
+                raise ValueError("set_score: tensors are used in place -- both weights diagonal or both dense")
+        else:  # a diagonal beside a dense weight, an array given once beside per-instance ones: written out
+            for k, a in args.items():
+                if any_dense and not dense.get(k, 1):
+                    a = _args.diagonal_as_dense(a)
+                args[k] = _args.written_out(a, b) if any_per and not per[k] else a
         m = _capi.Score()
         self._lib.copra_score_init(C.byref(m))
-        m.qx, m.ru, m.x_ref, m.x_lo, m.x_hi, m.u_lo, m.u_hi = (ptrs[k] for k in ("qx", "ru", "x_ref", "x_lo", "x_hi", "u_lo", "u_hi"))
-        m.dense, m.per_instance, m.on_device = int(dense), int(per), int(torch_in)
+        for k in given:
+            setattr(m, k, args[k].ptr if k in args else None)
+        m.dense, m.per_instance, m.on_device = any_dense, any_per, on_device
         m.ref_steps, m.tol = int(steps), float(tol)
         _capi.check(self._lib.copra_batch_set_score(self._h, C.byref(m)))
-        self._score_keep = keep if torch_in else None
+        self._hold("score", *args.values())
 
     def reset_score(self):
         """zero the records, in stream order behind the last tick (copra_batch_score_reset): a new episode"""
@@ -776,7 +631,7 @@ class BatchLMPC:
         the list.  outputs None (set_target(None)) ends the targets and keeps the last references."""
         if outputs is None:
             _capi.check(self._lib.copra_batch_set_target(self._h, None))
-            self._target_keep = None
+            self._release("target")
             return
         b, nx, nu = self.batch, self.nx, self.nu
         if setpoint is None or costs is None:
@@ -786,55 +641,28 @@ class BatchLMPC:
             raise ValueError("set_target: 1 .. 8 driven costs")
         if any(k < 0 or k >= len(self._costs) for k in idx):
             raise ValueError("set_target: no such cost")
-        torch_in = _is_torch(outputs) or _is_torch(setpoint)
-        if torch_in:
-            for v in (outputs, setpoint):
-                if not (_is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float64"):
-                    raise ValueError("set_target: contiguous CUDA float64 tensors are needed (outputs and setpoint numpy, or both tensors)")
-            Hc, sp = outputs, setpoint
-            hshape = tuple(Hc.shape)[::-1]  # (the ABI's column-major: the tensor holds outputs.T)
-        else:
-            Hn = np.asarray(outputs, dtype=np.float64)
-            hshape = tuple(Hn.shape)
-            Hc = np.ascontiguousarray(Hn.T) if Hn.ndim == 2 else Hn
-            sp = np.ascontiguousarray(setpoint, dtype=np.float64)
-        if hshape != (nu, nx):
-            raise _capi.CopraDomainError("set_target: outputs of shape (%d, %d) expected, got %s" % (nu, nx, hshape))
-        sh = tuple(sp.shape)
-        if sh == (nu,):
-            steps, per = 1, 0
-        elif len(sh) == 2 and sh[1] == nu and sh[0] >= 1:
-            steps, per = sh[0], 0
-        elif len(sh) == 3 and sh[0] == b and sh[2] == nu and sh[1] >= 1:
-            steps, per = sh[1], 1
-        else:
-            raise _capi.CopraDomainError("set_target: setpoint of shape (%d,), (steps, %d) or (%d, steps, %d) expected, got %s" % (nu, nu, b, nu, sh))
+        H = _args.expect(_args.marshal(outputs, "set_target", matrix=True), (nu, nx), "set_target: outputs")
+        sp, steps, per = _args.signal(setpoint, nu, b, True, "set_target: setpoint")
+        on_device, _ = _args.same_way("set_target", (H, sp))
         if int(offset) < 0:
             raise ValueError("set_target: offset < 0")
         maps, rows = [], []
         for k in idx:
             T, r = self._step_map(k)
-            maps.append(np.ascontiguousarray(T.T))  # column-major [r x n]
+            m = np.ascontiguousarray(T.T)  # column-major [r x n]
+            if on_device:  # (the maps live where outputs and setpoint do)
+                import torch
+                m = torch.from_numpy(m).cuda()
+            maps.append(_args.marshal(m, "set_target"))
             rows.append(r)
-        keep = [Hc, sp]
-        if torch_in:
-            import torch
-            maps = [torch.from_numpy(m).cuda() for m in maps]
-            mptr = [m.data_ptr() for m in maps]
-            hptr, rptr = Hc.data_ptr(), sp.data_ptr()
-        else:
-            mptr = [m.ctypes.data for m in maps]
-            hptr, rptr = Hc.ctypes.data, sp.ctypes.data
-        keep += maps
         t = _capi.Target()
         self._lib.copra_target_init(C.byref(t))
-        ci, cr, cm = (C.c_int * len(idx))(*idx), (C.c_int * len(idx))(*rows), (C.c_void_p * len(idx))(*mptr)
-        t.nr, t.H, t.r, t.steps, t.offset, t.per_instance = nu, hptr, rptr, int(steps), int(offset), per
-        t.n_costs, t.cost_index, t.cost_rows, t.cost_map, t.on_device = len(idx), ci, cr, cm, int(torch_in)
-        for k in idx:  # (the costs' references are the library's now)
-            self._ref_keep.pop(k, None)
+        ci, cr, cm = (C.c_int * len(idx))(*idx), (C.c_int * len(idx))(*rows), (C.c_void_p * len(idx))(*[m.ptr for m in maps])
+        t.nr, t.H, t.r, t.steps, t.offset, t.per_instance = nu, H.ptr, sp.ptr, int(steps), int(offset), per
+        t.n_costs, t.cost_index, t.cost_rows, t.cost_map, t.on_device = len(idx), ci, cr, cm, on_device
         _capi.check(self._lib.copra_batch_set_target(self._h, C.byref(t)))
-        self._target_keep = keep if torch_in else None
+        self._release(*[("reference", k) for k in idx])  # (the costs' references are the library's now)
+        self._hold("target", H, sp, *maps)
 
     def target(self):
         """the steady states z = [xs; us], (batch, nx + nu), as a numpy copy (copra_batch_get_target: waits for the last tick)"""
@@ -853,37 +681,50 @@ class BatchLMPC:
         """device pointer of the steady states (copra_batch_target_device); 0 while targets are off"""
         return int(self._lib.copra_batch_target_device(self._h) or 0)
 
-    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out=None, d_out=None, noise=None,
+    def _plant_step(self, plant, shared, disturbance, fallback_control, x_out, u_out, status_out, age_out=None, d_out=None, noise=None,
                     y_meas=None, y_out=None, xhat_out=None):
+        """(the struct of a tick, {its pointer fields: the _args.Arg behind each, None where not given})"""
         st = _capi.PlantStepObs()
         self._lib.copra_plant_step_obs_init(C.byref(st))
         b, nx, nu = self.batch, self.nx, self.nu
+        args = {}
         if plant is not None:
             A, B, d = plant
             lead = () if shared else (b,)
             for name, arr, shape in (("A", A, lead + (nx, nx)), ("B", B, lead + (nu, nx)), ("d", d, lead + (nx,))):
-                if arr is not None and not _is_torch(arr) and name != "d":  # natural indexing -> the ABI's column-major blocks (torch
+                if arr is not None and not _args.is_torch(arr) and name != "d":  # natural indexing -> the ABI's column-major blocks (torch
                     arr = np.swapaxes(np.asarray(arr, dtype=np.float64), -1, -2)  # tensors are in ABI layout already, as for set_system)
-                ptr, t = self._device(arr, shape, "plant " + name)  # (some but not all of them: the library's COPRA_ERR_ARG)
-                setattr(st, name, ptr)
-                keep.append(t)
+                args[name] = self._device(arr, shape, "plant " + name)  # (some but not all of them: the library's COPRA_ERR_ARG)
             st.shared = 1 if shared else 0
-        st.w, t1 = self._device(disturbance, (b, nx), "disturbance")
-        st.fallback_u, t2 = self._device(fallback_control, (b, nu), "fallback_control")
-        st.x_out, xo = self._output(x_out, (b, nx), "x_out")
-        st.u_out, uo = self._output(u_out, (b, nu), "u_out")
-        st.status_out, so = self._output(status_out, (b,), "status_out", "int32")
-        st.age_out, ao = self._output(age_out, (b,), "age_out", "int32")
-        st.d_out, do = self._output(d_out, (b, nx), "d_out")
+        args["w"] = self._device(disturbance, (b, nx), "disturbance")
+        args["fallback_u"] = self._device(fallback_control, (b, nu), "fallback_control")
+        args["x_out"] = self._output(x_out, (b, nx), "x_out")
+        args["u_out"] = self._output(u_out, (b, nu), "u_out")
+        args["status_out"] = self._output(status_out, (b,), "status_out", "int32")
+        args["age_out"] = self._output(age_out, (b,), "age_out", "int32")
+        args["d_out"] = self._output(d_out, (b, nx), "d_out")
         ny = self._ny  # (the observer's outputs: shapes are known only while it is on)
         if ny == 0 and any(a is not None and a is not False for a in (noise, y_meas, y_out, xhat_out)):
             raise ValueError("noise, y_meas, y_out and xhat_out belong to the observer (set_observer)")
-        st.v, t3 = self._device(noise, (b, ny), "noise")
-        st.y_meas, t4 = self._device(y_meas, (b, ny), "y_meas")
-        st.y_out, yo = self._output(y_out, (b, ny), "y_out")
-        st.xhat_out, ho = self._output(xhat_out, (b, nx), "xhat_out")
-        keep.extend([t1, t2, xo, uo, so, ao, do, t3, t4, yo, ho])
-        return st, dict(x_out=xo, u_out=uo, status_out=so, age_out=ao, d_out=do, y_out=yo, xhat_out=ho)
+        args["v"] = self._device(noise, (b, ny), "noise")
+        args["y_meas"] = self._device(y_meas, (b, ny), "y_meas")
+        args["y_out"] = self._output(y_out, (b, ny), "y_out")
+        args["xhat_out"] = self._output(xhat_out, (b, nx), "xhat_out")
+        return st, args
+
+    @staticmethod
+    def _fill(st, args):
+        for field, arg in args.items():
+            if arg is not None:  # (what is not given stays the null of copra_plant_step_obs_init)
+                setattr(st, field, arg.ptr)
+
+    def _ticked(self, args, names):
+        """the library took the tick: its tensors are held until the next one; {name: the tensor, None where not asked for}"""
+        self._hold("tick", *args.values())
+        return {k: args[k] and args[k].owner for k in names}
+
+    OUTS = ("x_out", "u_out", "status_out", "age_out", "d_out", "y_out", "xhat_out")
+    HISTS = ("x_hist", "u_hist", "status_hist", "age_hist", "d_hist", "y_hist", "xhat_hist")
 
     def advance(self, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None, stream=None,
                 age_out=None, d_out=None, noise=None, y_meas=None, y_out=None, xhat_out=None):
@@ -902,12 +743,11 @@ class BatchLMPC:
         With the observer on (set_observer): x_out is the plant's own state; noise (batch, ny) is added to the outputs; y_out (batch, ny) and
         xhat_out (batch, nx) receive the outputs and the new estimates.  y_meas (batch, ny): the measurement of a REAL plant after it applied
         the control -- no plant is simulated, plant_state() is left alone, x_out is not written, plant / disturbance / noise are ignored."""
-        keep = []
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out, noise, y_meas,
-                                    y_out, xhat_out)
+        st, args = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, age_out, d_out, noise, y_meas, y_out,
+                                    xhat_out)
+        self._fill(st, args)
         _capi.check(self._lib.copra_batch_advance(self._h, C.byref(st), C.c_void_p(stream or 0)))
-        self._tick_keep = keep
-        return outs
+        return self._ticked(args, self.OUTS)
 
     def rollout(self, ticks, plant=None, shared=False, disturbance=None, fallback_control=None, x_out=None, u_out=None, status_out=None,
                 disturbances=None, x_hist=None, u_hist=None, status_hist=None, stream=None, age_out=None, age_hist=None, solve_every=1,
@@ -926,29 +766,26 @@ class BatchLMPC:
         ticks = int(ticks)
         if ticks < 0:
             raise ValueError("rollout: ticks < 0")
-        keep = []
         ny = self._ny
         noise_seq = noise is not None and len(getattr(noise, "shape", ())) == 3
-        st, outs = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, keep, age_out, d_out,
+        st, args = self._plant_step(plant, shared, disturbance, fallback_control, x_out, u_out, status_out, age_out, d_out,
                                     None if noise_seq else noise, None, y_out, xhat_out)
         b, nx, nu = self.batch, self.nx, self.nu
         if ny == 0 and any(a is not None and a is not False for a in (y_hist, xhat_hist)):
             raise ValueError("y_hist and xhat_hist belong to the observer (set_observer)")
-        st.v_seq, vt = self._device(noise if noise_seq else None, (ticks, b, ny), "noise")
-        st.y_hist, yt = self._output(y_hist, (ticks, b, ny), "y_hist")
-        st.xhat_hist, ht = self._output(xhat_hist, (ticks, b, nx), "xhat_hist")
-        keep.extend([vt, yt, ht])
-        wp, wt = self._device(disturbances, (ticks, b, nx), "disturbances")
-        xp, xt = self._output(x_hist, (ticks + 1, b, nx), "x_hist")
-        up, ut = self._output(u_hist, (ticks, b, nu), "u_hist")
-        sp, stt = self._output(status_hist, (ticks, b), "status_hist", "int32")
-        st.age_hist, at = self._output(age_hist, (ticks, b), "age_hist", "int32")
+        args["v_seq"] = self._device(noise if noise_seq else None, (ticks, b, ny), "noise")
+        args["y_hist"] = self._output(y_hist, (ticks, b, ny), "y_hist")
+        args["xhat_hist"] = self._output(xhat_hist, (ticks, b, nx), "xhat_hist")
+        seq = dict(w_seq=self._device(disturbances, (ticks, b, nx), "disturbances"),  # (the call's own arguments, in its order)
+                   x_hist=self._output(x_hist, (ticks + 1, b, nx), "x_hist"),
+                   u_hist=self._output(u_hist, (ticks, b, nu), "u_hist"),
+                   status_hist=self._output(status_hist, (ticks, b), "status_hist", "int32"))
+        args["age_hist"] = self._output(age_hist, (ticks, b), "age_hist", "int32")
         st.solve_every = int(solve_every)
-        st.d_hist, dt = self._output(d_hist, (ticks, b, nx), "d_hist")
-        keep.extend([wt, xt, ut, stt, at, dt])
-        _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, wp, xp, up, sp, C.c_void_p(stream or 0)))
-        self._tick_keep = keep
-        return dict(outs, x_hist=xt, u_hist=ut, status_hist=stt, age_hist=at, d_hist=dt, y_hist=yt, xhat_hist=ht)
+        args["d_hist"] = self._output(d_hist, (ticks, b, nx), "d_hist")
+        self._fill(st, args)
+        _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, *[a and a.ptr for a in seq.values()], C.c_void_p(stream or 0)))
+        return self._ticked(dict(args, **seq), self.OUTS + self.HISTS)
 
     def state(self):
         """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""

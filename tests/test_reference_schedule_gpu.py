@@ -213,7 +213,7 @@ def test_torch_schedule_is_used_in_place_and_never_written():
     keep = sched.clone()
     eng = _engine(wl)
     eng.set_reference_schedule(0, sched, tc.NX)
-    assert eng._sched_keep[0] is sched
+    assert eng._held[("schedule", 0)] is sched
     eng.rollout(tc.TICKS + 25)  # (to beyond the end of the signal)
     eng.synchronize()
     assert torch.equal(sched, keep)
@@ -231,7 +231,7 @@ def test_torch_schedule_is_used_in_place_and_never_written():
     stale.solve()
     assert np.abs(stale.results()["control"] - eng.results()["control"]).max() > 1e-3
     eng.set_cost_reference(0, None)  # drops the kept tensor
-    assert 0 not in eng._sched_keep
+    assert ("schedule", 0) not in eng._held
 
 
 def test_error_codes():
