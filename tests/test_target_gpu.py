@@ -32,9 +32,9 @@ def _maps(wl):
     return [target_ref.step_map(c, nx, nu, wl["N"])[0] for c in wl["costs"]]
 
 
-def _check_targets(eng, wl, H, sig, offset=0, what="", singular=(), kept=None, B=None):
-    """target(), target_status() and the references of costs 0 and 1 against the reference computed from bias() and the schedule tick;
-    kept: (z, [p0, p1]) a singular instance must still hold"""
+def _check_targets(eng, wl, H, sig, offset=0, what="", singular=(), kept=None, B=None, maps=None, costs=(0, 1)):
+    """target(), target_status() and the references of the driven costs (0 and 1; `costs` with their step maps `maps` otherwise) against the
+    reference computed from bias() and the schedule tick; kept: (z, [p0, p1, ...]) a singular instance must still hold"""
     A, B = wl["A"], wl["B"] if B is None else B
     batch, nu = A.shape[0], B.shape[2]
     d, tau = eng.bias(), eng.schedule_tick()
@@ -54,8 +54,8 @@ def _check_targets(eng, wl, H, sig, offset=0, what="", singular=(), kept=None, B
     err = np.abs(z[good] - zt).max(axis=1).astype(np.float64)
     assert np.isfinite(z[good]).all() and (err <= bound).all(), (what, float((err / bound).max()))
     WORST["z"] = max(WORST["z"], float((err / bound).max()))
-    refs = [eng.cost_reference(k) for k in (0, 1)]
-    for k, T in enumerate(_maps(wl)):
+    refs = [eng.cost_reference(k) for k in costs]
+    for k, T in enumerate(_maps(wl) if maps is None else maps):
         p, pb = target_ref.p_true_and_bound(T, M[good], zt)
         S = refs[k].shape[1] // T.shape[0]
         got = refs[k][good].reshape(int(good.sum()), S, T.shape[0])
@@ -66,7 +66,7 @@ def _check_targets(eng, wl, H, sig, offset=0, what="", singular=(), kept=None, B
     if kept is not None:
         bad = ~good
         assert z[bad].tobytes() == kept[0][bad].tobytes(), what
-        for k in (0, 1):
+        for k in range(len(refs)):
             assert refs[k][bad].tobytes() == kept[1][k][bad].tobytes(), (what, k)
     print("%s: largest error / bound so far: z %.3g, references %.3g" % (what, WORST["z"], WORST["p"]))
     return z, refs
