@@ -471,6 +471,18 @@ def lib():
         L.copra_batch_get_target.argtypes = [vp, vp, vp]
         L.copra_batch_get_cost_reference.restype = C.c_int
         L.copra_batch_get_cost_reference.argtypes = [vp, C.c_int, vp]
+        L.copra_batch_set_input_delay.restype = C.c_int
+        L.copra_batch_set_input_delay.argtypes = [vp, C.c_int, vp, C.c_int]
+        L.copra_batch_input_delay.restype = C.c_int
+        L.copra_batch_input_delay.argtypes = [vp]
+        L.copra_batch_delay_state_device.restype = vp
+        L.copra_batch_delay_state_device.argtypes = [vp]
+        L.copra_batch_get_delay_state.restype = C.c_int
+        L.copra_batch_get_delay_state.argtypes = [vp, vp]
+        L.copra_batch_delay_queue_device.restype = C.c_int
+        L.copra_batch_delay_queue_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.copra_batch_get_delay_queue.restype = C.c_int
+        L.copra_batch_get_delay_queue.argtypes = [vp, vp, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -787,8 +787,44 @@ class BatchLMPC:
         _capi.check(self._lib.copra_batch_rollout(self._h, C.byref(st), ticks, *[a and a.ptr for a in seq.values()], C.c_void_p(stream or 0)))
         return self._ticked(dict(args, **seq), self.OUTS + self.HISTS)
 
+    DELAY_MAX = 8  # COPRA_DELAY_MAX
+
+    def set_input_delay(self, steps, u_init=None):
+        """Input delay in the tick (copra_batch_set_input_delay): the command a solve issues reaches the plant `steps` = D ticks later, D in
+        0 .. DELAY_MAX.  The library queues the D commands already issued, keeps the state at the current tick (delay_state()) and makes
+        the controller's x0 (state()) the state PREDICTED for the time the next command will act: the queue applied to the current state
+        with the controller's model.  advance() / rollout() then apply the queue's oldest command -- u_out, status_out and age_out describe
+        the command that reached the plant -- push the last solve's and predict again, all on the device.  u_init (batch, nu): what the
+        plant gets for the first D ticks, numpy (copied) or a torch CUDA float64 tensor (read in stream order); None: zeros.  Every call
+        resets the queue; 0 turns delay off.  Schedules and set_target take offset + D in a delayed loop.  Excludes set_backup_steps and
+        solve_every > 1."""
+        steps = int(steps)
+        arg = None if u_init is None or steps == 0 else _args.expect(_args.marshal(u_init, "set_input_delay"), (self.batch, self.nu), "set_input_delay")
+        _capi.check(self._lib.copra_batch_set_input_delay(self._h, steps, arg and arg.ptr, arg.on_device if arg else 0))
+        self._hold("delay", arg)  # (a tensor is read in stream order: kept until the next call)
+
+    def delay_state(self):
+        """the state at the current tick while input delay is on, (batch, nx), as a numpy copy (copra_batch_get_delay_state: waits for the
+        last tick): the measured state, or with the observer the estimate"""
+        out = np.empty((self.batch, self.nx))
+        _capi.check(self._lib.copra_batch_get_delay_state(self._h, out.ctypes.data))
+        return out
+
+    def delay_state_ptr(self):
+        """device pointer of the state at the current tick (copra_batch_delay_state_device); 0 while input delay is off"""
+        return int(self._lib.copra_batch_delay_state_device(self._h) or 0)
+
+    def delay_queue(self):
+        """(commands (batch, D, nu), statuses int32 (batch, D)) of the pending commands, OLDEST first, as numpy copies
+        (copra_batch_get_delay_queue: waits for the last tick); the command of a failed solve reads NaN"""
+        D = int(self._lib.copra_batch_input_delay(self._h))
+        q, s = np.empty((self.batch, max(D, 0), self.nu)), np.empty((self.batch, max(D, 0)), dtype=np.int32)
+        _capi.check(self._lib.copra_batch_get_delay_queue(self._h, q.ctypes.data, s.ctypes.data))
+        return q, s
+
     def state(self):
-        """the controller's current initial states, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for the last tick)"""
+        """the controller's current initial states -- what the next solve reads --, (batch, nx), as a numpy copy (copra_batch_get_x0: waits for
+        the last tick); while input delay is on (set_input_delay) this is the prediction, delay_state() the state at the current tick"""
         out = np.empty((self.batch, self.nx))
         _capi.check(self._lib.copra_batch_get_x0(self._h, out.ctypes.data))
         return out

@@ -21,6 +21,24 @@
 #include <cstddef>
 #include <cstring>
 
+// the shared model of copra_batch_set_shared_system on the device (the solve keeps it on the host and in its prepared model)
+copra_status_t shared_model_on_device(copra_batch* h)
+{
+    if (h->d_shA && !h->sh_dev_stale) return COPRA_OK;
+    const size_t nA = h->shA.size(), nB = h->shB.size(), nd = h->shd.size();
+    if (!h->d_shA) {
+        OWN_TRY(h->d_shA.alloc(nA));
+        OWN_TRY(h->d_shB.alloc(nB));
+        OWN_TRY(h->d_shd.alloc(nd));
+    }
+    HIP_TRY(hipStreamSynchronize(h->last_stream)); // (an advance that still reads the old model: once per model)
+    HIP_TRY(hipMemcpy(h->d_shA, h->shA.data(), nA * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_shB, h->shB.data(), nB * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_shd, h->shd.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+    h->sh_dev_stale = false;
+    return COPRA_OK;
+}
+
 namespace {
 
 // the caller's struct as THIS library knows it -- the widest form, copra_plant_step_obs_t, whose first bytes are the struct a caller of ABI 10
@@ -43,24 +61,6 @@ copra_status_t check_handle(const copra_batch* h, const char* who)
 {
     if (h->hp.plan.initial_state)
         return fail(COPRA_ERR_UNSUPPORTED, std::string(who) + ": the initial state of an InitialStateLMPC controller is a decision variable, not the plant's state");
-    return COPRA_OK;
-}
-
-// the shared model of copra_batch_set_shared_system on the device (the solve keeps it on the host and in its prepared model)
-copra_status_t shared_model_on_device(copra_batch* h)
-{
-    if (h->d_shA && !h->sh_dev_stale) return COPRA_OK;
-    const size_t nA = h->shA.size(), nB = h->shB.size(), nd = h->shd.size();
-    if (!h->d_shA) {
-        OWN_TRY(h->d_shA.alloc(nA));
-        OWN_TRY(h->d_shB.alloc(nB));
-        OWN_TRY(h->d_shd.alloc(nd));
-    }
-    HIP_TRY(hipStreamSynchronize(h->last_stream)); // (an advance that still reads the old model: once per model)
-    HIP_TRY(hipMemcpy(h->d_shA, h->shA.data(), nA * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_shB, h->shB.data(), nB * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_shd, h->shd.data(), nd * sizeof(double), hipMemcpyHostToDevice));
-    h->sh_dev_stale = false;
     return COPRA_OK;
 }
 
@@ -154,13 +154,14 @@ copra_status_t launch_observer(copra_batch* h, const PlantStepArgs& P, const cop
     Q.dhat_next = h->obs_Ld ? (double*)h->d_bias : nullptr;
     Q.xhat = h->x0; // (a caller's device buffer is read this once more, never written)
     Q.xhat_next = h->own_x0;
+    if (h->delay > 0) Q.xhat = h->d_delay_x, Q.xhat_next = h->d_delay_x; // input delay: the estimate is xnow, x0 the prediction from it
     Q.C = h->obs_C, Q.Lx = h->obs_Lx, Q.Ld = h->obs_Ld;
     Q.yv = Q.meas ? io.y_meas : io.v;
     if (!Q.meas && h->noise_sv && h->noise_ny == Q.ny) Q.sigma_v = h->noise_sv;
     Q.y_out = io.y_out, Q.xhat_out = io.xhat_out, Q.d_out = io.d_out;
     if (Q.same_model) Q.s.A = h->A, Q.s.B = h->B, Q.s.d = h->d, Q.s.shared = 0;
     if (Q.meas) { // a real plant: the state of the tick's image is the estimate, nothing of the simulated plant is looked at
-        Q.s.x0 = h->x0, Q.s.x0_next = nullptr, Q.s.x_out = nullptr, Q.s.w = nullptr, Q.s.sigma_w = nullptr;
+        Q.s.x0 = Q.xhat, Q.s.x0_next = nullptr, Q.s.x_out = nullptr, Q.s.w = nullptr, Q.s.sigma_w = nullptr;
     } else {
         Q.s.x0 = h->d_xp, Q.s.x0_next = h->d_xp;
     }
@@ -221,6 +222,13 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     P.fallback_u = st.fallback_u;
     P.status = h->ad.last_status;
     P.control = h->ad.last_control;
+    if (h->delay > 0) { // input delay: the command that reaches the plant is the ring's oldest, the state xnow (x0 is the prediction)
+        if (!h->d_delay_q || !h->d_delay_qs || !h->d_delay_x) return fail(COPRA_ERR_RUNTIME, std::string(who) + ": the input delay has lost its buffers");
+        P.control = (const double*)h->d_delay_q + (size_t)h->delay_head * P.nu;
+        P.ctrl_stride = h->delay * P.nu;
+        P.status = (const int*)h->d_delay_qs + (size_t)h->delay_head * P.batch;
+        P.x0 = h->d_delay_x, P.x0_next = h->d_delay_x;
+    }
     P.x_out = x_out;
     P.u_out = u_out;
     P.status_out = status_out;
@@ -269,10 +277,15 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
     h->x0 = h->own_x0;
     h->plan_fresh = false;
     h->last_stream = s; // (copra_batch_synchronize and the read-outs wait for the tick, not only for its solve)
+    if (h->delay > 0) { // the last solve's command into the slot just applied, and the prediction into x0: behind the plant step
+        const copra_status_t rc = launch_delay(h, 1, st.fallback_u, s, who);
+        if (rc != COPRA_OK) return rc;
+    }
     h->noise_tick += 1; // (counted whether noise is drawn or not: a seek or a new copra_batch_set_noise says where the draws stand)
     h->sched_tick += 1; // time moves on for every instance, a failed one included: the next solve reads the next window
     if (h->score_on) { // the records, against the true state: the plant's own while the observer simulates one, else the new x0 (the estimate
-        const double* const truth = h->obs_on && !io.y_meas ? (const double*)h->d_xp : h->x0; // on a y_meas tick, where no truth exists)
+        const double* const now = h->delay > 0 ? (const double*)h->d_delay_x : h->x0; // (input delay: x0 is the prediction, the state is xnow)
+        const double* const truth = h->obs_on && !io.y_meas ? (const double*)h->d_xp : now; // on a y_meas tick, where no truth exists)
         const copra_status_t rc = launch_score(h, truth, P.u_out, P.age_out, s, who);
         if (rc != COPRA_OK) return rc;
     }
@@ -331,6 +344,8 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
     if (obs.y_meas) return fail(COPRA_ERR_ARG, "copra_batch_rollout: y_meas is the measurement of a real plant, one tick at a time (copra_batch_advance)");
     const int every = st.solve_every;
     if (every < 0) return fail(COPRA_ERR_ARG, "copra_batch_rollout: negative solve_every");
+    if (every > 1 && h->delay > 0)
+        return fail(COPRA_ERR_RUNTIME, "copra_batch_rollout: solve_every > 1 with input delay on (copra_batch_set_input_delay): the ticks in between play the plan store");
     if (every > 1 && h->backup_steps < every - 1)
         return fail(COPRA_ERR_ARG, "copra_batch_rollout: solve_every = k needs backup plans of at least k - 1 steps (copra_batch_set_backup_steps)");
     hipStream_t s = (hipStream_t)hip_stream;
@@ -339,8 +354,9 @@ copra_status_t copra_batch_rollout(copra_batch_t* h, const copra_plant_step_t* s
     const size_t ny = h->obs_on ? (size_t)HP.batch * h->obs_ny : 0;
     if (x_hist && nd) { // the state the first solve reads -- with the observer on the plant's own state: the truth
         if (!h->x0) return fail(COPRA_ERR_RUNTIME, "copra_batch_rollout: no initial states set");
-        const double* const truth = h->obs_on && h->d_xp ? (const double*)h->d_xp : h->x0;
-        if (h->obs_on && s != h->last_stream) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (xp may still be written on the last tick's stream)
+        const double* const now = h->delay > 0 ? (const double*)h->d_delay_x : h->x0; // (input delay: x0 is the prediction, the state is xnow)
+        const double* const truth = h->obs_on && h->d_xp ? (const double*)h->d_xp : now;
+        if ((h->obs_on || h->delay > 0) && s != h->last_stream) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (xp may still be written on the last tick's stream)
         HIP_TRY(hipMemcpyAsync(x_hist, truth, nd * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     for (int t = 0; t < ticks; ++t) {
@@ -366,6 +382,8 @@ copra_status_t copra_batch_set_backup_steps(copra_batch_t* h, int steps)
     if (rc != COPRA_OK) return rc;
     const FusedPlan& P = h->hp.plan;
     if (steps < 0 || steps > P.N - 1) return fail(COPRA_ERR_ARG, std::string(who) + ": steps outside 0 .. N - 1");
+    if (steps > 0 && h->delay > 0)
+        return fail(COPRA_ERR_RUNTIME, std::string(who) + ": input delay is on (copra_batch_set_input_delay): the plan store reads the tail of the solve's controls");
     if (steps == 0) { // off: the store goes (the release waits for a tick that still uses it)
         h->backup_steps = 0;
         h->d_plan.reset();
@@ -432,7 +450,8 @@ copra_status_t copra_batch_set_bias(copra_batch_t* h, const double* d, int on_de
         HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a tick that still writes the estimates)
         HIP_TRY(hipMemcpy(h->d_bias, d, bytes, hipMemcpyHostToDevice));
     }
-    return launch_target(h, h->last_stream, who);
+    const copra_status_t rc_t = launch_target(h, h->last_stream, who);
+    return rc_t != COPRA_OK ? rc_t : launch_delay(h, 0, nullptr, h->last_stream, who); // (input delay on: the prediction with the new d)
 }
 
 copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* C, const double* Lx, const double* Ld, int per_instance, int on_device)
@@ -475,7 +494,8 @@ copra_status_t copra_batch_set_observer(copra_batch_t* h, int ny, const double* 
     }
     if (!was_on) { // turned on: the plant starts from the x0 in force, behind the last solve / tick
         if (!h->d_xp) OWN_TRY(h->d_xp.alloc(b * (size_t)P.nx));
-        if (nd) HIP_TRY(hipMemcpyAsync(h->d_xp, h->x0, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
+        const double* const now = h->delay > 0 && h->d_delay_x ? (const double*)h->d_delay_x : h->x0; // (input delay: x0 is the prediction, the state is xnow)
+        if (nd) HIP_TRY(hipMemcpyAsync(h->d_xp, now, nd * sizeof(double), hipMemcpyDeviceToDevice, h->last_stream));
     }
     h->obs_ny = ny, h->obs_per_instance = per_instance != 0;
     if (on_device) h->obs_C.borrow(C), h->obs_Lx.borrow(Lx), h->obs_Ld.borrow(Ld);

@@ -178,8 +178,9 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
         h->B = B;
         h->d = d;
         h->x0 = x0;
-        const copra_status_t rc = bias_restart(h, h->last_stream); // (estimator on: the caller's d is copied, not adopted)
-        return rc != COPRA_OK ? rc : launch_target(h, h->last_stream, "copra_batch_set_system");
+        copra_status_t rc = bias_restart(h, h->last_stream); // (estimator on: the caller's d is copied, not adopted)
+        if (rc == COPRA_OK) rc = launch_target(h, h->last_stream, "copra_batch_set_system");
+        return rc != COPRA_OK ? rc : delay_adopt_x0(h, h->last_stream, "copra_batch_set_system"); // (input delay on: xnow and the prediction)
     }
     const size_t nA = b * P.nx * P.nx, nB = b * P.nx * P.nu, nd = b * P.nx;
     if (!h->own_A) {
@@ -188,6 +189,7 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
         OWN_TRY(h->own_d.alloc((nd ? nd : 1)));
     }
     if (!h->own_x0) OWN_TRY(h->own_x0.alloc((nd ? nd : 1)));
+    if (h->delay > 0) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a prediction in flight writes own_x0)
     HIP_TRY(hipMemcpy(h->own_A, A, nA * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->own_B, B, nB * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->own_d, d, nd * sizeof(double), hipMemcpyHostToDevice));
@@ -196,8 +198,9 @@ copra_status_t copra_batch_set_system(copra_batch_t* h, const double* A, const d
     h->B = h->own_B;
     h->d = h->own_d;
     h->x0 = h->own_x0;
-    const copra_status_t rc = bias_restart(h, h->last_stream);
-    return rc != COPRA_OK ? rc : launch_target(h, h->last_stream, "copra_batch_set_system"); // (targets on: the steady states of the new model)
+    copra_status_t rc = bias_restart(h, h->last_stream);
+    if (rc == COPRA_OK) rc = launch_target(h, h->last_stream, "copra_batch_set_system"); // (targets on: the steady states of the new model)
+    return rc != COPRA_OK ? rc : delay_adopt_x0(h, h->last_stream, "copra_batch_set_system"); // (input delay on: xnow and the prediction)
 }
 
 } // extern "C"
@@ -253,8 +256,9 @@ copra_status_t copra_batch_set_system_rowmajor_async(copra_batch_t* h, const dou
     h->B = h->own_B;
     h->d = d; // (vectors have no layout: used in place)
     h->x0 = x0;
-    const copra_status_t rc = bias_restart(h, s); // (estimator on: d is read once more, on `s`, for the copy the estimates restart from)
-    return rc != COPRA_OK ? rc : launch_target(h, s, "copra_batch_set_system_rowmajor_async"); // (targets on: behind the transposes, on `s`)
+    copra_status_t rc = bias_restart(h, s); // (estimator on: d is read once more, on `s`, for the copy the estimates restart from)
+    if (rc == COPRA_OK) rc = launch_target(h, s, "copra_batch_set_system_rowmajor_async"); // (targets on: behind the transposes, on `s`)
+    return rc != COPRA_OK ? rc : delay_adopt_x0(h, s, "copra_batch_set_system_rowmajor_async"); // (input delay on: xnow and the prediction)
 }
 
 int copra_batch_lanes_per_instance(const copra_batch_t* h)
@@ -420,13 +424,14 @@ copra_status_t copra_batch_set_x0(copra_batch_t* h, const double* x0, int on_dev
     const FusedPlan& P = h->hp.plan;
     if (on_device) {
         h->x0 = x0;
-        return COPRA_OK;
+        return delay_adopt_x0(h, h->last_stream, "copra_batch_set_x0"); // (input delay on: x0 is copied into xnow, the prediction takes its place)
     }
     const size_t nd = (size_t)P.batch * P.nx;
     if (!h->own_x0) OWN_TRY(h->own_x0.alloc((nd ? nd : 1)));
+    if (h->delay > 0) HIP_TRY(hipStreamSynchronize(h->last_stream)); // (a prediction in flight writes own_x0)
     HIP_TRY(hipMemcpy(h->own_x0, x0, nd * sizeof(double), hipMemcpyHostToDevice));
     h->x0 = h->own_x0;
-    return COPRA_OK;
+    return delay_adopt_x0(h, h->last_stream, "copra_batch_set_x0");
 }
 
 copra_status_t copra_batch_set_outputs(copra_batch_t* h, double* control, double* trajectory, int* status, int* iter)

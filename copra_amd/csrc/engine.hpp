@@ -16,6 +16,9 @@
 //   copra_hip_target.hip   steady-state targets: copra_batch_set_target / _target_device / _target_status_device / _get_target and their
 //                          kernel (target_step.hpp); launch_target below is what the tick and the setters that move d, the setpoint's
 //                          block or the model call while targets are on
+//   copra_hip_delay.hip    input delay in the tick: copra_batch_set_input_delay / _input_delay / _delay_state_device / _get_delay_state /
+//                          _delay_queue_device / _get_delay_queue and their kernel (delay_step.hpp); launch_delay below is what the tick calls
+//                          behind its plant step while delay is on, and what the setters that move the state, d or the model call
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -249,6 +252,13 @@ struct copra_batch {
     DevIn<double> target_map[kTargetCosts];
     Dev<double> d_target; // [batch][nx + nu]: z = [xs ; us]
     Dev<int> d_target_status; // [batch]: 1 where the last calculation found the instance singular
+    // input delay of the tick (copra_batch_set_input_delay; copra_hip_delay.hip, delay_step.hpp): every buffer is taken by the setter, never by
+    // the tick; while it is on x0 (own_x0) is the PREDICTION the next solve reads and d_delay_x the state at the current tick
+    int delay = 0; // D: 0 is off
+    int delay_head = 0; // the ring slot the next plant step applies: the oldest pending command
+    Dev<double> d_delay_q; // [batch][D][nu]: the pending commands
+    Dev<int> d_delay_qs; // [D][batch]: the status of the solve that issued each
+    Dev<double> d_delay_x; // [batch][nx]: xnow -- the measured state, or the observer's estimate
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -419,5 +429,13 @@ copra_status_t launch_score(copra_batch* h, const double* x, const double* u, co
 // ---- copra_hip_target.hip: the steady states and the driven costs' references from the model, the d and the setpoint's block in force, on
 // `s` (behind the handle's last stream where that is another one); returns at once while targets are off; no synchronisation, no allocation ----
 copra_status_t launch_target(copra_batch* h, hipStream_t s, const char* who);
+// ---- copra_hip_plant.hip: the shared model of copra_batch_set_shared_system on the device, uploaded once per model ----
+copra_status_t shared_model_on_device(copra_batch* h);
+// ---- copra_hip_delay.hip: input delay.  launch_delay: with push the last solve's command and status go into the ring slot the plant step just
+// applied and the head moves on; then the prediction from xnow, the model and d in force and the queue becomes x0 (own_x0) -- on `s` (behind
+// the handle's last stream where that is another one), returns at once while delay is off; no synchronisation, no allocation.
+// delay_adopt_x0: a setter brought a new state -- h->x0 is copied into xnow on `s` and the prediction takes its place ----
+copra_status_t launch_delay(copra_batch* h, int push, const double* fallback_u, hipStream_t s, const char* who);
+copra_status_t delay_adopt_x0(copra_batch* h, hipStream_t s, const char* who);
 // ---- copra_hip_jit.hip: dense-QP kernels compiled at run time for one problem size (copra_qp_dense_specialise) ----
 hipFunction_t dense_jit_lookup(int n, int lanes);

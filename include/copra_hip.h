@@ -722,6 +722,62 @@ const int* copra_batch_target_status_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_target(copra_batch_t* h, double* z, int* status);
 copra_status_t copra_batch_get_cost_reference(copra_batch_t* h, int cost_index, double* p);
 
+/* ---- input delay in the tick: command queue and state predictor (ABI 16).  Every tick above assumes that the control computed from the state
+ *      at tick t reaches the plant at tick t.  In a real loop the solve, the bus and the drive take time: the command computed at t acts at
+ *      t + D.  The remedy is to queue the commands already issued and to hand the solver the state PREDICTED for the time its command will
+ *      act.  The reference leaves this to its caller, like everything between control() and xInit() (include/LMPC.h:108,
+ *      include/PreviewSystem.h:52); here copra_batch_set_input_delay(h, D, u_init, on_device), 0 <= D <= COPRA_DELAY_MAX, puts it into the tick.
+ *      D = 0 is the state of a new handle: delay is off, the buffers are released and the tick is the one of ABI 15.
+ *      With D >= 1 the library keeps per instance b
+ *        q[b][D][nu]   a ring of pending commands          qs[D][batch]   the status of the solve that issued each pending command
+ *        xnow[b][nx]   the state AT THE CURRENT TICK: the measured state, or with the observer the estimate xhat
+ *      and one handle-wide `head`, the slot applied next: every instance pops and pushes exactly one entry per tick.
+ *      What the solve reads: the controller's x0 (copra_batch_x0_device, copra_batch_get_x0) becomes the PREDICTION.  Start from xnow and
+ *      walk the D pending entries, oldest first, with the controller's MODEL (the A, B, d in force, per instance or the one system of
+ *      copra_batch_set_shared_system; d the estimates where the estimator or the observer's Ld is on) and no w, each entry by the plant
+ *      step's own rule:
+ *        status == COPRA_QP_OK          x <- Am x + Bm u + d        (the row sum in the order of the plant step)
+ *        else, this step has fallback_u the same with u = fallback_u[b]
+ *        else                           x is kept: the plant will hold that instance at that tick
+ *      A tick (copra_batch_advance, every tick of copra_batch_rollout), for instance b:
+ *        1. the plant step runs as above, reading q[b][head] and qs[head][b] in place of control[b][0 .. nu) and status[b], and xnow in place
+ *           of x0 (xhat = xnow with the observer).  u_out, age_out and status_out therefore describe the command that REACHED THE PLANT,
+ *           issued D ticks ago; the estimator and the observer see the applied control; x_out, x_hist and the score's truth stay the
+ *           current true state (the plant's xp while the observer simulates one, else xnow).
+ *        2. a kernel of its own, ordered behind it, writes the last launched solve's control[b][0 .. nu) and status[b] into slot head --
+ *           the status is looked at first, a failed instance's control is never loaded and its slot holds NaN; `fresh` is not looked at,
+ *           as with K = 0 -- advances head, forms the prediction from the updated xnow, d and queue and stores it as the controller's x0.
+ *      u_init is [batch][nu] (NULL: zeros) and fills all D slots with status COPRA_QP_OK.  Every call of the setter resets the queue, one
+ *      that repeats the D in force included.  When delay is turned on xnow is seeded by a stream-ordered copy of the x0 in force (a caller's
+ *      device buffer is read once and never written); a call while it is on keeps xnow.  The setter launches the first prediction.  It
+ *      synchronises the stream of the last solve / tick once; the tick neither synchronises nor allocates.
+ *      copra_batch_set_x0, copra_batch_set_bias, copra_batch_set_system and copra_batch_set_system_rowmajor_async while delay is on keep
+ *      the queue, set xnow / d / the model and predict again, with the same kernel and its push off (no step: failed entries count as held).
+ *      copra_batch_set_shared_system keeps delay on; the prediction then reads the one system.  D = 0 makes xnow the x0 again.
+ *      copra_batch_set_observer while delay is on seeds the plant's own state from xnow, the state in force, not from the prediction.
+ *      copra_batch_input_delay: the D in force (-1: NULL handle).  copra_batch_delay_state_device / copra_batch_get_delay_state: xnow
+ *      [batch][nx].  copra_batch_get_delay_queue waits for the last tick and copies the queue OLDEST FIRST, q [batch][D][nu] and status
+ *      [batch][D] (either may be NULL); copra_batch_delay_queue_device gives the ring as it lies on the device -- q [batch][D][nu],
+ *      status [D][batch] -- with the slot `head` of the oldest entry; entry j, oldest first, is slot (head + j) % D.
+ *      A real plant: copra_batch_advance with y_meas works unchanged.  It needs the observer (C = I, Lx = I is full-state measurement): the
+ *      caller applies u_out, the popped command, and measures.
+ *      Schedules: the schedules' tick is untouched.  The solve at tick t plans from time t + D: a delayed loop passes offset + D to
+ *      copra_batch_set_reference_schedule, copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule and
+ *      copra_target_t::offset.  The score's reference needs no shift: it is compared with the current true state.
+ *      Not covered yet (follow-ups): delay together with backup plans (K > 0) or solve_every > 1 -- the plan store reads the tail of
+ *      `control` with its stride; whichever is asked for second gets COPRA_ERR_RUNTIME --, per-instance delays, fractional delays, and
+ *      fusing the push and the prediction into the plant step's launch.
+ *      COPRA_ERR_ARG: a NULL handle, D outside 0 .. 8, a NULL destination.  COPRA_ERR_RUNTIME: no system or no x0 set yet, the getters
+ *      while delay is off, the exclusion above.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller, as for the tick itself; an
+ *      instance whose image does not fit the LDS. ---- */
+#define COPRA_DELAY_MAX 8
+copra_status_t copra_batch_set_input_delay(copra_batch_t* h, int steps, const double* u_init, int on_device);
+int copra_batch_input_delay(const copra_batch_t* h);
+const double* copra_batch_delay_state_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_delay_state(copra_batch_t* h, double* x);
+copra_status_t copra_batch_delay_queue_device(const copra_batch_t* h, const double** q, const int** status, int* head);
+copra_status_t copra_batch_get_delay_queue(copra_batch_t* h, double* q, int* status);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
