@@ -110,6 +110,27 @@ class ScoreSummary(C.Structure):
                 + [(n, C.c_longlong) for n in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")])
 
 
+class Trace(C.Structure):
+    """copra_trace_t: what copra_batch_set_trace records of every tick, and the limits of its viol row"""
+    _fields_ = [("struct_size", C.c_int), ("capacity", C.c_longlong), ("what", C.c_int), ("every", C.c_int), ("x_lo", C.c_void_p),
+                ("x_hi", C.c_void_p), ("u_lo", C.c_void_p), ("u_hi", C.c_void_p), ("tol", C.c_double), ("on_device", C.c_int)]
+
+
+class TraceHead(C.Structure):
+    """copra_trace_head_t: the 64 bytes in front of a slot's statistics"""
+    _fields_ = [(n, C.c_longlong) for n in ("tick", "tau", "solved", "replayed", "fallback", "held", "violating", "reserved")]
+
+
+TRACE_X, TRACE_U, TRACE_ERR = 1, 2, 4
+TRACE_HEAD_DTYPE = np.dtype([(n, "i8") for n, _ in TraceHead._fields_])
+SCORE_STAT_DTYPE = np.dtype([("n", "i8"), ("mean", "f8"), ("m2", "f8"), ("min", "f8"), ("max", "f8"), ("argmin", "i8"), ("argmax", "i8")])
+
+
+def trace_slot_dtype(rows):
+    """one slot of a trace: the head, then `rows` statistics"""
+    return np.dtype([("head", TRACE_HEAD_DTYPE), ("stat", SCORE_STAT_DTYPE, (rows,))])
+
+
 class Target(C.Structure):
     """copra_target_t: the controlled outputs, the setpoint signal and the driven costs of copra_batch_set_target"""
     _fields_ = [("struct_size", C.c_int), ("nr", C.c_int), ("H", C.c_void_p), ("r", C.c_void_p), ("steps", C.c_longlong), ("offset", C.c_int),
@@ -483,6 +504,18 @@ def lib():
         L.copra_batch_delay_queue_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
         L.copra_batch_get_delay_queue.restype = C.c_int
         L.copra_batch_get_delay_queue.argtypes = [vp, vp, vp]
+        L.copra_trace_init.restype = None
+        L.copra_trace_init.argtypes = [C.POINTER(Trace)]
+        L.copra_batch_set_trace.restype = C.c_int
+        L.copra_batch_set_trace.argtypes = [vp, C.POINTER(Trace)]
+        L.copra_batch_trace_reset.restype = C.c_int
+        L.copra_batch_trace_reset.argtypes = [vp]
+        L.copra_batch_trace_info.restype = C.c_int
+        L.copra_batch_trace_info.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        L.copra_batch_trace_device.restype = vp
+        L.copra_batch_trace_device.argtypes = [vp]
+        L.copra_batch_get_trace.restype = C.c_int
+        L.copra_batch_get_trace.argtypes = [vp, C.c_longlong, C.c_longlong, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

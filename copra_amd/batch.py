@@ -38,7 +38,7 @@ class BatchLMPC:
         # The tensors the library reads or writes in place, by slot; a setter fills its slot AFTER the library accepted the call (a refused
         # call leaves the tensors in force alive) and a host copy or None in a tensor's place empties it (_hold).  What else ends a slot:
         #   "system", "x0", "outputs", "tick"   only their own next call
-        #   "bias", "noise", "score"            X(None)
+        #   "bias", "noise", "score", "trace"   X(None)
         #   "observer", "target"                X(None); set_shared_system (the library ends both)
         #   ("reference", k)                    set_cost_reference(k, ..); set_reference_schedule(k, ..); set_target(.., costs with k)
         #   ("weights", k)                      set_cost_weights(k, None)
@@ -593,6 +593,75 @@ class BatchLMPC:
         out = {f: {k: getattr(getattr(s, f), k) for k, _ in _capi.ScoreStat._fields_} for f in ("jx", "ju", "viol_sum", "viol_max", "peak")}
         out.update({k: int(getattr(s, k)) for k in ("ticks", "held", "replayed", "fallback", "violating", "instances_violating", "instances_held")})
         return out
+
+    # ---- ensemble traces (copra_batch_set_trace, ABI 17): every recorded tick reduces the batch to one slot on the device ----
+    def set_trace(self, capacity, state=True, control=True, estimate_error=False, state_limits=None, control_limits=None, tol=0.0, every=1):
+        """Ensemble traces (copra_batch_set_trace): from now on every advance() / tick of rollout() whose count t since this call (or
+        reset_trace()) has t % every == 0 reduces the batch into the next of `capacity` slots on the device -- n, mean, m2, min, max, argmin,
+        argmax over the instances of every row of the true state (state), the applied control (control; a held instance has none), the
+        estimate minus the plant's state while the observer simulates a plant (estimate_error; empty on other ticks), and, with any limit,
+        the tick's largest violation (the score's rule) with the number of instances beyond tol -- so an envelope needs no x_hist / u_hist.
+        state_limits / control_limits: (lower, upper), each (nx,) / (nu,), one for the batch, or None; infinite entries are allowed.  numpy:
+        copied; torch CUDA float64 tensors (all of them then): used in place and kept alive.  A full trace records nothing further
+        (trace_info()["missed"] counts).  set_trace(None): tracing ends."""
+        if capacity is None:
+            _capi.check(self._lib.copra_batch_set_trace(self._h, None))
+            self._release("trace")
+            return
+        xl, xh = state_limits if state_limits is not None else (None, None)
+        ul, uh = control_limits if control_limits is not None else (None, None)
+        rows = dict(x_lo=self.nx, x_hi=self.nx, u_lo=self.nu, u_hi=self.nu)
+        args = {k: _args.expect(_args.marshal(v, "set_trace: " + k), (rows[k],), "set_trace: " + k)
+                for k, v in dict(x_lo=xl, x_hi=xh, u_lo=ul, u_hi=uh).items() if v is not None}
+        on_device = _args.same_way("set_trace", args.values())[0] if args else 0
+        m = _capi.Trace()
+        self._lib.copra_trace_init(C.byref(m))
+        for k in rows:
+            setattr(m, k, args[k].ptr if k in args else None)
+        m.capacity, m.every, m.tol, m.on_device = int(capacity), int(every), float(tol), on_device
+        m.what = (_capi.TRACE_X if state else 0) | (_capi.TRACE_U if control else 0) | (_capi.TRACE_ERR if estimate_error else 0)
+        _capi.check(self._lib.copra_batch_set_trace(self._h, C.byref(m)))
+        self._trace_groups = [(name, n) for name, n, on in (("x", self.nx, state), ("u", self.nu, control), ("err", self.nx, estimate_error)) if on]
+        self._trace_viol = bool(args)
+        self._hold("trace", *args.values())
+
+    def reset_trace(self):
+        """the trace's tick count back to 0, in stream order behind the last tick (copra_batch_trace_reset): the next recorded tick is slot 0"""
+        _capi.check(self._lib.copra_batch_trace_reset(self._h))
+
+    def trace_info(self):
+        """dict(recorded, missed, rows, slot_bytes) of copra_batch_trace_info: slots written, recordable ticks a full trace let pass, the
+        statistics per slot and its size (64 + 56 rows)"""
+        rec, mis, rows, size = C.c_longlong(), C.c_longlong(), C.c_int(), C.c_longlong()
+        _capi.check(self._lib.copra_batch_trace_info(self._h, C.byref(rec), C.byref(mis), C.byref(rows), C.byref(size)))
+        return dict(recorded=rec.value, missed=mis.value, rows=rows.value, slot_bytes=size.value)
+
+    def trace_slots(self):
+        """the recorded slots as they lie on the device: a numpy structured array (_capi.trace_slot_dtype(rows): head, stat[rows]); waits for
+        the last tick (copra_batch_get_trace)"""
+        info = self.trace_info()
+        out = np.zeros(info["recorded"], dtype=_capi.trace_slot_dtype(info["rows"]))
+        assert out.dtype.itemsize == info["slot_bytes"]
+        _capi.check(self._lib.copra_batch_get_trace(self._h, 0, info["recorded"], out.ctypes.data))
+        return out
+
+    def trace(self):
+        """the trace as a dict: head, a structured array (tick, tau, solved, replayed, fallback, held, violating, reserved) with one entry
+        per recorded tick; x, u, err: structured (ticks, rows) arrays of n / mean / m2 / min / max / argmin / argmax for the groups that
+        set_trace asked for; viol (ticks,) likewise where limits were given (variance = m2 / (n - 1)).  Waits for the last tick."""
+        slots = self.trace_slots()
+        out, at = dict(head=slots["head"].copy()), 0
+        for name, n in self._trace_groups:
+            out[name] = slots["stat"][:, at:at + n].copy()
+            at += n
+        if self._trace_viol:
+            out["viol"] = slots["stat"][:, at].copy()
+        return out
+
+    @property
+    def trace_ptr(self):
+        """device pointer of the slots (copra_batch_trace_device); 0 while tracing is off"""
+        return int(self._lib.copra_batch_trace_device(self._h) or 0)
 
     # ---- steady-state targets (copra_batch_set_target, ABI 15): the references of the driven costs follow d and a setpoint ----
     def _step_map(self, cost_index):

@@ -11,6 +11,7 @@
 // copra_batch_set_noise / _noise_seek / _noise_tick / _draw_noise: Monte-Carlo ticks -- phase 1 of the plant step draws process and sensor
 // noise from a counter-based generator (plant_noise.hpp) at the handle's noise tick; builds of the kernels of their own, no memory.
 // copra_batch_set_score (copra_hip_score.hip): while scoring is on, advance() hands the tick's state, control and age to launch_score.
+// copra_batch_set_trace (copra_hip_trace.hip): while tracing is on, advance() hands the same, and the estimate, to launch_trace behind it.
 // copra_batch_set_target (copra_hip_target.hip): while targets are on, advance(), copra_batch_schedule_seek and copra_batch_set_bias call
 // launch_target behind what they did -- the steady states and the driven costs' references follow d and the setpoint.
 #include "engine.hpp"
@@ -237,6 +238,10 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
         if (!P.u_out) P.u_out = h->d_score_u;
         if (!P.age_out) P.age_out = h->d_score_age;
     }
+    if (h->trace_on) { // ... and the trace likewise, with the buffers copra_batch_set_trace took
+        if (!P.u_out) P.u_out = h->d_trace_u;
+        if (!P.age_out) P.age_out = h->d_trace_age;
+    }
     if (h->backup_steps > 0) {
         P.backup_steps = h->backup_steps;
         P.fresh = h->plan_fresh;
@@ -287,6 +292,12 @@ copra_status_t advance(copra_batch* h, const copra_plant_step_t& st, const TickI
         const double* const now = h->delay > 0 ? (const double*)h->d_delay_x : h->x0; // (input delay: x0 is the prediction, the state is xnow)
         const double* const truth = h->obs_on && !io.y_meas ? (const double*)h->d_xp : now; // on a y_meas tick, where no truth exists)
         const copra_status_t rc = launch_score(h, truth, P.u_out, P.age_out, s, who);
+        if (rc != COPRA_OK) return rc;
+    }
+    if (h->trace_on) { // the fleet's statistics of this tick, from the same true state; the estimate beside it where the observer simulates a plant
+        const double* const now = h->delay > 0 ? (const double*)h->d_delay_x : h->x0;
+        const bool simulated = h->obs_on && !io.y_meas;
+        const copra_status_t rc = launch_trace(h, simulated ? (const double*)h->d_xp : now, simulated ? now : nullptr, P.u_out, P.age_out, s, who);
         if (rc != COPRA_OK) return rc;
     }
     const copra_status_t rc = write_windows(h, s, who);

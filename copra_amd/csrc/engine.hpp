@@ -19,6 +19,8 @@
 //   copra_hip_delay.hip    input delay in the tick: copra_batch_set_input_delay / _input_delay / _delay_state_device / _get_delay_state /
 //                          _delay_queue_device / _get_delay_queue and their kernel (delay_step.hpp); launch_delay below is what the tick calls
 //                          behind its plant step while delay is on, and what the setters that move the state, d or the model call
+//   copra_hip_trace.hip    ensemble traces: copra_batch_set_trace / _trace_reset / _trace_info / _trace_device / _get_trace and their kernel
+//                          (trace_step.hpp); launch_trace below is what the tick calls behind its score while tracing is on
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -156,6 +158,7 @@ struct LimitSchedule {
 };
 
 constexpr int kScoreArrays = 7; // the arrays of a score's measure (copra_score_t)
+constexpr int kTraceArrays = 4; // the limits of a trace (copra_trace_t)
 constexpr int kTargetCosts = 8; // the costs one target calculation drives (copra_target_t; kTargetMaxCosts of target_step.hpp)
 
 // Ownership is by type: a Dev<T> / PinnedBuf<T> / Bag member owns its memory and frees it with the handle; every raw pointer is borrowed
@@ -259,6 +262,18 @@ struct copra_batch {
     Dev<double> d_delay_q; // [batch][D][nu]: the pending commands
     Dev<int> d_delay_qs; // [D][batch]: the status of the solve that issued each
     Dev<double> d_delay_x; // [batch][nx]: xnow -- the measured state, or the observer's estimate
+    // ensemble traces (copra_batch_set_trace; copra_hip_trace.hip, trace_step.hpp): every buffer is taken by the setter, never by the tick; the
+    // slot a recorded tick writes is counted HERE, on the host, and handed to its launches
+    bool trace_on = false;
+    int trace_what = 0, trace_every = 1, trace_rows = 0, trace_in_lds = 0;
+    long long trace_cap = 0; // slots
+    long long trace_tick = 0, trace_recorded = 0, trace_missed = 0; // ticks since the last set / reset; slots written; recordable ticks a full trace let pass
+    double trace_tol = 0.0;
+    DevIn<double> trace_lim[kTraceArrays]; // x_lo, x_hi, u_lo, u_hi; null: not given
+    Dev<unsigned char> d_trace; // [capacity] slots
+    Dev<unsigned char> d_trace_part; // [chunks] partials of a tick's first stage, slot-shaped
+    Dev<double> d_trace_u; // [batch][nu]: the tick's u_out where neither the caller nor the score gave one ...
+    Dev<int> d_trace_age; // ... and [batch] its age_out
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -426,6 +441,10 @@ fused_kernel_t select_tier2_kernel(const FusedPlan& P);
 // ---- copra_hip_score.hip: one tick's update of the records, on `s` behind the plant step -- x [batch][nx] the true state after the tick, u
 // [batch][nu] and age [batch] what the tick wrote as u_out / age_out; called only while h->score_on; no synchronisation, no allocation ----
 copra_status_t launch_score(copra_batch* h, const double* x, const double* u, const int* age, hipStream_t s, const char* who);
+// ---- copra_hip_trace.hip: one tick of the trace, on `s` behind the score -- x, u, age as for launch_score; est [batch][nx] the estimate of the
+// same tick where the observer simulates a plant (x is then the plant's own state), else null; called only while h->trace_on; moves the trace's
+// tick count, launches on a recorded tick only; no synchronisation, no allocation ----
+copra_status_t launch_trace(copra_batch* h, const double* x, const double* est, const double* u, const int* age, hipStream_t s, const char* who);
 // ---- copra_hip_target.hip: the steady states and the driven costs' references from the model, the d and the setpoint's block in force, on
 // `s` (behind the handle's last stream where that is another one); returns at once while targets are off; no synchronisation, no allocation ----
 copra_status_t launch_target(copra_batch* h, hipStream_t s, const char* who);

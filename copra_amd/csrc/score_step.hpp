@@ -409,7 +409,7 @@ COPRA_DEV ScoreCounts score_fold_counts(const ScoreReduceArgs& R, int wg, int ti
     return acc;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(COPRA_SCORE_HELPERS_ONLY) // (copra_hip_trace.hip takes the helpers alone: the kernels have ONE home, copra_hip_score.hip)
 __global__ __launch_bounds__(kScoreThreads) void copra_score_kernel(const ScoreArgs S)
 {
     extern __shared__ __align__(16) double score_image[];
@@ -422,7 +422,9 @@ __global__ __launch_bounds__(kScoreThreads) void copra_score_kernel(const ScoreA
     __syncthreads();
     score_store(S, wg, tid, kScoreThreads, score_image);
 }
+#endif
 
+#if defined(__HIPCC__)
 __device__ __forceinline__ ScoreStat score_shfl_down(const ScoreStat& p, int off)
 {
     ScoreStat q;
@@ -440,6 +442,9 @@ __device__ __forceinline__ ScoreCounts score_shfl_down(const ScoreCounts& p, int
     return q;
 }
 
+#endif
+
+#if defined(__HIPCC__) && !defined(COPRA_SCORE_HELPERS_ONLY)
 static_assert(sizeof(ScoreStat) == sizeof(ScoreCounts), "the waves' words in LDS serve both");
 __global__ __launch_bounds__(kScoreThreads) void copra_score_reduce_kernel(const ScoreReduceArgs R)
 {

@@ -72,6 +72,46 @@ def merge_score_summaries(summaries, first_instances):
     return out
 
 
+TRACE_COUNTS = ("solved", "replayed", "fallback", "held", "violating")
+
+
+def merge_traces(traces, first_instances):
+    """The trace of a batch spread over handles from the handles' own BatchLMPC.trace() dicts, tick by tick: every row's statistics are merged
+    with the device's rule (_merge_score_stat) in the order given, first_instances[k] added to handle k's argmin / argmax (-1 stays), the
+    head counts added.  The shards must have recorded the same ticks: `tick` and `tau` equal across them (ValueError otherwise).  Counts, n,
+    min, max and args are those of one trace over the whole batch; mean and m2 agree with it to rounding."""
+    import numpy as np
+    if len(traces) != len(first_instances):
+        raise ValueError("merge_traces: one first instance per trace")
+    if not traces:
+        raise ValueError("merge_traces: no trace")
+    head = traces[0]["head"].copy()
+    groups = [k for k in ("x", "u", "err", "viol") if k in traces[0]]
+    for t in traces[1:]:
+        if [k for k in ("x", "u", "err", "viol") if k in t] != groups or any(t[k].shape != traces[0][k].shape for k in groups):
+            raise ValueError("merge_traces: the traces record different rows")
+        if not (np.array_equal(t["head"]["tick"], head["tick"]) and np.array_equal(t["head"]["tau"], head["tau"])):
+            raise ValueError("merge_traces: the traces record different ticks")
+        for k in TRACE_COUNTS:
+            head[k] += t["head"][k]
+    out = dict(head=head)
+    fields = traces[0][groups[0]].dtype.names if groups else ()
+    for g in groups:
+        merged = traces[0][g].copy()
+        flat = merged.reshape(-1)
+        for e in range(flat.size):
+            acc = None
+            for t, first in zip(traces, first_instances):
+                st = {f: t[g].reshape(-1)[e][f].item() for f in fields}
+                for arg in ("argmin", "argmax"):
+                    st[arg] = st[arg] + int(first) if st[arg] >= 0 else -1
+                acc = st if acc is None else _merge_score_stat(acc, st)
+            for f in fields:
+                flat[f][e] = acc[f]
+        out[g] = merged
+    return out
+
+
 def slab_layout(batch, n, X):
     """byte offsets of the four result arrays inside one flat slab (all 8-byte aligned): [U | status | iter | X].  The
     trajectory comes LAST so that the head of the slab -- controls, status, iteration counts: 492 of the 1500 bytes per instance at

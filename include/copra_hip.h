@@ -778,6 +778,76 @@ copra_status_t copra_batch_get_delay_state(copra_batch_t* h, double* x);
 copra_status_t copra_batch_delay_queue_device(const copra_batch_t* h, const double** q, const int** status, int* head);
 copra_status_t copra_batch_get_delay_queue(copra_batch_t* h, double* q, int* status);
 
+/* ---- ensemble traces: per-tick fleet statistics on the device (ABI 17).  The scores above reduce a run to one record per instance: how
+ *      each robot did over the whole run.  A Monte-Carlo study also asks how the FLEET looked at tick t -- the mean, spread and extremes of
+ *      every state and control, the share violating a limit, the share held or on a backup plan, the observer's ensemble error -- which
+ *      otherwise takes x_hist / u_hist / age_hist / xhat_hist off the device.  A trace is a buffer of `capacity` slots on the device; every
+ *      recorded tick reduces the batch into the next slot, behind the score on the tick's stream.
+ *      The slot: one copra_trace_head_t (64 bytes), then `rows` copra_score_stat_t in the order x, u, err, viol -- the groups `what` names
+ *      and, where any limit is given, ONE row viol: 64 + 56 rows bytes.
+ *        COPRA_TRACE_X    nx rows: the true state after the tick -- the state the score reads: the plant's own while the observer
+ *                         simulates one, the estimate on a y_meas tick, xnow under an input delay, otherwise the new x0
+ *        COPRA_TRACE_U    nu rows: the applied control (u_out); a HELD instance has none -- its age decides, its NaN row is never read
+ *        COPRA_TRACE_ERR  nx rows: estimate - plant state (one subtraction; the estimate of the same tick, xnow under delay) on ticks where
+ *                         the observer simulates a plant; on every other tick the rows are empty statistics
+ *        viol             vmax, the score's own rule: the largest of max(0, lo_r - z_r, z_r - hi_r) over the rows of x, then of u (held: no
+ *                         u rows); comparisons with `>` from 0.0, so a NaN row counts 0
+ *      A row's statistic is over the instances whose value is FINITE, as in the summary: n, mean, m2, min, max, argmin, argmax (ties: the
+ *      lowest index); with n == 0: mean = m2 = 0, min = +inf, max = -inf, arg = -1.
+ *      The head: tick, the trace's own tick count since the last set or reset (0 for the first); tau, the schedule tick after that tick;
+ *      solved = #(age == 0), replayed = #(age >= 1), fallback = #(age == COPRA_PLAN_FALLBACK), held = #(age == COPRA_PLAN_HELD) -- they sum
+ *      to the batch --; violating = #(vmax > tol), 0 without limits; reserved = 0.
+ *      The reduction order is the contract.  Row r of a recorded tick is reduced exactly as copra_batch_score_summary reduces a field, with
+ *      "record i" read as "instance i's value of row r":
+ *        stage 1: chunk c is instances [1024 c, 1024 (c + 1)), one workgroup of 256 threads each.  Thread t merges, from the empty statistic,
+ *                 instances 1024 c + t, + 256, + 512, + 768 in ascending order; inside each wave of 64 lanes, for off = 32, 16, 8, 4, 2, 1,
+ *                 lane l <- merge(lane l, lane l + off); thread 0 merges the four waves in ascending order, (((w0, w1), w2), w3).
+ *        stage 2: one workgroup over the chunks' partials: thread t merges partials t, t + 256, ... in ascending order, then the same lane
+ *                 tree and fold of the waves.
+ *      The head counts are integer sums through the same tree.  No floating-point atomics, no counter on the device: two traces of the
+ *      same run are equal byte for byte, whatever the grid or the occupancy.
+ *      Which ticks: with t the trace's tick count, the ticks with t % every == 0 are recorded (every == 0 means 1).  t moves at every tick
+ *      while tracing is on.  A tick never fails because the trace is full: further ticks are not recorded and `missed` counts them.
+ *      Lifetime: copra_batch_set_trace takes the slots, the partials and -- for ticks where neither the caller nor the score supplies u_out /
+ *      age_out -- buffers for them; it waits for the handle's last stream once.  A call while tracing is on replaces the trace and restarts
+ *      it; copra_batch_set_trace(h, NULL) ends tracing and releases the buffers; copra_batch_trace_reset takes the tick count back to 0 in
+ *      stream order: the next recorded tick writes slot 0 behind everything launched before.  copra_batch_trace_info reports the slots
+ *      recorded, the ticks missed, the rows and the bytes of a slot (each pointer may be NULL); copra_batch_trace_device returns the slots
+ *      on the device (NULL while tracing is off); copra_batch_get_trace waits for the last tick and copies slots [first, first + count).
+ *      The tick: two launches per recorded tick behind the score and before the schedule windows, no synchronisation, no allocation;
+ *      while tracing was never enabled the tick launches exactly what it launched in ABI 16.  Tracing works with backup plans, solve_every,
+ *      the estimator, the observer and y_meas, noise, scores, targets, input delay, every schedule and the shared model: it only reads what
+ *      they decided.  Limits on the device (on_device) are used in place and must stay valid; host limits are copied.
+ *      Not covered yet (follow-ups): per-instance limits or a reference signal in the trace, quantiles, and a one-launch variant in which
+ *      the last workgroup does stage 2.
+ *      COPRA_ERR_ARG: a NULL handle, capacity < 1, no (or an unknown) `what` bit, every < 0, a negative or NaN tol, lo > hi or a NaN limit
+ *      in a host array, a NULL destination, first / count outside the recorded slots.  COPRA_ERR_RUNTIME: reset, info or get while tracing
+ *      is off.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller, as for the tick itself. ---- */
+#define COPRA_TRACE_X 1
+#define COPRA_TRACE_U 2
+#define COPRA_TRACE_ERR 4
+typedef struct {
+    int struct_size; /* append-only, set by copra_trace_init */
+    long long capacity; /* recorded ticks the trace holds, >= 1 */
+    int what; /* COPRA_TRACE_* bits, at least one */
+    int every; /* record the ticks t with t % every == 0 (0 means 1) */
+    const double* x_lo; /* [nx], one for the batch; NULL: none */
+    const double* x_hi;
+    const double* u_lo; /* [nu] likewise; any limit given adds ONE row viol and the count violating */
+    const double* u_hi;
+    double tol; /* >= 0 */
+    int on_device; /* limits used in place, must stay valid; else copied */
+} copra_trace_t;
+typedef struct {
+    long long tick, tau, solved, replayed, fallback, held, violating, reserved;
+} copra_trace_head_t;
+void copra_trace_init(copra_trace_t* trace);
+copra_status_t copra_batch_set_trace(copra_batch_t* h, const copra_trace_t* trace);
+copra_status_t copra_batch_trace_reset(copra_batch_t* h);
+copra_status_t copra_batch_trace_info(const copra_batch_t* h, long long* recorded, long long* missed, int* rows, long long* slot_bytes);
+const void* copra_batch_trace_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_trace(copra_batch_t* h, long long first, long long count, void* host);
+
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
  *      (src/LMPC.cpp:233-247).  Here the caller hands the whole reference SIGNAL of cost `cost_index` over once,
