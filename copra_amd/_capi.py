@@ -122,6 +122,7 @@ class TraceHead(C.Structure):
 
 
 TRACE_X, TRACE_U, TRACE_ERR = 1, 2, 4
+TRACE_QUANT_MAX = 8  # COPRA_TRACE_QUANT_MAX
 TRACE_HEAD_DTYPE = np.dtype([(n, "i8") for n, _ in TraceHead._fields_])
 SCORE_STAT_DTYPE = np.dtype([("n", "i8"), ("mean", "f8"), ("m2", "f8"), ("min", "f8"), ("max", "f8"), ("argmin", "i8"), ("argmax", "i8")])
 
@@ -516,6 +517,14 @@ def lib():
         L.copra_batch_trace_device.argtypes = [vp]
         L.copra_batch_get_trace.restype = C.c_int
         L.copra_batch_get_trace.argtypes = [vp, C.c_longlong, C.c_longlong, vp]
+        L.copra_batch_set_trace_quantiles.restype = C.c_int
+        L.copra_batch_set_trace_quantiles.argtypes = [vp, C.POINTER(C.c_double), C.c_int]
+        L.copra_batch_trace_quantile_info.restype = C.c_int
+        L.copra_batch_trace_quantile_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.copra_batch_trace_quantiles_device.restype = vp
+        L.copra_batch_trace_quantiles_device.argtypes = [vp]
+        L.copra_batch_get_trace_quantiles.restype = C.c_int
+        L.copra_batch_get_trace_quantiles.argtypes = [vp, C.c_longlong, C.c_longlong, vp]
         L.copra_batch_x0_device.restype = vp
         L.copra_batch_x0_device.argtypes = [vp]
         L.copra_batch_get_x0.restype = C.c_int

@@ -663,6 +663,43 @@ class BatchLMPC:
         """device pointer of the slots (copra_batch_trace_device); 0 while tracing is off"""
         return int(self._lib.copra_batch_trace_device(self._h) or 0)
 
+    # ---- trace quantiles (copra_batch_set_trace_quantiles, ABI 18): exact order statistics of every row of a recorded tick ----
+    def set_trace_quantiles(self, levels):
+        """Trace quantiles (copra_batch_set_trace_quantiles): from now on every recorded tick of the trace in force also selects, for every
+        row of its slot and every level p in `levels` (at most 8, each in [0, 1], in any order, repeats allowed), the order statistic
+        k = min(n - 1, max(0, ceil(p n) - 1)) of the row's n finite values -- numpy's method="inverted_cdf": 0 the minimum, 1 the maximum, 0.5
+        the lower median; NaN for a row without a finite value -- so a percentile band needs no x_hist / u_hist.  Needs set_trace first and
+        restarts the trace, so every recorded slot has its quantiles.  None or an empty list ends quantiles and keeps the trace; set_trace
+        ends them too."""
+        lv = np.zeros(0) if levels is None else np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+        if lv.size == 0:
+            _capi.check(self._lib.copra_batch_set_trace_quantiles(self._h, None, 0))
+            return
+        _capi.check(self._lib.copra_batch_set_trace_quantiles(self._h, lv.ctypes.data_as(C.POINTER(C.c_double)), int(lv.size)))
+
+    def trace_quantiles(self):
+        """the quantiles of the recorded ticks as a dict: levels (nq,); x, u, err: (ticks, rows, nq) float64 for the groups set_trace asked
+        for; viol (ticks, nq) where limits were given -- the groups trace() returns, slot k of one beside slot k of the other.  Waits for the
+        last tick (copra_batch_get_trace_quantiles)."""
+        nq, lv = C.c_int(), (C.c_double * _capi.TRACE_QUANT_MAX)()
+        _capi.check(self._lib.copra_batch_trace_quantile_info(self._h, C.byref(nq), lv))
+        info = self.trace_info()
+        flat = np.zeros((info["recorded"], info["rows"], nq.value))
+        if flat.size:
+            _capi.check(self._lib.copra_batch_get_trace_quantiles(self._h, 0, info["recorded"], flat.ctypes.data))
+        out, at = dict(levels=np.array(lv[:nq.value], dtype=np.float64)), 0
+        for name, n in self._trace_groups:
+            out[name] = flat[:, at:at + n].copy()
+            at += n
+        if self._trace_viol:
+            out["viol"] = flat[:, at].copy()
+        return out
+
+    @property
+    def trace_quantiles_ptr(self):
+        """device pointer of the quantile buffer [capacity][rows][levels] (copra_batch_trace_quantiles_device); 0 while quantiles are off"""
+        return int(self._lib.copra_batch_trace_quantiles_device(self._h) or 0)
+
     # ---- steady-state targets (copra_batch_set_target, ABI 15): the references of the driven costs follow d and a setpoint ----
     def _step_map(self, cost_index):
         """T_c = [M_c N_c] of the step form of cost `cost_index` (natural indexing) and its rows r_c, from the dict the constructor received: a

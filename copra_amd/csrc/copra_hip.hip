@@ -912,7 +912,7 @@ bool use_riccati(copra_batch* h)
 
 extern "C" {
 
-int copra_abi_version(void) { return 17; } // 17: + COPRA_TRACE_X / _U / _ERR, copra_trace_t, copra_trace_head_t, copra_trace_init, copra_batch_set_trace, copra_batch_trace_reset, copra_batch_trace_info, copra_batch_trace_device, copra_batch_get_trace; 16: + COPRA_DELAY_MAX, copra_batch_set_input_delay, copra_batch_input_delay, copra_batch_delay_state_device, copra_batch_get_delay_state, copra_batch_delay_queue_device, copra_batch_get_delay_queue; 15: + copra_target_t, copra_target_init, copra_batch_set_target, copra_batch_target_device, copra_batch_target_status_device, copra_batch_get_target, copra_batch_get_cost_reference; 14: + copra_score_t, copra_score_init, copra_batch_set_score, copra_batch_score_reset, copra_batch_score_device, copra_batch_get_score, copra_batch_score_summary; 13: + copra_noise_t, copra_noise_init, copra_batch_set_noise, copra_batch_noise_seek, copra_batch_noise_tick, copra_batch_draw_noise; 12: + copra_batch_set_observer, copra_batch_set_plant_state, copra_batch_plant_state_device, copra_batch_get_plant_state, copra_plant_step_obs_t (v, y_meas, y_out, xhat_out, v_seq, y_hist, xhat_hist), copra_plant_step_obs_init; 11: + copra_batch_set_bias_estimator, copra_batch_set_bias, copra_batch_bias_device, copra_batch_get_bias, copra_plant_step_ex_t (d_out, d_hist), copra_plant_step_ex_init; 10: + copra_batch_set_backup_steps, copra_plant_step_t::age_out / age_hist / solve_every; 9: + copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
+int copra_abi_version(void) { return 18; } // 18: + COPRA_TRACE_QUANT_MAX, copra_batch_set_trace_quantiles, copra_batch_trace_quantile_info, copra_batch_trace_quantiles_device, copra_batch_get_trace_quantiles; 17: + COPRA_TRACE_X / _U / _ERR, copra_trace_t, copra_trace_head_t, copra_trace_init, copra_batch_set_trace, copra_batch_trace_reset, copra_batch_trace_info, copra_batch_trace_device, copra_batch_get_trace; 16: + COPRA_DELAY_MAX, copra_batch_set_input_delay, copra_batch_input_delay, copra_batch_delay_state_device, copra_batch_get_delay_state, copra_batch_delay_queue_device, copra_batch_get_delay_queue; 15: + copra_target_t, copra_target_init, copra_batch_set_target, copra_batch_target_device, copra_batch_target_status_device, copra_batch_get_target, copra_batch_get_cost_reference; 14: + copra_score_t, copra_score_init, copra_batch_set_score, copra_batch_score_reset, copra_batch_score_device, copra_batch_get_score, copra_batch_score_summary; 13: + copra_noise_t, copra_noise_init, copra_batch_set_noise, copra_batch_noise_seek, copra_batch_noise_tick, copra_batch_draw_noise; 12: + copra_batch_set_observer, copra_batch_set_plant_state, copra_batch_plant_state_device, copra_batch_get_plant_state, copra_plant_step_obs_t (v, y_meas, y_out, xhat_out, v_seq, y_hist, xhat_hist), copra_plant_step_obs_init; 11: + copra_batch_set_bias_estimator, copra_batch_set_bias, copra_batch_bias_device, copra_batch_get_bias, copra_plant_step_ex_t (d_out, d_hist), copra_plant_step_ex_init; 10: + copra_batch_set_backup_steps, copra_plant_step_t::age_out / age_hist / solve_every; 9: + copra_batch_set_constraint_schedule, copra_batch_set_control_bound_schedule; 8: + copra_batch_set_reference_schedule, copra_batch_schedule_seek, copra_batch_schedule_tick; 7: + copra_plant_step_t, copra_plant_step_init, copra_batch_advance, copra_batch_rollout, copra_batch_x0_device, copra_batch_get_x0; 6: + copra_batch_set_cost_weights; 5: + copra_options_t, copra_options_init, copra_set_default_options, copra_batch_create_with_options; 3: + copra_batch_last_first_tier_seconds, copra_batch_set_system_rowmajor_async; 4: + copra_batch_lane_pass_info, copra_batch_set_cost_reference_all
 
 const char* copra_last_error(void) { return g_copra_err.c_str(); }
 

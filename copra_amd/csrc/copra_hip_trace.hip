@@ -21,6 +21,7 @@ namespace {
 void trace_off(copra_batch* h) // (a release waits for a tick that still uses the buffer)
 {
     h->trace_on = false;
+    trace_quant_off(h); // (quantiles belong to the trace in force)
     for (int k = 0; k < kTraceArrays; ++k) h->trace_lim[k].reset();
     h->d_trace.reset();
     h->d_trace_part.reset();
@@ -62,7 +63,7 @@ copra_status_t launch_trace(copra_batch* h, const double* x, const double* est, 
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(copra_trace_kernel<2>, dim3(1), dim3(kScoreThreads), 0, s, T);
     HIP_TRY(hipGetLastError());
-    return COPRA_OK;
+    return launch_trace_quant(h, T, slot, s, who); // (copra_hip_trace_quant.hip: one launch more while quantiles are on, else nothing)
 }
 
 extern "C" {
@@ -110,6 +111,7 @@ copra_status_t copra_batch_set_trace(copra_batch_t* h, const copra_trace_t* trac
     if ((double)m.capacity * (double)slot > 1e15) return fail(COPRA_ERR_ARG, std::string(who) + ": capacity beyond any device");
     h->trace_on = false; // (a failed attempt leaves the feature off, never a trace half replaced)
     HIP_TRY(hipStreamSynchronize(h->last_stream)); // a tick that still writes the old slots or reads the old limits first
+    trace_quant_off(h); // (the quantiles of the trace this one replaces end with it: copra_batch_set_trace_quantiles)
     for (int k = 0; k < kTraceArrays; ++k) {
         if (m.on_device || !arr[k]) h->trace_lim[k].borrow(arr[k]);
         else OWN_TRY(h->trace_lim[k].copy_in(arr[k], count[k]));

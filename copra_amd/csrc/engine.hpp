@@ -21,6 +21,9 @@
 //                          behind its plant step while delay is on, and what the setters that move the state, d or the model call
 //   copra_hip_trace.hip    ensemble traces: copra_batch_set_trace / _trace_reset / _trace_info / _trace_device / _get_trace and their kernel
 //                          (trace_step.hpp); launch_trace below is what the tick calls behind its score while tracing is on
+//   copra_hip_trace_quant.hip  trace quantiles: copra_batch_set_trace_quantiles / _trace_quantile_info / _trace_quantiles_device /
+//                          _get_trace_quantiles and their kernel (trace_quant_step.hpp); launch_trace_quant below is what launch_trace calls
+//                          behind its own launches while quantiles are on
 // and, host only and free of HIP: device_mem.hpp, the owners of device and pinned memory.  The two allocator policies below are the only
 // place in the library that allocates or frees.
 #pragma once
@@ -274,6 +277,13 @@ struct copra_batch {
     Dev<unsigned char> d_trace_part; // [chunks] partials of a tick's first stage, slot-shaped
     Dev<double> d_trace_u; // [batch][nu]: the tick's u_out where neither the caller nor the score gave one ...
     Dev<int> d_trace_age; // ... and [batch] its age_out
+    // trace quantiles (copra_batch_set_trace_quantiles; copra_hip_trace_quant.hip, trace_quant_step.hpp): they belong to the trace in force --
+    // the slot index is the trace's, and whatever ends or replaces the trace ends them
+    bool quant_on = false;
+    int quant_count = 0; // levels
+    double quant_level[COPRA_TRACE_QUANT_MAX] = {};
+    Dev<double> d_quant; // [capacity][rows][levels]
+    Dev<unsigned long long> d_quant_keys; // [rows][batch]: the keys of a recorded tick, written by the kernel's first pass
     Dev<double> d_cost_w[kMaxCosts]; // per-instance cost weights (owned copies) ...
     const double* cost_w[kMaxCosts] = {}; // ... or borrowed device pointers (copra_batch_set_cost_weights)
     // While a controller has per-instance weights its first tier must not be the Riccati-factor tier (its tables hold the creation
@@ -445,6 +455,14 @@ copra_status_t launch_score(copra_batch* h, const double* x, const double* u, co
 // same tick where the observer simulates a plant (x is then the plant's own state), else null; called only while h->trace_on; moves the trace's
 // tick count, launches on a recorded tick only; no synchronisation, no allocation ----
 copra_status_t launch_trace(copra_batch* h, const double* x, const double* est, const double* u, const int* age, hipStream_t s, const char* who);
+// ---- copra_hip_trace_quant.hip: the quantiles of a recorded tick, on `s` behind the trace's launches -- T the tick as launch_trace handed it
+// to its kernels, `slot` the slot it counted; returns at once while quantiles are off; no synchronisation, no allocation.  trace_quant_off:
+// quantiles end and their buffers go ----
+namespace copra_hip {
+struct TraceArgs;
+}
+copra_status_t launch_trace_quant(copra_batch* h, const copra_hip::TraceArgs& T, long long slot, hipStream_t s, const char* who);
+void trace_quant_off(copra_batch* h);
 // ---- copra_hip_target.hip: the steady states and the driven costs' references from the model, the d and the setpoint's block in force, on
 // `s` (behind the handle's last stream where that is another one); returns at once while targets are off; no synchronisation, no allocation ----
 copra_status_t launch_target(copra_batch* h, hipStream_t s, const char* who);

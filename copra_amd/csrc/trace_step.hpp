@@ -284,7 +284,7 @@ COPRA_DEV void trace_store_counts(const TraceArgs& T, int stage, int wg, const S
     *reinterpret_cast<TraceHead*>(T.slot) = h;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(COPRA_TRACE_HELPERS_ONLY) // (copra_hip_trace_quant.hip takes the helpers alone: the kernels have ONE home, copra_hip_trace.hip)
 // One part (a row, or the counts) of one workgroup, done by ONE wave: its lane l plays the threads l, 64 + l, 128 + l, 192 + l of the written
 // order -- four folds, then the lane tree of the four waves side by side, four chains that do not depend on each other and hide each other's
 // latency (a merge is two divisions deep) --, and lane 0 folds the four in ascending order.  Which wave computes a part changes no bit of it:

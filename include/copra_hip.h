@@ -818,8 +818,8 @@ copra_status_t copra_batch_get_delay_queue(copra_batch_t* h, double* q, int* sta
  *      while tracing was never enabled the tick launches exactly what it launched in ABI 16.  Tracing works with backup plans, solve_every,
  *      the estimator, the observer and y_meas, noise, scores, targets, input delay, every schedule and the shared model: it only reads what
  *      they decided.  Limits on the device (on_device) are used in place and must stay valid; host limits are copied.
- *      Not covered yet (follow-ups): per-instance limits or a reference signal in the trace, quantiles, and a one-launch variant in which
- *      the last workgroup does stage 2.
+ *      Not covered yet (follow-ups): per-instance limits or a reference signal in the trace, and a one-launch variant in which the last
+ *      workgroup does stage 2.
  *      COPRA_ERR_ARG: a NULL handle, capacity < 1, no (or an unknown) `what` bit, every < 0, a negative or NaN tol, lo > hi or a NaN limit
  *      in a host array, a NULL destination, first / count outside the recorded slots.  COPRA_ERR_RUNTIME: reset, info or get while tracing
  *      is off.  COPRA_ERR_UNSUPPORTED: an InitialStateLMPC controller, as for the tick itself. ---- */
@@ -847,6 +847,43 @@ copra_status_t copra_batch_trace_reset(copra_batch_t* h);
 copra_status_t copra_batch_trace_info(const copra_batch_t* h, long long* recorded, long long* missed, int* rows, long long* slot_bytes);
 const void* copra_batch_trace_device(const copra_batch_t* h);
 copra_status_t copra_batch_get_trace(copra_batch_t* h, long long first, long long count, void* host);
+
+/* ---- trace quantiles: exact per-tick fleet percentiles on the device (ABI 18).  A slot's mean and spread are a band for a Gaussian row; a
+ *      velocity against its bound or the violation row, zero for most of the fleet, is none, and the extremes are one robot each.  With
+ *      copra_batch_set_trace_quantiles every recorded tick also selects, for every row of the slot and each of `count` levels, an order
+ *      statistic of the row -- where 5 %, 50 % and 95 % of the fleet lie -- without x_hist / u_hist leaving the device.
+ *      The rule.  For a recorded tick and row r of the slot -- the same rows in the same order x | u | err | viol, the same values the slot's
+ *      statistic is made of: a held instance has no u rows, no instance has err rows off an observer tick, viol is vmax --
+ *        V    the instances whose value is finite; n = |V| is the n of the row's statistic in the slot
+ *        key  V is ordered ascending by the key of the value's 64 bits b:  key = b ^ (b >> 63 ? ~0ull : 1ull << 63)  -- numeric order, with
+ *             -0.0 before +0.0
+ *        k    for a level p:  c = ceil(p * (double)n), one FP64 multiply, then ceil;  k = min(n - 1, max(0, c - 1));  the quantile is the
+ *             k-th element, 0-based.  p = 0 gives the minimum, p = 1 the maximum, p = 0.5 with n even the lower median (numpy's
+ *             method="inverted_cdf")
+ *        n == 0: the quiet NaN with bits 0x7FF8000000000000
+ *      An order statistic is an element of the data: the result has one right set of bytes, whatever the grid or the occupancy.
+ *      Levels: at most COPRA_TRACE_QUANT_MAX, each finite in [0, 1]; they need not be sorted and may repeat.  `levels` is a host array.
+ *      The buffer: [capacity][rows][count] doubles beside the slots; slot k of one belongs to slot k of the other.
+ *      Lifetime: copra_batch_set_trace_quantiles needs tracing on; it waits for the handle's last stream once, takes the buffer and the key
+ *      buffer the kernel works in ([rows][batch] 64-bit keys) and RESTARTS the trace -- tick count, recorded and missed go to 0 --, so every
+ *      recorded slot has its quantiles.  levels == NULL or count == 0 ends quantiles and keeps the trace and its slots.  Quantiles belong to
+ *      the trace in force: copra_batch_set_trace, whether it replaces the trace or ends it with NULL, ends them too;
+ *      copra_batch_trace_reset keeps them.  copra_batch_trace_quantile_info reports the levels (`levels` has room for
+ *      COPRA_TRACE_QUANT_MAX, entries past count are 0; each pointer may be NULL); copra_batch_trace_quantiles_device returns the buffer
+ *      (NULL while quantiles are off); copra_batch_get_trace_quantiles waits for the last tick and copies slots [first, first + count),
+ *      checked against the recorded slots as copra_batch_get_trace checks them.
+ *      The tick: a recorded tick launches ONE kernel more behind the trace's two, on the tick's stream, into the slot the host counted: one
+ *      workgroup per row, a radix select on the key, eight passes of eight bits over histograms in LDS (integer atomics).  No
+ *      synchronisation, no allocation, no counter on the device, no floating-point atomics.  A full trace records nothing further, a tick
+ *      that `every` skips launches nothing, and while quantiles were never enabled the tick launches what it launched in ABI 17.
+ *      Exact quantiles of shards do not merge: there is no counterpart of merging two slots.
+ *      COPRA_ERR_ARG: a NULL handle, count outside 0 .. COPRA_TRACE_QUANT_MAX, a level that is NaN or outside [0, 1], a NULL destination,
+ *      first / count outside the recorded slots.  COPRA_ERR_RUNTIME: tracing off; info or get while quantiles are off. ---- */
+#define COPRA_TRACE_QUANT_MAX 8
+copra_status_t copra_batch_set_trace_quantiles(copra_batch_t* h, const double* levels, int count);
+copra_status_t copra_batch_trace_quantile_info(const copra_batch_t* h, int* count, double* levels /* [COPRA_TRACE_QUANT_MAX], may be NULL */);
+const double* copra_batch_trace_quantiles_device(const copra_batch_t* h);
+copra_status_t copra_batch_get_trace_quantiles(copra_batch_t* h, long long first, long long count, double* host);
 
 /* ---- reference schedules: tracking inside the tick.  The reference's API has no setter for a cost's p (include/costFunctions.h:103-219: a
  *      constructor argument); a tracking loop replaces the cost object every tick and the next solve evaluates the new one
